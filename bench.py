@@ -5,6 +5,12 @@ A "step" is one full timestep of the selected scheme (default: ECSIM = first_pus
 assembly, implicit field solve, second_push, field update) of BASELINE.json's headline configuration: 256^3 cells,
 64 particles per cell, one electron species, uniform B0 -- all resident in HBM before the timed region.
 
+A plain run (`python bench.py --gpus 1 --steps K --warmup W`) sets up, warms up, times K steps and prints one JSON line;
+the figures it derives from the library's own timers of those steps (phases, rooflines) ride along.  `--full` adds the
+measurements that take runs of their own: the CPU oracle baseline (`cpu_baseline`), the device copy probe
+(`device_copy_GBps`) and, for `--scheme basic`, the CG solve on matM (`cg_matM`); without it those fields are null.
+`--dump-outputs DIR` writes what the last timed step computed (see dump_outputs) for output-by-output comparisons.
+
 One process per GPU.  `python bench.py --gpus N` with N > 1 and no WORLD_SIZE in the environment STARTS the N ranks
 itself (fresh child processes, one per GPU, RCCL over xGMI; the parent never touches the GPU); under
 `python -m torch.distributed.run --nproc-per-node N bench.py --gpus N` each process is one of the ranks.
@@ -24,6 +30,7 @@ os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")  # dmabuf IPC only on t
 HBM_PEAK_GBS = 8000.0   # MI355X HBM3E spec peak (MI355X_MICROARCH.md); ~6.3 TB/s is the measured copy rate
 FP64_PEAK_TF = 78.6     # fp64 vector = fp64 matrix peak of MI355X (measured with v_mfma_f64_16x16x4: 75.5)
 FILL_FLOP_PER_PARTICLE = 1200.0  # 576 products + adds of decompose_ecsim_current + the per-particle algebra
+DUMP_VALUES = 1 << 20   # --dump-outputs: values kept of each grid array (summed over the ranks), ~8 MB in float64
 
 
 def parse_args(argv=None):
@@ -49,12 +56,20 @@ def parse_args(argv=None):
     ap.add_argument("--drift", type=float, default=None,
                     help="basic: beam momentum +-drift (m c) of the two electron species along x (default 0.2: the two-stream "
                          "set-up of BASELINE configs[1]; 0: two thermal species)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need, each outside the timed region: the CPU "
+                         "oracle baseline, the device copy probe and (--scheme basic) the CG solve on matM.  Without it a "
+                         "run sets up, warms up, times the steps, writes --dump-outputs and prints the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed to DIR/<name>.npy (float64): E, B, "
+                         "the charge density of every species (a fixed, seeded sample of at most %d values each), the "
+                         "energies, the momenta and the Krylov iterations of that step" % DUMP_VALUES)
     ap.add_argument("--cpu-grid", type=int, default=64)   # 64^3 x ppc, as SURVEY 8(d) asks: ~20 s of oracle work
     ap.add_argument("--cpu-steps", type=int, default=2)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU oracle baseline")
     ap.add_argument("--no-probe", dest="probe", action="store_false",
-                    help="skip the device copy probe (1 GiB device-to-device copies: the achievable copy rate of THIS box, "
-                         "SURVEY 8(d); on by default, outside the timed region)")
+                    help="--full without the device copy probe (1 GiB device-to-device copies: the achievable copy rate of "
+                         "THIS box, SURVEY 8(d); outside the timed region)")
     ap.add_argument("--plain-gmres", action="store_true", help="unpreconditioned GMRES(30), as the CPU oracle runs")
     ap.add_argument("--fused-rebin", type=int, default=None, choices=[0, 1, 2],
                     help="ecsim: 1 the re-binning's scatter deferred into the assembly's particle loads, 0 scatter first (default: the library's)")
@@ -67,6 +82,8 @@ def parse_args(argv=None):
                     help="ecsim is the headline workload (BASELINE configs[2]); basic = configs[1], ecsimcorr = configs[4] "
                          "at one GPU's share: side measurements")
     args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     side = args.scheme != "ecsim"
     if args.grid is None:
         args.grid = 128 if side else 256
@@ -279,6 +296,43 @@ def species(args):
     return [(args.ppc, 1.0, -1.0, 1.0)]
 
 
+def sample_index(size, k, seed):
+    """sorted flat indices of a fixed, seeded sample of at most k of `size` values; None = keep them all"""
+    import numpy as np
+
+    if size <= k:
+        return None
+    return np.unique(np.random.default_rng(seed).integers(0, size, k))
+
+
+def dump_outputs(args, ctx, sorts, its_last, rank, world):
+    """--dump-outputs DIR: what a caller of the timed path receives after its last step, as DIR/<name>.npy in float64.
+    The fields and the charge densities (the particles' positions, independent of their order inside a cell, which the
+    binning's atomics decide) are sampled at the same seeded indices in every run with the same arguments; with N > 1
+    ranks every rank writes its own slab as <name>_r<rank>.npy."""
+    import numpy as np
+    import xpic_amd as X
+
+    os.makedirs(args.dump_outputs, exist_ok=True)
+    suffix = f"_r{rank}" if world > 1 else ""
+    k = DUMP_VALUES // world
+
+    def save(name, a):
+        np.save(os.path.join(args.dump_outputs, name + suffix + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+    def sampled(a, seed):
+        idx = sample_index(a.size, k, seed)
+        return a if idx is None else a.reshape(-1)[idx]
+
+    for name, fid in (("E", X.E), ("B", X.B)):
+        save(name, sampled(ctx.get_field(fid), 11))
+    for i, s in enumerate(sorts):
+        save(f"charge_density_{i}", sampled(ctx.charge_density(s), 13))
+    save("energy", ctx.energy())
+    save("momentum", ctx.momentum())
+    save("ksp_iterations", np.array([its_last], dtype=np.float64))
+
+
 PMC_FILES = {"ecsim": "pmc_traffic_256.txt", "basic": "pmc_traffic_basic_128.txt", "ecsimcorr": "pmc_traffic_ecsimcorr_128.txt"}
 
 
@@ -486,7 +540,7 @@ def rank_body(args, rank, world, local_rank, job):
         ctx.set_preconditioner(0)
     elif (args.cheb_degree > 0 or args.precond is not None) and args.scheme != "basic":
         ctx.set_preconditioner(args.precond if args.precond is not None else 1, args.cheb_degree)
-    copy_rate = ctx.probe_copy_bandwidth(1 << 30, 5) if args.probe else None
+    copy_rate = ctx.probe_copy_bandwidth(1 << 30, 5) if args.full and args.probe else None
     for _ in range(args.warmup):
         ctx.step()
     ctx.profile_enable(True)
@@ -496,7 +550,8 @@ def rank_body(args, rank, world, local_rank, job):
     t0 = time.perf_counter()
     its = 0
     for _ in range(args.steps):
-        its += ctx.step()
+        its_last = ctx.step()
+        its += its_last
     barrier()
     elapsed = time.perf_counter() - t0
     comm = ctx.comm_stats()
@@ -504,7 +559,7 @@ def rank_body(args, rank, world, local_rank, job):
     its_total = job.reduce(its, "sum")
 
     cg_line = None
-    if args.scheme == "basic" and world == 1:
+    if args.full and args.scheme == "basic" and world == 1:
         # BASELINE.json configs[1] asks for "Poisson CG": the reference has no Poisson solve; its SPD operator is
         # matM = 2 I + 0.5 dt^2 rot- rot+ (Config 2) -> CG on matM with a manufactured right-hand side
         rng = np.random.default_rng(7)
@@ -721,8 +776,11 @@ def rank_body(args, rank, world, local_rank, job):
             line["roofline_esirkepov"] = esk
             line["roofline_assembly"] = fill
         line["roofline_spmv"] = spmv
+    if args.dump_outputs:
+        ctx.profile_enable(False)
+        dump_outputs(args, ctx, sorts, its_last, rank, world)
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(args)
         else:
             line["cpu_baseline"] = None

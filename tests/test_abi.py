@@ -74,7 +74,7 @@ def test_product_does_not_reference_the_oracle():
                 assert "oracle" not in txt.lower(), os.path.join(dirpath, f)
 
 
-def test_host_mirror_selftest():
+def test_host_mirror_selftest(tmp_path):
     """Host logic of the C++ mirror (JSON reader, Builder::parse_value units, TableDiagnostic text format against
     literal lines of the reference's golden tables) -- runs without a GPU."""
     import subprocess
@@ -84,7 +84,7 @@ def test_host_mirror_selftest():
         import __graft_entry__
 
         __graft_entry__.build()
-    out = subprocess.run([exe, "--selftest"], capture_output=True, text=True, timeout=60)
+    out = subprocess.run([exe, "--selftest", str(tmp_path)], capture_output=True, text=True, timeout=60)
     assert out.returncode == 0 and "selftest ok" in out.stdout, out.stdout + out.stderr
 
 

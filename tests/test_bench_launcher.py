@@ -5,6 +5,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -58,7 +59,7 @@ def test_launcher_does_not_touch_the_gpu_or_exec():
     assert out.returncode == 0 and out.stdout.startswith("gpus"), out.stdout + out.stderr
 
 
-def test_launcher_stops_ranks_that_hang():
+def test_launcher_stops_ranks_that_hang(tmp_path):
     """A rank stuck in a collective must not hang the parent: on the wall-clock limit the launcher terminates (then kills)
     the children it started and exits non-zero.  Here the 'ranks' are stand-ins that ignore SIGTERM and sleep."""
     code = r"""
@@ -66,27 +67,28 @@ import os, sys, time
 sys.path.insert(0, %r)
 import bench
 bench.count_gpus = lambda: 2
-hang = os.path.join(%r, 'tests', '_hang_rank.py')
+hang = os.path.join(%r, '_hang_rank.py')
 open(hang, 'w').write('import signal, time\nsignal.signal(signal.SIGTERM, signal.SIG_IGN)\ntime.sleep(600)\n')
 real_popen = bench.subprocess.Popen
 bench.subprocess.Popen = lambda cmd, env=None: real_popen([sys.executable, hang], env=env)
 args = bench.parse_args(['--gpus', '2', '--grid', '32', '--rank-timeout', '2'])
 t0 = time.time()
 rc = bench.launch_ranks(args, [])
-os.unlink(hang)
 print('rc', rc, 'after', round(time.time() - t0, 1))
-""" % (ROOT, ROOT)
+""" % (ROOT, str(tmp_path))
     out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=120)
     assert out.returncode == 0, out.stdout + out.stderr
     assert "rc 124" in out.stdout and "did not finish within" in out.stderr
 
 
 @pytest.mark.gpu
-def test_two_rank_rehearsal_reports_two_ranks():
+def test_two_rank_rehearsal_reports_two_ranks(tmp_path):
     """`bench.py --gpus 2` on the one-GPU box: two child ranks share GPU 0, exchange over gloo (XPIC_BENCH_COMM=gloo),
-    the line says n_gpus = 2 (read back from the communicator) and no particle is lost."""
+    the line says n_gpus = 2 (read back from the communicator) and no particle is lost; --dump-outputs writes every
+    rank's slab."""
     out = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--grid", "32", "--ppc", "8", "--steps", "2", "--warmup", "1",
-                          "--no-cpu-baseline"], env=_env(XPIC_BENCH_COMM="gloo"), capture_output=True, text=True, timeout=500)
+                          "--no-cpu-baseline", "--dump-outputs", str(tmp_path)], env=_env(XPIC_BENCH_COMM="gloo"),
+                         capture_output=True, text=True, timeout=500)
     assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, out.stdout
@@ -94,6 +96,10 @@ def test_two_rank_rehearsal_reports_two_ranks():
     assert line["n_gpus"] == 2 and line["steps"] == 2 and line["scaling"] == "strong"
     assert line["config"]["particles_per_gpu"] == 8 * 32 * 32 * 16
     assert line["value"] > 0 and line["ksp_iterations_per_step"] > 0
+    for r in range(2):
+        assert np.load(tmp_path / f"E_r{r}.npy").shape == (16, 32, 32, 3)
+        assert np.load(tmp_path / f"charge_density_0_r{r}.npy").shape == (16, 32, 32)
+    assert np.array_equal(np.load(tmp_path / "energy_r0.npy"), np.load(tmp_path / "energy_r1.npy"))  # global sums
 
 
 @pytest.mark.gpu
@@ -124,7 +130,7 @@ def test_eight_rank_rehearsal_in_one_process():
 
 @pytest.mark.gpu
 def test_single_rank_line_has_the_contract_fields():
-    out = subprocess.run([sys.executable, BENCH, "--grid", "32", "--ppc", "16", "--steps", "2", "--warmup", "1",
+    out = subprocess.run([sys.executable, BENCH, "--grid", "32", "--ppc", "16", "--steps", "2", "--warmup", "1", "--full",
                           "--cpu-grid", "16", "--cpu-steps", "1"], env=_env(), capture_output=True, text=True, timeout=500)
     assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-3000:]
     line = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][0])
@@ -145,6 +151,69 @@ def test_single_rank_line_has_the_contract_fields():
     assert line["roofline_spmv"]["bound"] == "hbm"
     c = line["cpu_baseline"]
     assert c["kind"] == "port" and c["cores"] >= 1 and c["ksp_iters_per_s_at_sample_grid"] > 0
+    assert line["device_copy_GBps"] > 0
+
+
+@pytest.mark.gpu
+def test_plain_run_is_lean_and_dumps_the_last_step(tmp_path):
+    """Without --full the line carries the headline and the figures of the timed steps only (no CPU baseline, no copy
+    probe); --dump-outputs writes the LAST timed step's outputs in float64: 1 warm-up + 3 timed steps and 3 warm-up + 1
+    timed step end on the same 4th step and dump the same arrays, while the state after 1 step is a different one."""
+    lines, dumps = [], []
+    for k, (warmup, steps) in enumerate(((1, 3), (3, 1), (0, 1))):
+        d = tmp_path / f"run{k}"
+        out = subprocess.run([sys.executable, BENCH, "--grid", "32", "--ppc", "16", "--steps", str(steps), "--warmup",
+                              str(warmup), "--dump-outputs", str(d)], env=_env(), capture_output=True, text=True, timeout=500)
+        assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-3000:]
+        found = [l for l in out.stdout.splitlines() if l.startswith("{")]
+        assert len(found) == 1, out.stdout
+        lines.append(json.loads(found[0]))
+        dumps.append({p.stem: np.load(p) for p in sorted(d.glob("*.npy"))})
+    line = lines[0]
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert key in line, key
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["dtype"] == "f64" and line["unit"] == "particles/s"
+    assert line["value"] == pytest.approx(16 * 32 ** 3 / (line["ms_per_step"] * 1e-3), rel=1e-9)
+    assert line["cpu_baseline"] is None and line["device_copy_GBps"] is None
+    a, b, c = dumps
+    assert sorted(a) == ["B", "E", "charge_density_0", "energy", "ksp_iterations", "momentum"]
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    assert a["E"].shape == (32, 32, 32, 3) and a["charge_density_0"].shape == (32, 32, 32)  # small grids: whole arrays
+    assert a["ksp_iterations"][0] > 0 and np.abs(a["E"]).max() > 0
+    # one timed step: the dumped Krylov iterations are that step's, as the line counts them
+    for l, dump in ((lines[1], b), (lines[2], c)):
+        assert l["steps"] == 1 and dump["ksp_iterations"][0] == l["ksp_iterations_per_step"]
+    for name in a:
+        assert a[name].dtype == np.float64 and np.all(np.isfinite(a[name])), name
+        # the same inputs and the same 4 steps; only the order of the atomic sums differs between two runs
+        assert np.abs(a[name] - b[name]).max() <= 1e-6 * max(np.abs(b[name]).max(), 1e-30), name
+    assert np.abs(a["E"] - c["E"]).max() > 1e-3 * np.abs(a["E"]).max()  # the 4th step's fields are not the 1st's
+
+
+def test_plain_and_full_arguments():
+    """--full is off unless asked for; --steps sets the timed steps and must be at least one."""
+    sys.path.insert(0, ROOT)
+    import bench
+
+    a = bench.parse_args(["--steps", "7", "--warmup", "2"])
+    assert not a.full and a.dump_outputs is None and a.steps == 7 and a.warmup == 2
+    b = bench.parse_args(["--full", "--dump-outputs", "out"])
+    assert b.full and b.dump_outputs == "out"
+    with pytest.raises(SystemExit):
+        bench.parse_args(["--steps", "0"])
+
+
+def test_dump_sample_is_fixed_and_bounded():
+    """--dump-outputs keeps at most DUMP_VALUES of a grid array, at the same seeded indices in every run."""
+    sys.path.insert(0, ROOT)
+    import bench
+
+    assert bench.sample_index(1000, 4096, 11) is None
+    i, j = bench.sample_index(3 * 256 ** 3, bench.DUMP_VALUES, 11), bench.sample_index(3 * 256 ** 3, bench.DUMP_VALUES, 11)
+    assert np.array_equal(i, j) and 0.98 * bench.DUMP_VALUES < len(i) <= bench.DUMP_VALUES
+    assert np.all(np.diff(i) > 0) and i[0] >= 0 and i[-1] < 3 * 256 ** 3
+    # the largest dump of a headline-sized run: E, B and the charge densities of two species, 8 bytes a value
+    assert 4 * bench.DUMP_VALUES * 8 <= 64 << 20
 
 
 def test_pmc_traffic_is_quoted_only_for_the_sources_it_was_taken_on(tmp_path, monkeypatch):

@@ -1,10 +1,13 @@
 # copies the artifacts of tools/final_bench.sh <tag> from gpurun_out/ into profiles/${P}_*:  tools/copy_final.sh <tag>
+# The four bench.py --full lines come from BENCH_OUT (default bench_out/, as in final_bench.sh); stops at the first missing file.
+set -e
 T=${1:-r04}; P=${2:-r04}
 cd /root/repo
-cp gpurun_out/bench_256_$T.json profiles/${P}_bench_256.json
-cp gpurun_out/bench_basic_$T.json profiles/${P}_bench_basic_128.json
-cp gpurun_out/bench_ecsimcorr_$T.json profiles/${P}_bench_ecsimcorr_128.json
-cp gpurun_out/bench_cfg4_$T.json profiles/${P}_bench_cfg4_512x512x64.json
+OUT=${BENCH_OUT:-bench_out}
+cp $OUT/bench_256_$T.json profiles/${P}_bench_256.json
+cp $OUT/bench_basic_$T.json profiles/${P}_bench_basic_128.json
+cp $OUT/bench_ecsimcorr_$T.json profiles/${P}_bench_ecsimcorr_128.json
+cp $OUT/bench_cfg4_$T.json profiles/${P}_bench_cfg4_512x512x64.json
 cp gpurun_out/bench_n2_rehearsal_$T.json profiles/${P}_bench_n2_gloo_rehearsal_128.json
 cp gpurun_out/bench_n8_threads_$T.json profiles/${P}_bench_n8_threads_rehearsal_256.json
 cp "$(ls -t gpurun_out/prof_$T/runc/*_kernel_stats.csv | head -1)" profiles/${P}_rocprofv3_kernel_stats_256.csv  # (the merged directory keeps older runs: the newest file)

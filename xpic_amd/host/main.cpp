@@ -1,20 +1,26 @@
 // main.cpp -- mirror of the reference's src/main.cpp:9-40: configuration -> build_simulation -> initialize ->
 // calculate -> finalize, exceptions reported and turned into a non-zero exit.
 //   usage: xpic_hip.out <config.json> [output directory override]
+//          xpic_hip.out --selftest [scratch directory, default /tmp/xpic_selftest]
 #include <fstream>
 #include <iostream>
 
 #include "xpic_host.h"
 
 // Host-logic self test (no GPU needed): the JSON reader, Builder::parse_value and the table text format,
-// checked against literal lines of the reference's golden files.
-static int selftest()
+// checked against literal lines of the reference's golden files.  Writes one table under `dir`.
+static int selftest(const std::string& dir)
 {
   int bad = 0;
   auto expect = [&](bool ok, const char* what) {
     if (!ok) { std::cerr << "selftest FAILED: " << what << "\n"; ++bad; }
   };
-  Configuration::overwrite(xjson::parse(R"({"OutputDirectory": "/tmp/xpic_selftest", "Simulation": "ecsim",
+  std::string dir_json;
+  for (char ch : dir) {
+    if (ch == '"' || ch == '\\') dir_json += '\\';
+    dir_json += ch;
+  }
+  Configuration::overwrite(xjson::parse(R"({"OutputDirectory": ")" + dir_json + R"(", "Simulation": "ecsim",
     "Geometry": {"x": "2 [dx]", "y": 5.0, "z": "32 [dz]", "t": "30 [1/w_pe]", "dx": 0.5, "dy": 0.5, "dz": 0.25,
       "dt": 0.1, "diagnose_period": "100 [dt]", "da_boundary_x": "DM_BOUNDARY_PERIODIC",
       "da_boundary_y": "DM_BOUNDARY_PERIODIC", "da_boundary_z": "DM_BOUNDARY_PERIODIC"},
@@ -48,12 +54,12 @@ static int selftest()
         ++row;
         return 0;
       }
-    } tab("/tmp/xpic_selftest/temporal/t.txt");
+    } tab(dir + "/temporal/t.txt");
     tab.diagnose(0);
     tab.diagnose(1);
     tab.finalize();
   }
-  std::ifstream f("/tmp/xpic_selftest/temporal/t.txt");
+  std::ifstream f(dir + "/temporal/t.txt");
   std::string l0, l1, l2;
   std::getline(f, l0); std::getline(f, l1); std::getline(f, l2);
   expect(l0 == "Time    dE             dB             dK_electrons   dE+dB+dK", "table header");
@@ -65,7 +71,7 @@ static int selftest()
 
 int main(int argc, char** argv)
 {
-  if (argc == 2 && std::string(argv[1]) == "--selftest") return selftest();
+  if ((argc == 2 || argc == 3) && std::string(argv[1]) == "--selftest") return selftest(argc == 3 ? argv[2] : "/tmp/xpic_selftest");
   if (argc < 2) {
     std::cerr << "usage: " << argv[0] << " <config.json> [output directory]\n";
     return 2;
