@@ -71,7 +71,7 @@ const char* xpic_last_error(void);
 /* XPIC_VERSION, with XPIC_VERSION_EXPERIMENT_BIT set when any object of the library was built with -DXPIC_EXPERIMENT
  * (ablation switches and in-kernel timers of the kernels; some produce wrong physics by design): refuse such a library
  * for production runs. */
-#define XPIC_VERSION 2
+#define XPIC_VERSION 3
 #define XPIC_VERSION_EXPERIMENT_BIT 0x40000000
 int xpic_version(void);
 
@@ -264,6 +264,43 @@ int xpic_charge_density(xpic_ctx* ctx, int sort, double* rho_zyx);
 /* DistributionMoment::collect with moment "density" (src/diagnostics/distribution_moment.cpp:125-216): cell-centred
  * first-order deposit of n/Np -> out[z][y][x].  Uses the scratch vector XPIC_W2. */
 int xpic_moment_density(xpic_ctx* ctx, int sort, double* out_zyx);
+/* DistributionMoment::collect of one sort with any of its six moments (src/diagnostics/distribution_moment.cpp:157-298,
+ * builder builders/distribution_moment_builder.cpp:16-23): cell-centred first-order deposit of moment(p) * n/Np from
+ * round(r/d - 1) over 2 x 2 x 2 cells.  region6 = {start x, y, z, size x, y, z} in global cells (NULL: the whole box).  The
+ * reference's region rule (:59-108, :157-210): a particle counts iff its storage cell lies in the region; a deposit lands
+ * iff its cell lies in the region, after a periodic wrap on each axis the region spans in full.  out[nzl][ny][nx][dof]
+ * over the local slab (the reference's DOF layout), zero outside the region; dof = 1, 3, 6, 3, 6, 3 in the order of
+ * enum xpic_moment_kind.  Collective over the z-slabs (ghost-plane deposits go to their owner).  Uses the scratch vector
+ * XPIC_W2, and XPIC_W1 as well for the 6-component moments. */
+enum xpic_moment_kind {
+  XPIC_MOMENT_DENSITY = 0,            /* get_density (:212-216), dof 1 */
+  XPIC_MOMENT_CURRENT = 1,            /* get_current (:218-224): q v, dof 3 */
+  XPIC_MOMENT_MOMENTUM_FLUX = 2,      /* get_momentum_flux (:226-239): m v_i v_j, i <= j, dof 6 */
+  XPIC_MOMENT_MOMENTUM_FLUX_DIAG = 3, /* get_momentum_flux_diag (:241-251): m v_i v_i, dof 3 */
+  XPIC_MOMENT_MOMENTUM_FLUX_CYL = 4,  /* get_momentum_flux_cyl (:279-292): (r, phi, z) about (geom_x/2, geom_y/2), dof 6 */
+  XPIC_MOMENT_MOMENTUM_FLUX_DIAG_CYL = 5 /* get_momentum_flux_diag_cyl (:294-304), dof 3 */
+};
+int xpic_moment(xpic_ctx* ctx, int sort, int kind, const int region6[6], double* out);
+/* VelocityDistribution::collect (src/diagnostics/velocity_distribution.cpp:112-163; builder
+ * builders/velocity_distribution_builder.cpp:13-115): a cell counts iff it lies in the geometry's AABB (FLOOR_STEP of the
+ * bounds) and its centre (g + 0.5) d passes WithinBox / WithinCylinder (src/utils/geometries.cpp:3-19); each of its
+ * particles adds n/Np to bin (ROUND_STEP(v1, dvx), ROUND_STEP(v2, dvy)) (std::round: half away from zero), bins outside the
+ * histogram are dropped.  geom = {min x, y, z, max x, y, z} (box) or {center x, y, z, radius, height} (cylinder);
+ * vreg = {vx_min, vy_min, vx_max, vy_max, dvx, dvy}.  As the reference's set_regions (:57-68) WRITES it, both axes start
+ * at ROUND_STEP(vx_min, dvx) and have ROUND_STEP(vx_max - vx_min, dvx) bins: vy_min, vy_max never enter (dvy does, as the
+ * bin width of v2).  vgrid4 = {vsize_x, vsize_y, vstart_x, vstart_y}: column i of out holds the bin vstart_x + i (vstart
+ * = ROUND_STEP(vx_min, dvx), half away from zero); out[vsize_y][vsize_x] (NULL: the sizes and starts only), the whole
+ * histogram on every z-slab (collective: the VecScatter ADD, :159-160).  At most 2^15 bins per axis.  Uses the scratch
+ * vector XPIC_W0; a histogram of more bins than a field vector holds (a fine histogram on a small grid) takes a device
+ * buffer of its own for the call. */
+enum xpic_projector {
+  XPIC_PROJ_VX_VY = 0,  /* get_vx_vy (:166-169) */
+  XPIC_PROJ_VZ_VXY = 1, /* get_vz_vxy (:171-175): (vz, |(vx, vy)|) */
+  XPIC_PROJ_VR_VPHI = 2 /* get_vr_vphi (:177-193): about (geom_x/2, geom_y/2) */
+};
+enum xpic_vgeometry { XPIC_GEOM_BOX = 0, XPIC_GEOM_CYLINDER = 1 };
+int xpic_velocity_distribution(xpic_ctx* ctx, int sort, int projector, int geometry, const double geom[7],
+  const double vreg[6], int* vgrid4, double* out);
 /* ChargeConservation (charge_conservation.cpp:117-171): xpic_charge_collect() = initialize(); then once per step
  * xpic_charge_columns(): out = {N1dQ_0, N2dQ_0, ..., N1dQ_tot, N2dQ_tot} of (rho_new - rho_old)/dt + div(-) J.
  * Uses the scratch vectors XPIC_W0..W2. */

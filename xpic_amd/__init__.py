@@ -28,7 +28,7 @@ SYMBOLS = [
     "xpic_update_cells", "xpic_ecsim_fill_current", "xpic_ecsim_second_push", "xpic_basic_push",
     "xpic_ecsimcorr_first_push", "xpic_ecsimcorr_second_push", "xpic_ecsimcorr_final_update",
     "xpic_calculate_energy", "xpic_ecsimcorr_scalars", "xpic_solve", "xpic_set_tolerances", "xpic_set_preconditioner", "xpic_set_overlap", "xpic_comm_stats", "xpic_set_fill_kernel", "xpic_set_fused_rebin", "xpic_get_fill_variant", "xpic_debug_set", "xpic_step",
-    "xpic_energy", "xpic_momentum", "xpic_charge_density", "xpic_moment_density", "xpic_cell_traversal", "xpic_implicit_esirkepov_interpolate",
+    "xpic_energy", "xpic_momentum", "xpic_charge_density", "xpic_moment_density", "xpic_moment", "xpic_velocity_distribution", "xpic_cell_traversal", "xpic_implicit_esirkepov_interpolate",
     "xpic_implicit_esirkepov_decompose", "xpic_charge_collect", "xpic_charge_columns", "xpic_comm_rccl_unique_id", "xpic_comm_init_rccl", "xpic_comm_init_callbacks", "xpic_comm_size", "xpic_comm_peer_export", "xpic_comm_peer_import",
     "xpic_profile_enable", "xpic_profile_reset", "xpic_profile_get", "xpic_probe_copy_bandwidth",
 ]
@@ -56,6 +56,14 @@ class Geometry(C.Structure):
     _fields_ = [("n", C.c_int32 * 3), ("d", C.c_double * 3), ("dt", C.c_double), ("periodic", C.c_int32 * 3),
                 ("rank", C.c_int32), ("nranks", C.c_int32), ("device", C.c_int32), ("self_ring", C.c_int32)]
 
+
+# include/xpic_hip.h: enum xpic_moment_kind (the reference's order) and the components of each moment
+MOMENTS = {"density": 0, "current": 1, "momentum_flux": 2, "momentum_flux_diag": 3, "momentum_flux_cyl": 4,
+           "momentum_flux_diag_cyl": 5}
+MOMENT_DOF = {"density": 1, "current": 3, "momentum_flux": 6, "momentum_flux_diag": 3, "momentum_flux_cyl": 6,
+              "momentum_flux_diag_cyl": 3}
+PROJECTORS = {"vx_vy": 0, "vz_vxy": 1, "vr_vphi": 2}  # enum xpic_projector
+GEOMETRIES = {"box": 0, "BoxGeometry": 0, "cylinder": 1, "CylinderGeometry": 1}  # enum xpic_vgeometry
 
 DEBUG_GATHER_WINDOW, DEBUG_PENCIL_LIMIT, DEBUG_SURROGATE_SCALE = 0, 1, 2  # include/xpic_hip.h: xpic_debug_set
 PEER_BLOB_BYTES = 256  # include/xpic_hip.h: XPIC_PEER_BLOB_BYTES
@@ -399,6 +407,34 @@ class Context:
         out = np.zeros((self.nzl, self.n[1], self.n[0]))
         self._ck(self.L.xpic_moment_density(self.h, sort, _dp(out)))
         return out
+
+    def moment(self, sort, name, region=None):
+        """DistributionMoment `name` of one sort (include/xpic_hip.h: xpic_moment) -> (nzl, ny, nx, dof) over this slab.
+        region: None (the whole box) or (start xyz, size xyz) in global cells, as six numbers or two triples."""
+        dof = MOMENT_DOF[name]
+        out = np.zeros((self.nzl, self.n[1], self.n[0], dof))
+        reg = None
+        if region is not None:
+            reg = (C.c_int * 6)(*[int(v) for v in np.asarray(region, dtype=np.int64).reshape(6)])
+        self._ck(self.L.xpic_moment(self.h, sort, MOMENTS[name], reg, _dp(out)))
+        return out
+
+    def velocity_distribution(self, sort, projector, geometry, vmin=(-1.0, -1.0), vmax=(1.0, 1.0), dv=(0.1, 0.1)):
+        """VelocityDistribution of one sort (include/xpic_hip.h: xpic_velocity_distribution) -> (array [vsize_y][vsize_x],
+        vstart (x, y)), the whole histogram on every slab.  geometry: {"name": "box", "min": xyz, "max": xyz} or
+        {"name": "cylinder", "center": xyz, "radius": r, "height": h} ("BoxGeometry" / "CylinderGeometry" as well)."""
+        kind = GEOMETRIES[geometry["name"]]
+        if kind == 0:
+            gp = list(geometry["min"]) + list(geometry["max"]) + [0.0]
+        else:
+            gp = list(geometry["center"]) + [geometry["radius"], geometry["height"], 0.0]
+        gp = np.array(gp, dtype=np.float64)
+        vreg = np.array([vmin[0], vmin[1], vmax[0], vmax[1], dv[0], dv[1]], dtype=np.float64)
+        vg = (C.c_int * 4)()  # vsize_x, vsize_y, vstart_x, vstart_y (include/xpic_hip.h)
+        self._ck(self.L.xpic_velocity_distribution(self.h, sort, PROJECTORS[projector], kind, _dp(gp), _dp(vreg), vg, None))
+        out = np.zeros((vg[1], vg[0]))
+        self._ck(self.L.xpic_velocity_distribution(self.h, sort, PROJECTORS[projector], kind, _dp(gp), _dp(vreg), vg, _dp(out)))
+        return out, (int(vg[2]), int(vg[3]))
 
     def cell_traversal(self, end, start, max_pts=8):
         end, start = np.ascontiguousarray(end, dtype=np.float64), np.ascontiguousarray(start, dtype=np.float64)

@@ -1,5 +1,6 @@
 // api.hip -- the C ABI of include/xpic_hip.h: context life cycle, boundary copies, per-phase entry points
 // and the timestep drivers that mirror timestep_implementation() of the reference's schemes.
+#include <algorithm>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -865,6 +866,56 @@ int xpic_moment_density(xpic_ctx* ctx, int sort, double* out_zyx)
   XPIC_CALL(field_export(ctx, tmp, v3.data()));
   for (long i = 0; i < ctx->g.nown; ++i) out_zyx[i] = v3[3 * i];
   return 0;
+}
+
+int xpic_moment(xpic_ctx* ctx, int sort, int kind, const int region6[6], double* out)
+{
+  CTX_CHECK(ctx); SORT_CHECK(sort);
+  XPIC_CHECK(out, "null argument");
+  const int D = moment_dof(kind);
+  XPIC_CHECK(D > 0, "unknown moment kind");
+  const GridDev& g = ctx->g;
+  double* comp[6];
+  for (int j = 0; j < 6; ++j) comp[j] = ctx->field[D > 3 ? XPIC_W1 + j / 3 : XPIC_W2] + (long)(j % 3) * g.cstride;
+  XPIC_CALL(moment_region(ctx, ctx->sorts[sort], kind, region6, comp));
+  std::vector<double> v3((size_t)g.nown * 3);
+  for (int v = 0; v < (D + 2) / 3; ++v) {
+    XPIC_CALL(field_export(ctx, comp[3 * v], v3.data()));
+    const int nc = std::min(3, D - 3 * v);
+    for (long i = 0; i < g.nown; ++i)
+      for (int j = 0; j < nc; ++j) out[i * D + 3 * v + j] = v3[3 * i + j];
+  }
+  return 0;
+}
+
+int xpic_velocity_distribution(xpic_ctx* ctx, int sort, int projector, int geometry, const double geom[7],
+  const double vreg[6], int* vgrid4, double* out)
+{
+  CTX_CHECK(ctx); SORT_CHECK(sort);
+  XPIC_CHECK(geom && vreg && vgrid4, "null argument");
+  int aabb[6], vs = 0, vn = 0;
+  XPIC_CALL(vdist_sizes(ctx->g, geometry, geom, vreg, aabb, &vs, &vn)); // (bounds the bin count before any allocation)
+  vgrid4[0] = vgrid4[1] = vn;
+  vgrid4[2] = vgrid4[3] = vs;
+  if (!out) return 0;
+  XPIC_CHECK(vn > 0, "velocity distribution: empty histogram (vmax <= vmin)");
+  const long nb = (long)vn * vn;
+  // the scratch vector XPIC_W0 when it holds the histogram; a finer histogram than a (small) field vector holds takes a
+  // buffer of its own for the call
+  double* hist = ctx->field[XPIC_W0];
+  const bool own = nb > ctx->nvec;
+  if (own) XPIC_HIP(hipMalloc(&hist, sizeof(double) * nb));
+  int rc = velocity_distribution(ctx, ctx->sorts[sort], projector, geometry, geom, vreg, hist);
+  if (rc == 0) {
+    hipError_t e = hipMemcpyAsync(out, hist, sizeof(double) * nb, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) {
+      set_error(std::string("velocity distribution read-back: ") + hipGetErrorString(e));
+      rc = 1;
+    }
+  }
+  if (own) (void)hipFree(hist);
+  return rc;
 }
 
 int xpic_charge_collect(xpic_ctx* ctx) // ChargeConservation::initialize, charge_conservation.cpp:117-123

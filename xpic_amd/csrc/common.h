@@ -351,6 +351,13 @@ int kinetic_sums_global(xpic_ctx* c, Sort& s, double* out5); // summed over the 
 int scale_velocities(xpic_ctx* c, Sort& s, double lambda);
 int momentum_sums_global(xpic_ctx* c, Sort& s, const double* E, double* out6);
 
+// moments.hip
+int moment_dof(int kind); // 0: unknown kind
+// comp[j]: component j of the deposit (stored field layout); comp[0] and comp[3] are the starts of whole vectors
+int moment_region(xpic_ctx* c, Sort& s, int kind, const int* region6, double* const* comp);
+int vdist_sizes(const GridDev& g, int geometry, const double* geom, const double* vreg, int* aabb6, int* vs, int* vn);
+int velocity_distribution(xpic_ctx* c, Sort& s, int projector, int geometry, const double* geom, const double* vreg, double* hist);
+
 // ecsim.hip
 int ecsim_fill_sort(xpic_ctx* c, Sort& s, const double* B, double* currI_sort, double* matL, bool first_sort, bool post_ghost_rows);
 int ecsim_fill_check(xpic_ctx* c); // the assembly's device-side error word, agreed on by all slabs (once per assembly)

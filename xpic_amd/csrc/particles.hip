@@ -1256,6 +1256,7 @@ int moment_density(xpic_ctx* c, Sort& s, double* vec)
   XPIC_CALL(sort_materialize(c, s)); // (a deferred re-binning whose assembly has not run)
   XPIC_HIP(hipMemsetAsync(vec, 0, sizeof(double) * c->nvec, c->stream));
   if (s.n > 0) {
+    Timed t(c, "moment_density");
     hipLaunchKernelGGL(k_moment_density, dim3(pgrid(s.n)), dim3(kBlock), 0, c->stream, c->g, s.d, s.n,
       s.par.n / s.par.Np, vec);
     XPIC_HIP(hipGetLastError());

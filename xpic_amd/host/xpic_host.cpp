@@ -538,15 +538,42 @@ PetscErrorCode FieldView::diagnose(PetscInt t)
 }
 
 DistributionMoment::DistributionMoment(const std::string& out_dir, interfaces::Simulation& simulation,
-  interfaces::Particles& particles, const Region& region)
-  : FieldView(out_dir, simulation, -1, region), particles_(particles)
+  interfaces::Particles& particles, int kind, const Region& region)
+  : FieldView(out_dir, simulation, -1, region), particles_(particles), kind_(kind)
 {
 }
 
+// DistributionMoment::collect (distribution_moment.cpp:157-210): only the region's particles and deposits count
 PetscErrorCode DistributionMoment::fetch(std::vector<double>& data)
 {
-  data.resize((size_t)geom_nx * geom_ny * geom_nz);
-  HIPCALL(xpic_moment_density(simulation.ctx, particles_.sort_id, data.data()));
+  data.resize((size_t)geom_nx * geom_ny * geom_nz * region_.dof);
+  const int region6[6] = {(int)region_.start[0], (int)region_.start[1], (int)region_.start[2], (int)region_.size[0],
+    (int)region_.size[1], (int)region_.size[2]};
+  HIPCALL(xpic_moment(simulation.ctx, particles_.sort_id, kind_, region6, data.data()));
+  return 0;
+}
+
+VelocityDistribution::VelocityDistribution(const std::string& out_dir, interfaces::Simulation& simulation,
+  interfaces::Particles& particles, int projector, int geometry, const double geom[7], const double vreg[6])
+  : simulation(simulation), particles_(particles), out_dir_(out_dir), projector_(projector), geometry_(geometry)
+{
+  std::copy(geom, geom + 7, geom_);
+  std::copy(vreg, vreg + 6, vreg_);
+}
+
+// DistributionMoment::diagnose + FieldView::diagnose (velocity_distribution.cpp:96-110): the whole histogram, float32
+PetscErrorCode VelocityDistribution::diagnose(PetscInt t)
+{
+  if (diagnose_period > 0 && t % diagnose_period != 0) return 0;
+  int vsize[4]; // vsize_x, vsize_y, vstart_x, vstart_y
+  HIPCALL(xpic_velocity_distribution(simulation.ctx, particles_.sort_id, projector_, geometry_, geom_, vreg_, vsize, nullptr));
+  std::vector<double> data((size_t)vsize[0] * vsize[1]);
+  HIPCALL(xpic_velocity_distribution(simulation.ctx, particles_.sort_id, projector_, geometry_, geom_, vreg_, vsize, data.data()));
+  std::vector<float> out(data.begin(), data.end());
+  make_dirs(out_dir_);
+  std::ofstream f(out_dir_ + "/" + FieldView::format_time(t), std::ios::binary);
+  if (!f) throw std::runtime_error("Cannot open " + out_dir_ + "/" + FieldView::format_time(t));
+  f.write(reinterpret_cast<const char*>(out.data()), (std::streamsize)(out.size() * sizeof(float)));
   return 0;
 }
 
@@ -640,21 +667,62 @@ PetscErrorCode build_diagnostics(interfaces::Simulation& simulation,
     }
     else if (name == "DistributionMoment") {
       const std::string particles = info.at("particles").as_string(), moment = info.at("moment").as_string();
-      static const char* known[] = {"density", "current", "momentum_flux", "momentum_flux_cyl", "momentum_flux_diag",
-        "momentum_flux_diag_cyl"};
-      if (std::find_if(std::begin(known), std::end(known), [&](const char* k) { return moment == k; }) == std::end(known))
-        throw std::runtime_error("Unknown moment name " + moment + " for particles " + particles);
-      if (moment != "density")
-        throw std::runtime_error("moment " + moment + " is not offered by the HIP backends (density only)");
-      region.dim = 3; region.dof = 1; region.size[3] = 1;
+      // distribution_moment_builder.cpp:16-23: name -> dof; here also -> enum xpic_moment_kind
+      static const struct { const char* name; int dof, kind; } known[] = {{"density", 1, XPIC_MOMENT_DENSITY},
+        {"current", 3, XPIC_MOMENT_CURRENT}, {"momentum_flux", 6, XPIC_MOMENT_MOMENTUM_FLUX},
+        {"momentum_flux_cyl", 6, XPIC_MOMENT_MOMENTUM_FLUX_CYL}, {"momentum_flux_diag", 3, XPIC_MOMENT_MOMENTUM_FLUX_DIAG},
+        {"momentum_flux_diag_cyl", 3, XPIC_MOMENT_MOMENTUM_FLUX_DIAG_CYL}};
+      const auto k = std::find_if(std::begin(known), std::end(known), [&](const auto& e) { return moment == e.name; });
+      if (k == std::end(known)) throw std::runtime_error("Unknown moment name " + moment + " for particles " + particles);
+      region.dim = k->dof > 1 ? 4 : 3; region.dof = k->dof; region.start[3] = 0; region.size[3] = k->dof;
       if (info.contains("region")) parse_region(info.at("region"), region, suffix, particles + " " + moment);
       check_region(region, particles + " " + moment);
       LOG("  " << moment << " diagnostic is added for " << particles << ", suffix: " << (suffix.empty() ? "<empty>" : suffix));
       if (!suffix.empty()) suffix = "_" + suffix;
       result.emplace_back(std::make_unique<DistributionMoment>(CONFIG().out_dir + "/" + particles + "/" + moment + suffix,
-        simulation, simulation.get_named_particles(particles), region));
+        simulation, simulation.get_named_particles(particles), k->kind, region));
     }
-    else throw std::runtime_error("Unknown diagnostic name " + name + " (HIP backends: FieldView, DistributionMoment)");
+    else if (name == "VelocityDistribution") { // velocity_distribution_builder.cpp:13-115
+      const std::string particles = info.at("particles").as_string(), projector = info.at("projector").as_string();
+      int proj = -1;
+      if (projector == "vx_vy") proj = XPIC_PROJ_VX_VY;
+      else if (projector == "vz_vxy") proj = XPIC_PROJ_VZ_VXY;
+      else if (projector == "vr_vphi") proj = XPIC_PROJ_VR_VPHI;
+      else throw std::runtime_error("Unkown projector name " + projector);
+      const auto& geometry = info.at("geometry");
+      const std::string gname = geometry.at("name").as_string();
+      int gkind;
+      double geom[7] = {0, 0, 0, 0, 0, 0, 0};
+      if (gname == "BoxGeometry") { // Builder::load_geometry (src/interfaces/builder.cpp:83-94): the whole box by default
+        gkind = XPIC_GEOM_BOX;
+        Vector3R mn, mx;
+        mx[0] = geom_x; mx[1] = geom_y; mx[2] = geom_z;
+        if (geometry.contains("min")) mn = Builder::parse_vector(geometry, "min");
+        if (geometry.contains("max")) mx = Builder::parse_vector(geometry, "max");
+        for (int i = 0; i < 3; ++i) { geom[i] = mn[i]; geom[3 + i] = mx[i]; }
+      }
+      else if (gname == "CylinderGeometry") { // (:96-113): centred, radius min(geom_x, geom_y) / 2, height geom_z
+        gkind = XPIC_GEOM_CYLINDER;
+        Vector3R c;
+        c[0] = 0.5 * geom_x; c[1] = 0.5 * geom_y; c[2] = 0.5 * geom_z;
+        if (geometry.contains("center")) c = Builder::parse_vector(geometry, "center");
+        for (int i = 0; i < 3; ++i) geom[i] = c[i];
+        geom[3] = geometry.contains("radius") ? geometry.at("radius").as_double() : 0.5 * std::min(geom_x, geom_y);
+        geom[4] = geometry.contains("height") ? geometry.at("height").as_double() : geom_z;
+      }
+      else throw std::runtime_error("Unknown geometry name " + gname);
+      double vreg[6] = {-1, -1, +1, +1, 0, 0}; // vx_min, vy_min, vx_max, vy_max, dvx, dvy
+      const auto& dv = info.at("dv");
+      vreg[4] = dv.arr.at(0).as_double();
+      vreg[5] = dv.arr.at(1).as_double();
+      if (info.contains("vmax")) { vreg[2] = info.at("vmax").arr.at(0).as_double(); vreg[3] = info.at("vmax").arr.at(1).as_double(); }
+      if (info.contains("vmin")) { vreg[0] = info.at("vmin").arr.at(0).as_double(); vreg[1] = info.at("vmin").arr.at(1).as_double(); }
+      LOG("  " << projector << " velocity distribution diagnostic is added for " << particles);
+      result.emplace_back(std::make_unique<VelocityDistribution>(CONFIG().out_dir + "/" + particles + "/" + projector, simulation,
+        simulation.get_named_particles(particles), proj, gkind, geom, vreg));
+    }
+    else throw std::runtime_error("Unknown diagnostic name " + name +
+      " (HIP backends: FieldView, DistributionMoment, VelocityDistribution)");
   }
   return 0;
 }

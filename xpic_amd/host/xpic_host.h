@@ -298,14 +298,31 @@ protected:
   Region region_;
 };
 
-class DistributionMoment final : public FieldView { // src/diagnostics/distribution_moment.cpp, moment "density"
+class DistributionMoment final : public FieldView { // src/diagnostics/distribution_moment.cpp, all six moments
 public:
+  // kind: enum xpic_moment_kind; the deposit follows the region rule of the reference (xpic_moment)
   DistributionMoment(const std::string& out_dir, interfaces::Simulation& simulation, interfaces::Particles& particles,
-    const Region& region);
+    int kind, const Region& region);
 
 protected:
   PetscErrorCode fetch(std::vector<double>& data) override;
   interfaces::Particles& particles_;
+  int kind_;
+};
+
+// src/diagnostics/velocity_distribution.cpp: <out_dir>/<time> = float32 [vsize_y][vsize_x] every diagnose_period steps
+class VelocityDistribution final : public interfaces::Diagnostic {
+public:
+  VelocityDistribution(const std::string& out_dir, interfaces::Simulation& simulation, interfaces::Particles& particles,
+    int projector, int geometry, const double geom[7], const double vreg[6]);
+  PetscErrorCode diagnose(PetscInt t) override;
+
+private:
+  interfaces::Simulation& simulation;
+  interfaces::Particles& particles_;
+  std::string out_dir_;
+  int projector_, geometry_;
+  double geom_[7], vreg_[6];
 };
 
 // ---- restart files (src/diagnostics/simulation_backup.cpp:30-160): <out_dir>/<t>/{E,B,B0} as PETSc binary Vecs
