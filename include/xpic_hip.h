@@ -71,7 +71,7 @@ const char* xpic_last_error(void);
 /* XPIC_VERSION, with XPIC_VERSION_EXPERIMENT_BIT set when any object of the library was built with -DXPIC_EXPERIMENT
  * (ablation switches and in-kernel timers of the kernels; some produce wrong physics by design): refuse such a library
  * for production runs. */
-#define XPIC_VERSION 3
+#define XPIC_VERSION 4
 #define XPIC_VERSION_EXPERIMENT_BIT 0x40000000
 int xpic_version(void);
 
@@ -301,6 +301,53 @@ enum xpic_projector {
 enum xpic_vgeometry { XPIC_GEOM_BOX = 0, XPIC_GEOM_CYLINDER = 1 };
 int xpic_velocity_distribution(xpic_ctx* ctx, int sort, int projector, int geometry, const double geom[7],
   const double vreg[6], int* vgrid4, double* out);
+/* ---- the per-step commands of an open system (src/commands/).  geometry / geom as in xpic_velocity_distribution.  Every
+ * call is collective over the z-slabs: the counts and energies it returns are summed over them. */
+/* RemoveParticles::execute (src/commands/remove_particles.cpp:11-40): every local cell whose CORNER (start + g) d fails
+ * WithinBox (half-open) / WithinCylinder (strict |z - center z| < height / 2) (src/utils/geometries.cpp:3-19) is emptied
+ * (VelocityDistribution tests the cell centre instead).  *removed = records removed, *energy = sum of 0.5 m v^2 n/Np over
+ * them (Energy::get_kinetic, src/diagnostics/energy.cpp:188-191).  The other cells keep their records in their order; when
+ * no failing cell holds a record, no record is touched. */
+int xpic_remove_particles(xpic_ctx* ctx, int sort, int geometry, const double geom[7], int64_t* removed, double* energy);
+/* FieldsDamping::execute (src/commands/fields_damping.cpp:15-111): on E and on B - B0 (B0 added back), every node whose
+ * point (x + 0.5, y + 0.5, z + 0.5) d -- the cell centre, for all three components -- lies outside the geometry is scaled
+ * by DampForBox / DampForCylinder (:71-111) as written; *energy = sum of 0.5 |f|^2 (1 - damping^2) over both fields (no
+ * cell volume, as Energy::get_field).  As written, the box's factor on the lower side is 1 - c at the wall and 1 at the
+ * interface, on the upper side 1 - c at the interface and 1 at the wall; the cylinder's width is center x - radius and
+ * its factor is 0 from delta0 = width (1 + 1/sqrt(c)) outwards. */
+int xpic_fields_damping(xpic_ctx* ctx, int E, int B, int B0, int geometry, const double geom[7], double coefficient,
+  double* energy);
+/* InjectParticles::execute (src/commands/inject_particles.cpp:26-63) for `pairs` pairs: each draws one coordinate
+ * (PreciseCoordinate / CoordinateInBox / CoordinateInCylinder, src/utils/particles_load.cpp:6-30), then the momentum of
+ * the ionized and then of the ejected sort (PreciseMomentum / MaxwellianMomentum with `tov`, :46-76; T in the reference's
+ * keV, mec2 = 511).  The draws come from a counter-based stream keyed by (seed, step, pair): this build's own RNG, not the
+ * reference's mt19937, and every z-slab draws the same pairs and keeps those in its planes.  A pair is added to both sorts
+ * iff its coordinate lies in the local box (Particles::add_particle, src/interfaces/particles.cpp:47-67); new records
+ * follow the old ones of their cell.  *added = pairs added, energy2 = kinetic energy added to the ionized, the ejected
+ * sort.  The two sorts must differ.  More records than a sort's capacity fail with an error on every slab, before any
+ * sort is changed. */
+enum xpic_coordinate_kind { XPIC_COORD_PRECISE = 0, XPIC_COORD_IN_BOX = 1, XPIC_COORD_IN_CYLINDER = 2 };
+enum xpic_momentum_kind { XPIC_MOMENTUM_PRECISE = 0, XPIC_MOMENTUM_MAXWELLIAN = 1 };
+typedef struct xpic_momentum_params {
+  int32_t kind;     /* enum xpic_momentum_kind */
+  int32_t tov;      /* MaxwellianMomentum: p /= sqrt(m^2 + p^2) */
+  double value[3];  /* PreciseMomentum: the value; MaxwellianMomentum: the drift px, py, pz (SortParameters) */
+  double T[3];      /* MaxwellianMomentum: Tx, Ty, Tz (SortParameters) */
+} xpic_momentum_params;
+typedef struct xpic_inject_params {
+  int32_t coordinate; /* enum xpic_coordinate_kind */
+  int32_t reserved;
+  double geom[7];     /* the point (precise), {min xyz, max xyz} (box), {center xyz, radius, height} (cylinder) */
+  xpic_momentum_params momentum[2]; /* ionized, ejected */
+  uint64_t seed;
+} xpic_inject_params;
+int xpic_inject_particles(xpic_ctx* ctx, int ionized, int ejected, const xpic_inject_params* params, int64_t pairs,
+  int64_t step, int64_t* added, double energy2[2]);
+/* SetCoilsField::operator() (src/commands/set_magnetic_field.cpp:38-150): field += the field of the coils {z0, R, I}
+ * (coils3[3 i ..]) about the axis (geom_x / 2, geom_y / 2), by the reference's 2000-point quadrature with its
+ * denominator_tolerance, at the positions it writes: Bx at (x, y + 1/2, z + 1/2) d, By at (x + 1/2, y, z + 1/2) d,
+ * Bz at (x + 1/2, y + 1/2, z) d.  A Bx or By node on the axis (r = 0) is 0 / 0 there as in the reference: NaN. */
+int xpic_set_coils_field(xpic_ctx* ctx, int field, int ncoils, const double* coils3);
 /* ChargeConservation (charge_conservation.cpp:117-171): xpic_charge_collect() = initialize(); then once per step
  * xpic_charge_columns(): out = {N1dQ_0, N2dQ_0, ..., N1dQ_tot, N2dQ_tot} of (rho_new - rho_old)/dt + div(-) J.
  * Uses the scratch vectors XPIC_W0..W2. */

@@ -28,7 +28,8 @@ SYMBOLS = [
     "xpic_update_cells", "xpic_ecsim_fill_current", "xpic_ecsim_second_push", "xpic_basic_push",
     "xpic_ecsimcorr_first_push", "xpic_ecsimcorr_second_push", "xpic_ecsimcorr_final_update",
     "xpic_calculate_energy", "xpic_ecsimcorr_scalars", "xpic_solve", "xpic_set_tolerances", "xpic_set_preconditioner", "xpic_set_overlap", "xpic_comm_stats", "xpic_set_fill_kernel", "xpic_set_fused_rebin", "xpic_get_fill_variant", "xpic_debug_set", "xpic_step",
-    "xpic_energy", "xpic_momentum", "xpic_charge_density", "xpic_moment_density", "xpic_moment", "xpic_velocity_distribution", "xpic_cell_traversal", "xpic_implicit_esirkepov_interpolate",
+    "xpic_energy", "xpic_momentum", "xpic_charge_density", "xpic_moment_density", "xpic_moment", "xpic_velocity_distribution", "xpic_remove_particles", "xpic_fields_damping",
+    "xpic_inject_particles", "xpic_set_coils_field", "xpic_cell_traversal", "xpic_implicit_esirkepov_interpolate",
     "xpic_implicit_esirkepov_decompose", "xpic_charge_collect", "xpic_charge_columns", "xpic_comm_rccl_unique_id", "xpic_comm_init_rccl", "xpic_comm_init_callbacks", "xpic_comm_size", "xpic_comm_peer_export", "xpic_comm_peer_import",
     "xpic_profile_enable", "xpic_profile_reset", "xpic_profile_get", "xpic_probe_copy_bandwidth",
 ]
@@ -64,6 +65,30 @@ MOMENT_DOF = {"density": 1, "current": 3, "momentum_flux": 6, "momentum_flux_dia
               "momentum_flux_diag_cyl": 3}
 PROJECTORS = {"vx_vy": 0, "vz_vxy": 1, "vr_vphi": 2}  # enum xpic_projector
 GEOMETRIES = {"box": 0, "BoxGeometry": 0, "cylinder": 1, "CylinderGeometry": 1}  # enum xpic_vgeometry
+
+COORDINATES = {"PreciseCoordinate": 0, "CoordinateInBox": 1, "CoordinateInCylinder": 2}  # enum xpic_coordinate_kind
+MOMENTA = {"PreciseMomentum": 0, "MaxwellianMomentum": 1}  # enum xpic_momentum_kind
+
+
+class MomentumParams(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("tov", C.c_int32), ("value", C.c_double * 3), ("T", C.c_double * 3)]
+
+
+class InjectParams(C.Structure):
+    _fields_ = [("coordinate", C.c_int32), ("reserved", C.c_int32), ("geom", C.c_double * 7),
+                ("momentum", MomentumParams * 2), ("seed", C.c_uint64)]
+
+
+def _geom7(geometry):
+    """(kind, double[7]) of a geometry dict: {"name": "box", "min": xyz, "max": xyz} or {"name": "cylinder", "center": xyz,
+    "radius": r, "height": h} ("BoxGeometry" / "CylinderGeometry" as well)"""
+    kind = GEOMETRIES[geometry["name"]]
+    if kind == 0:
+        gp = list(geometry["min"]) + list(geometry["max"]) + [0.0]
+    else:
+        gp = list(geometry["center"]) + [geometry["radius"], geometry["height"], 0.0, 0.0]
+    return kind, np.array(gp, dtype=np.float64)
+
 
 DEBUG_GATHER_WINDOW, DEBUG_PENCIL_LIMIT, DEBUG_SURROGATE_SCALE = 0, 1, 2  # include/xpic_hip.h: xpic_debug_set
 PEER_BLOB_BYTES = 256  # include/xpic_hip.h: XPIC_PEER_BLOB_BYTES
@@ -435,6 +460,50 @@ class Context:
         out = np.zeros((vg[1], vg[0]))
         self._ck(self.L.xpic_velocity_distribution(self.h, sort, PROJECTORS[projector], kind, _dp(gp), _dp(vreg), vg, _dp(out)))
         return out, (int(vg[2]), int(vg[3]))
+
+    # ---- the per-step commands (include/xpic_hip.h: xpic_remove_particles ... xpic_set_coils_field)
+    def remove_particles(self, sort, geometry):
+        """RemoveParticles: empties every cell whose corner lies outside `geometry` -> (records removed, their energy),
+        summed over the slabs"""
+        kind, gp = _geom7(geometry)
+        n, e = C.c_int64(), C.c_double()
+        self._ck(self.L.xpic_remove_particles(self.h, sort, kind, _dp(gp), C.byref(n), C.byref(e)))
+        return n.value, e.value
+
+    def fields_damping(self, geometry, coefficient, E=E, B=B, B0=B0):
+        """FieldsDamping of E and B - B0 outside `geometry` -> the damped energy, summed over the slabs"""
+        kind, gp = _geom7(geometry)
+        e = C.c_double()
+        self._ck(self.L.xpic_fields_damping(self.h, E, B, B0, kind, _dp(gp), C.c_double(coefficient), C.byref(e)))
+        return e.value
+
+    def inject_particles(self, ionized, ejected, pairs, step, coordinate, momentum_i, momentum_e, seed=1):
+        """InjectParticles of `pairs` pairs at step `step` -> (pairs added, (energy ionized, energy ejected)), summed over
+        the slabs.  coordinate: {"name": "PreciseCoordinate", "value": xyz} or a CoordinateInBox / CoordinateInCylinder
+        geometry dict (keys as remove_particles'); momentum_*: {"name": "PreciseMomentum", "value": xyz} or
+        {"name": "MaxwellianMomentum", "T": (Tx, Ty, Tz), "drift": (px, py, pz), "tov": bool}."""
+        p = InjectParams()
+        p.coordinate = COORDINATES[coordinate["name"]]
+        if p.coordinate == 0:
+            p.geom[:] = [float(v) for v in coordinate["value"]] + [0.0] * 4
+        else:
+            p.geom[:] = [float(v) for v in _geom7(dict(coordinate, name="box" if p.coordinate == 1 else "cylinder"))[1]]
+        for k, m in enumerate((momentum_i, momentum_e)):
+            mp = p.momentum[k]
+            mp.kind = MOMENTA[m["name"]]
+            mp.tov = int(bool(m.get("tov", False)))
+            mp.value[:] = [float(v) for v in (m["value"] if mp.kind == 0 else m.get("drift", (0.0, 0.0, 0.0)))]
+            mp.T[:] = [float(v) for v in m.get("T", (0.0, 0.0, 0.0))]
+        p.seed = int(seed)
+        added, e2 = C.c_int64(), np.zeros(2)
+        self._ck(self.L.xpic_inject_particles(self.h, ionized, ejected, C.byref(p), C.c_int64(int(pairs)),
+                                              C.c_int64(int(step)), C.byref(added), _dp(e2)))
+        return added.value, (float(e2[0]), float(e2[1]))
+
+    def set_coils_field(self, coils, field=B0):
+        """SetCoilsField: field += the field of the coils [(z0, R, I), ...]"""
+        c3 = np.ascontiguousarray(np.asarray(coils, dtype=np.float64).reshape(-1, 3))
+        self._ck(self.L.xpic_set_coils_field(self.h, field, int(c3.shape[0]), _dp(c3)))
 
     def cell_traversal(self, end, start, max_pts=8):
         end, start = np.ascontiguousarray(end, dtype=np.float64), np.ascontiguousarray(start, dtype=np.float64)

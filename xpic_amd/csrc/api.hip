@@ -406,6 +406,7 @@ int xpic_destroy(xpic_ctx* ctx)
   (void)hipFree(ctx->kry_t); (void)hipFree(ctx->kry_Z); (void)hipFree(ctx->kry_p[0]); (void)hipFree(ctx->kry_p[1]); (void)hipFree(ctx->kry_p[2]);
   (void)hipFree(ctx->red_partial); (void)hipFree(ctx->red_out); (void)hipHostFree(ctx->red_host);
   (void)hipFree(ctx->scan_tmp);
+  (void)hipFree(ctx->cmd_start); (void)hipFree(ctx->cmd_add); (void)hipFree(ctx->cmd_rank);
   (void)hipFree(ctx->abar32); (void)hipFree(ctx->abar_work); (void)hipFree(ctx->abar_r);
   (void)hipFree(ctx->lrow_buf[0]); (void)hipFree(ctx->lrow_buf[1]);
   for (int i = 0; i < 4; ++i) (void)hipFree(ctx->halo_buf[i]);
@@ -916,6 +917,35 @@ int xpic_velocity_distribution(xpic_ctx* ctx, int sort, int projector, int geome
   }
   if (own) (void)hipFree(hist);
   return rc;
+}
+
+// ---- the per-step commands (commands.hip)
+int xpic_remove_particles(xpic_ctx* ctx, int sort, int geometry, const double geom[7], int64_t* removed, double* energy)
+{ // RemoveParticles::execute, remove_particles.cpp:11-40
+  CTX_CHECK(ctx); SORT_CHECK(sort);
+  return remove_particles(ctx, ctx->sorts[sort], geometry, geom, removed, energy);
+}
+
+int xpic_fields_damping(xpic_ctx* ctx, int E, int B, int B0, int geometry, const double geom[7], double coefficient,
+  double* energy)
+{ // FieldsDamping::execute, fields_damping.cpp:15-111
+  CTX_CHECK(ctx); FIELD_CHECK(E); FIELD_CHECK(B); FIELD_CHECK(B0);
+  XPIC_CHECK(E != B && E != B0 && B != B0, "fields_damping: E, B and B0 must be three different vectors");
+  return fields_damping(ctx, ctx->field[E], ctx->field[B], ctx->field[B0], geometry, geom, coefficient, energy);
+}
+
+int xpic_inject_particles(xpic_ctx* ctx, int ionized, int ejected, const xpic_inject_params* params, int64_t pairs,
+  int64_t step, int64_t* added, double energy2[2])
+{ // InjectParticles::execute, inject_particles.cpp:26-63
+  CTX_CHECK(ctx); SORT_CHECK(ionized); SORT_CHECK(ejected);
+  XPIC_CHECK(params, "null argument");
+  return inject_particles(ctx, ctx->sorts[ionized], ctx->sorts[ejected], *params, pairs, step, added, energy2);
+}
+
+int xpic_set_coils_field(xpic_ctx* ctx, int field, int ncoils, const double* coils3)
+{ // SetCoilsField::operator(), set_magnetic_field.cpp:38-150
+  CTX_CHECK(ctx); FIELD_CHECK(field);
+  return set_coils_field(ctx, ctx->field[field], ncoils, coils3);
 }
 
 int xpic_charge_collect(xpic_ctx* ctx) // ChargeConservation::initialize, charge_conservation.cpp:117-123

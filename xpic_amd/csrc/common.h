@@ -243,6 +243,12 @@ struct xpic_ctx {
   double* red_host = nullptr;
   int* scan_tmp = nullptr;
   long scan_tmp_n = 0;
+  // commands.hip: the new cell_start of a rebuilt sort (swapped with the sort's own, same size), the injected records per
+  // cell, and the arrival rank of every injected pair in its cell
+  int* cmd_start = nullptr;
+  int* cmd_add = nullptr;
+  int* cmd_rank = nullptr;
+  int64_t cmd_rank_n = 0;
   double rtol = 1e-7, atol = 1e-7;
   int maxit = 100;
   xpic::Comm comm;
@@ -343,6 +349,7 @@ int sort_append_host(xpic_ctx* c, Sort& s, int64_t n, const double* pts6, int64_
 int sort_download(xpic_ctx* c, Sort& s, double* pts6, int32_t* cell_of);
 int sort_fill_synthetic(xpic_ctx* c, Sort& s, const xpic_load_params& lp);
 int sort_occupancy(xpic_ctx* c, Sort& s, int64_t* out8);
+int exclusive_scan(xpic_ctx* c, const int* in, long n, int* out, int* total_host); // out[n] = total
 int ecsim_second_push(xpic_ctx* c, Sort& s, const double* E, const double* B, bool prebin = false);
 int charge_density(xpic_ctx* c, Sort& s, double* rho_vec);
 int moment_density(xpic_ctx* c, Sort& s, double* vec);
@@ -357,6 +364,14 @@ int moment_dof(int kind); // 0: unknown kind
 int moment_region(xpic_ctx* c, Sort& s, int kind, const int* region6, double* const* comp);
 int vdist_sizes(const GridDev& g, int geometry, const double* geom, const double* vreg, int* aabb6, int* vs, int* vn);
 int velocity_distribution(xpic_ctx* c, Sort& s, int projector, int geometry, const double* geom, const double* vreg, double* hist);
+
+// commands.hip (the reference's src/commands/); geom as xpic_velocity_distribution's
+int remove_particles(xpic_ctx* c, Sort& s, int geometry, const double* geom, int64_t* removed, double* energy);
+int fields_damping(xpic_ctx* c, double* E, double* B, const double* B0, int geometry, const double* geom, double coefficient,
+  double* energy);
+int inject_particles(xpic_ctx* c, Sort& si, Sort& se, const xpic_inject_params& p, int64_t pairs, int64_t step,
+  int64_t* added, double* energy2);
+int set_coils_field(xpic_ctx* c, double* F, int ncoils, const double* coils3);
 
 // ecsim.hip
 int ecsim_fill_sort(xpic_ctx* c, Sort& s, const double* B, double* currI_sort, double* matL, bool first_sort, bool post_ghost_rows);

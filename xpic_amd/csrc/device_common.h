@@ -5,6 +5,17 @@
 
 namespace xpic {
 
+// Counter-based splitmix64 stream: u01 draws from (0, 1), never 0 or 1 (a log of it is finite).  The synthetic loader keys one
+// stream per particle, InjectParticles one per (seed, step, pair).  This build's own RNG, not the reference's mt19937.
+__host__ __device__ inline uint64_t splitmix(uint64_t& x)
+{
+  uint64_t z = (x += 0x9E3779B97F4A7C15ull);
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  return z ^ (z >> 31);
+}
+__host__ __device__ inline double u01(uint64_t& st) { return ((splitmix(st) >> 11) + 0.5) * (1.0 / 9007199254740992.0); }
+
 // g_bound_periodic (src/interfaces/point.cpp:18-26): ONE wrap, s == L is left as is.
 __device__ inline double bound_periodic(double s, double L)
 {

@@ -691,15 +691,7 @@ __global__ void __launch_bounds__(kBlock) k_pack(GridDev g, SortDev s, int64_t n
   cell[i] = cell_of(g, s.r[0][i], s.r[1][i], s.r[2][i]);
 }
 
-// ---- synthetic loader (bench / smoke only): counter-based splitmix64 stream per particle -----------
-__device__ inline uint64_t splitmix(uint64_t& x)
-{
-  uint64_t z = (x += 0x9E3779B97F4A7C15ull);
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-__device__ inline double u01(uint64_t& st) { return ((splitmix(st) >> 11) + 0.5) * (1.0 / 9007199254740992.0); }
+// ---- synthetic loader (bench / smoke only): counter-based splitmix64 stream per particle (device_common.h: u01) -----------
 
 // REGULAR: particle p sits in cell p / ppc (exactly ppc per cell, the generated order IS the sorted order);
 // otherwise the position is uniform over the whole slab like CoordinateInBox + SetParticles
@@ -769,6 +761,8 @@ __global__ void __launch_bounds__(kBlock) k_fill_counts(int* count, int* start, 
   if (i <= ncell) start[i] = (int)(i * ppc);
 }
 
+}  // namespace
+
 int exclusive_scan(xpic_ctx* c, const int* in, long n, int* out, int* total_host)
 {
   const int ntiles = (int)((n + kScanTile - 1) / kScanTile);
@@ -789,8 +783,6 @@ int exclusive_scan(xpic_ctx* c, const int* in, long n, int* out, int* total_host
   }
   return 0;
 }
-
-}  // namespace
 
 int sort_alloc(xpic_ctx* c, Sort& s, int64_t cap)
 {

@@ -11,6 +11,7 @@
 #include <cmath>
 #include <cstdio>
 #include <iostream>
+#include <map>
 #include <random>
 #include <sstream>
 #include <stdexcept>
@@ -280,7 +281,22 @@ PetscErrorCode Simulation::init_particles()
   const Configuration::json_t& json = CONFIG().json;
   const Configuration::json_t* it = json.find("Particles");
   if (!it || it->arr.empty()) return 0;
-  // capacity: the SetParticles presets tell how many points each sort will get; leave head-room for migration
+  // capacity: the SetParticles presets tell how many points each sort will get; leave head-room for migration.  The
+  // InjectParticles step presets add their pairs of the run to both of their sorts.
+  std::map<std::string, int64_t> injected;
+  if (const Configuration::json_t* sp = json.find("StepPresets")) {
+    for (auto&& info : sp->arr) {
+      if (!info.contains("command") || info.at("command").as_string() != "InjectParticles") continue;
+      const std::string ionized = info.at("ionized").as_string(), ejected = info.at("ejected").as_string();
+      PetscInt Np = 0;
+      for (auto&& pinfo : it->arr)
+        if (pinfo.contains("sort_name") && pinfo.at("sort_name").as_string() == ionized) Np = pinfo.at("Np").as_int();
+      const InjectionSchedule s = injection_schedule(info, Np);
+      const int64_t steps = std::max<int64_t>(0, (int64_t)std::min(s.end, geom_nt) - std::max<PetscInt>(s.start, 1) + 1);
+      injected[ionized] += steps * std::max<PetscInt>(s.per_step, 0);
+      injected[ejected] += steps * std::max<PetscInt>(s.per_step, 0);
+    }
+  }
   for (auto&& info : it->arr) {
     if (!info.contains("sort_name")) continue;
     SortParameters p;
@@ -305,7 +321,7 @@ PetscErrorCode Simulation::init_particles()
     auto sort = std::make_shared<Particles>(*this, p);
     xpic_sort_params sp{p.Np, p.n, p.q, p.m};
     const int64_t cells = (int64_t)geom_nx * geom_ny * geom_nz;
-    const int64_t capacity = std::max<int64_t>(cells * p.Np * 5 / 4 + 4096, 1 << 16);
+    const int64_t capacity = std::max<int64_t>(cells * p.Np * 5 / 4 + 4096, 1 << 16) + injected[p.sort_name];
     HIPCALL(xpic_add_sort(ctx, &sp, capacity, &sort->sort_id));
     particles_.emplace_back(sort);
     LOG("  " << p.sort_name << " are added");
@@ -397,12 +413,129 @@ SetMagneticField::SetMagneticField(interfaces::Simulation& sim, int field, int f
 
 PetscErrorCode SetMagneticField::execute(PetscInt /* t */) // src/commands/set_magnetic_field.cpp:12-19, 27-35
 {
+  if (!coils_.empty()) { // SetCoilsField: += into the field (:38-102)
+    HIPCALL(xpic_set_coils_field(sim_.ctx, field_, (int)(coils_.size() / 3), coils_.data()));
+    if (field_axpy_ >= 0) HIPCALL(xpic_vec_axpy(sim_.ctx, field_axpy_, 1.0, field_));
+    return 0;
+  }
   const size_t n = (size_t)geom_nx * geom_ny * geom_nz;
   std::vector<double> v(3 * n);
   for (size_t i = 0; i < n; ++i)
     for (int c = 0; c < 3; ++c) v[3 * i + c] = value_[c]; // VecStrideSet
   HIPCALL(xpic_field_set(sim_.ctx, field_, v.data()));
   if (field_axpy_ >= 0) HIPCALL(xpic_vec_axpy(sim_.ctx, field_axpy_, 1.0, field_));
+  return 0;
+}
+
+int geometry_kind(const std::string& name)
+{
+  if (name == "BoxGeometry") return XPIC_GEOM_BOX;
+  if (name == "CylinderGeometry") return XPIC_GEOM_CYLINDER;
+  throw std::runtime_error("Unknown geometry name " + name);
+}
+
+void load_geometry(const Configuration::json_t& info, int kind, double geom[7])
+{
+  using interfaces::Builder;
+  for (int i = 0; i < 7; ++i) geom[i] = 0.0;
+  if (kind == XPIC_GEOM_BOX) { // builder.cpp:83-94: the whole box by default
+    Vector3R mn, mx;
+    mx[0] = geom_x; mx[1] = geom_y; mx[2] = geom_z;
+    if (info.contains("min")) mn = Builder::parse_vector(info, "min");
+    if (info.contains("max")) mx = Builder::parse_vector(info, "max");
+    for (int i = 0; i < 3; ++i) { geom[i] = mn[i]; geom[3 + i] = mx[i]; }
+    return;
+  }
+  Vector3R c; // (:96-113): centred, radius min(geom_x, geom_y) / 2, height geom_z
+  c[0] = 0.5 * geom_x; c[1] = 0.5 * geom_y; c[2] = 0.5 * geom_z;
+  if (info.contains("center")) c = Builder::parse_vector(info, "center");
+  for (int i = 0; i < 3; ++i) geom[i] = c[i];
+  geom[3] = info.contains("radius") ? info.at("radius").as_double() : 0.5 * std::min(geom_x, geom_y);
+  geom[4] = info.contains("height") ? info.at("height").as_double() : geom_z;
+}
+
+SetMagneticField::SetMagneticField(interfaces::Simulation& sim, int field, int field_axpy, std::vector<double> coils3)
+  : sim_(sim), field_(field), field_axpy_(field_axpy), coils_(std::move(coils3))
+{
+}
+
+RemoveParticles::RemoveParticles(interfaces::Simulation& sim, interfaces::Particles& particles, int kind, const double geom[7])
+  : sim_(sim), particles_(particles), kind_(kind)
+{
+  std::copy(geom, geom + 7, geom_);
+}
+
+PetscErrorCode RemoveParticles::execute(PetscInt /* t */)
+{
+  int64_t removed = 0;
+  HIPCALL(xpic_remove_particles(sim_.ctx, particles_.sort_id, kind_, geom_, &removed, &removed_energy_));
+  LOG("  Particles have been removed from \"" << particles_.parameters.sort_name << "\": " << removed);
+  return 0;
+}
+
+FieldsDamping::FieldsDamping(interfaces::Simulation& sim, int E, int B, int B0, int kind, const double geom[7],
+  PetscReal coefficient)
+  : sim_(sim), E_(E), B_(B), B0_(B0), kind_(kind), coefficient_(coefficient)
+{
+  std::copy(geom, geom + 7, geom_);
+}
+
+PetscErrorCode FieldsDamping::execute(PetscInt /* t */)
+{
+  HIPCALL(xpic_fields_damping(sim_.ctx, E_, B_, B0_, kind_, geom_, coefficient_, &damped_energy_));
+  LOG("  Fields are damped, additional energy runoff: " << damped_energy_);
+  return 0;
+}
+
+// InjectParticlesBuilder::build (inject_particles_builder.cpp:11-71) with load_coordinate's count (particles_builder.cpp:10-38)
+InjectionSchedule injection_schedule(const Configuration::json_t& info, PetscInt ionized_Np)
+{
+  InjectionSchedule s; // t in [0, 1] by default (:21-24)
+  if (info.contains("injection_start")) s.start = ROUND_STEP(info.at("injection_start").as_double(), dt);
+  if (info.contains("injection_end")) {
+    const auto& v = info.at("injection_end");
+    if (v.is_string()) { if (v.as_string() == "geom_t") s.end = geom_nt; }
+    else s.end = ROUND_STEP(v.as_double(), dt);
+  }
+  const auto& ci = info.at("coordinate");
+  const std::string cname = ci.at("name").as_string();
+  const PetscReal frac = ionized_Np / (dx * dy * dz);
+  PetscInt number = 0;
+  double g[7];
+  if (cname == "PreciseCoordinate") number = ionized_Np;
+  else if (cname == "CoordinateInBox") {
+    load_geometry(ci, XPIC_GEOM_BOX, g);
+    number = (PetscInt)(((g[3] - g[0]) * (g[4] - g[1]) * (g[5] - g[2])) * frac);
+  }
+  else if (cname == "CoordinateInCylinder") {
+    load_geometry(ci, XPIC_GEOM_CYLINDER, g);
+    number = (PetscInt)(M_PI * (g[3] * g[3]) * g[4] * frac);
+  }
+  else throw std::runtime_error("Unknown coordinate generator name " + cname);
+  PetscInt tau = s.end - s.start;
+  if (info.contains("tau")) tau = ROUND_STEP(info.at("tau").as_double(), dt);
+  if (tau == 0) throw std::runtime_error("InjectParticles: tau is zero steps (a division by zero in the reference)");
+  s.per_step = number / tau;
+  if (info.contains("per_step_particles_num")) s.per_step = info.at("per_step_particles_num").as_int();
+  return s;
+}
+
+InjectParticles::InjectParticles(interfaces::Simulation& sim, interfaces::Particles& ionized, interfaces::Particles& ejected,
+  const InjectionSchedule& schedule, const xpic_inject_params& params)
+  : sim_(sim), ionized_(ionized), ejected_(ejected), schedule_(schedule), params_(params)
+{
+}
+
+PetscErrorCode InjectParticles::execute(PetscInt t) // inject_particles.cpp:26-63
+{
+  energy_i_ = energy_e_ = 0.0;
+  if (t < schedule_.start || t > schedule_.end) return 0;
+  int64_t added = 0;
+  double e2[2] = {0, 0};
+  HIPCALL(xpic_inject_particles(sim_.ctx, ionized_.sort_id, ejected_.sort_id, &params_, schedule_.per_step, t, &added, e2));
+  energy_i_ = e2[0];
+  energy_e_ = e2[1];
+  LOG("  Particles have been injected: " << added);
   return 0;
 }
 
@@ -452,6 +585,22 @@ PetscErrorCode build_commands(interfaces::Simulation& simulation, const std::str
           return r;
         };
       }
+      else if (cname == "CoordinateInCylinder") { // particles_load.cpp:20-30, particles_builder.cpp:31-35
+        double g[7];
+        load_geometry(ci, XPIC_GEOM_CYLINDER, g);
+        number_of_particles = M_PI * (g[3] * g[3]) * g[4] * frac; // truncation
+        const Vector3R c{{g[0], g[1], g[2]}};
+        const PetscReal R = g[3], h = g[4];
+        gc = [c, R, h]() {
+          const PetscReal r = R * std::sqrt(random_01());
+          const PetscReal phi = 2.0 * M_PI * random_01();
+          Vector3R p;
+          p[0] = c[0] + r * std::cos(phi);
+          p[1] = c[1] + r * std::sin(phi);
+          p[2] = c[2] + h * (random_01() - 0.5);
+          return p;
+        };
+      }
       else throw std::runtime_error("Unknown coordinate generator name " + cname);
       MomentumGenerator gm;
       const auto& mi = info.at("momentum");
@@ -488,8 +637,82 @@ PetscErrorCode build_commands(interfaces::Simulation& simulation, const std::str
       if (info.contains("field_axpy")) axpy = simulation.get_named_vector(info.at("field_axpy").as_string());
       const auto& setter = info.at("setter");
       const std::string sname = setter.at("name").as_string();
-      if (sname != "SetUniformField") throw std::runtime_error("Unknown setter name " + sname);
-      result.emplace_back(std::make_unique<SetMagneticField>(simulation, field, axpy, Builder::parse_vector(setter, "value")));
+      if (sname == "SetUniformField")
+        result.emplace_back(std::make_unique<SetMagneticField>(simulation, field, axpy, Builder::parse_vector(setter, "value")));
+      else if (sname == "SetCoilsField") { // set_magnetic_field_builder.cpp:45-57
+        std::vector<double> coils;
+        for (auto&& coil : setter.at("coils").arr) {
+          coils.push_back(coil.at("z0").as_double());
+          coils.push_back(coil.at("R").as_double());
+          coils.push_back(coil.at("I").as_double());
+          LOG("    Adding magnetic coil, z0: " << coils[coils.size() - 3] << ", R: " << coils[coils.size() - 2] << ", I: " << coils.back());
+        }
+        result.emplace_back(std::make_unique<SetMagneticField>(simulation, field, axpy, std::move(coils)));
+      }
+      else throw std::runtime_error("Unknown setter name " + sname);
+    }
+    else if (command == "RemoveParticles") { // remove_particles_builder.cpp:11-44
+      auto& particles = simulation.get_named_particles(info.at("particles").as_string());
+      const auto& geometry = info.at("geometry");
+      const int kind = geometry_kind(geometry.at("name").as_string());
+      double g[7];
+      load_geometry(geometry, kind, g);
+      result.emplace_back(std::make_unique<RemoveParticles>(simulation, particles, kind, g));
+      LOG("  RemoveParticles command is added for \"" << particles.parameters.sort_name << "\"");
+    }
+    else if (command == "FieldsDamping") { // fields_damping_builder.cpp:11-51
+      const int E = simulation.get_named_vector(info.at("E").as_string());
+      const int B = simulation.get_named_vector(info.at("B").as_string());
+      const int B0 = simulation.get_named_vector(info.at("B0").as_string());
+      const PetscReal coefficient = info.at("damping_coefficient").as_double();
+      const auto& geometry = info.at("geometry");
+      const int kind = geometry_kind(geometry.at("name").as_string());
+      double g[7];
+      load_geometry(geometry, kind, g);
+      result.emplace_back(std::make_unique<FieldsDamping>(simulation, E, B, B0, kind, g, coefficient));
+      LOG("  FieldsDamping command is added");
+    }
+    else if (command == "InjectParticles") { // inject_particles_builder.cpp:11-71
+      auto& ionized = simulation.get_named_particles(info.at("ionized").as_string());
+      auto& ejected = simulation.get_named_particles(info.at("ejected").as_string());
+      const InjectionSchedule schedule = injection_schedule(info, ionized.parameters.Np);
+      xpic_inject_params p{};
+      const auto& ci = info.at("coordinate");
+      const std::string cname = ci.at("name").as_string();
+      if (cname == "PreciseCoordinate") {
+        p.coordinate = XPIC_COORD_PRECISE;
+        const Vector3R v = Builder::parse_vector(ci, "value");
+        for (int i = 0; i < 3; ++i) p.geom[i] = v[i];
+      }
+      else {
+        p.coordinate = cname == "CoordinateInBox" ? XPIC_COORD_IN_BOX : XPIC_COORD_IN_CYLINDER;
+        load_geometry(ci, cname == "CoordinateInBox" ? XPIC_GEOM_BOX : XPIC_GEOM_CYLINDER, p.geom);
+      }
+      interfaces::Particles* sorts[2] = {&ionized, &ejected};
+      const char* keys[2] = {"momentum_i", "momentum_e"};
+      for (int k = 0; k < 2; ++k) { // ParticlesBuilder::load_momentum (particles_builder.cpp:40-68)
+        const auto& mi = info.at(keys[k]);
+        const std::string mname = mi.at("name").as_string();
+        xpic_momentum_params& m = p.momentum[k];
+        if (mname == "PreciseMomentum") {
+          m.kind = XPIC_MOMENTUM_PRECISE;
+          const Vector3R v = Builder::parse_vector(mi, "value");
+          for (int i = 0; i < 3; ++i) m.value[i] = v[i];
+        }
+        else if (mname == "MaxwellianMomentum") {
+          const SortParameters& sp = sorts[k]->parameters;
+          m.kind = XPIC_MOMENTUM_MAXWELLIAN;
+          m.tov = mi.contains("tov") && mi.at("tov").as_bool() ? 1 : 0;
+          m.value[0] = sp.px; m.value[1] = sp.py; m.value[2] = sp.pz;
+          m.T[0] = sp.Tx; m.T[1] = sp.Ty; m.T[2] = sp.Tz;
+        }
+        else throw std::runtime_error("Unknown momentum generator name " + mname);
+      }
+      p.seed = (uint64_t)result.size(); // the command's place in its list: two injections draw different pairs
+      result.emplace_back(std::make_unique<InjectParticles>(simulation, ionized, ejected, schedule, p));
+      LOG("  InjectParticles command is added with ionized: \"" << ionized.parameters.sort_name << "\", ejected: \""
+        << ejected.parameters.sort_name << "\", " << schedule.per_step << " pairs per step in [" << schedule.start << ", "
+        << schedule.end << "]");
     }
     else throw std::runtime_error("Unknown command name " + command);
   }
@@ -690,27 +913,9 @@ PetscErrorCode build_diagnostics(interfaces::Simulation& simulation,
       else if (projector == "vr_vphi") proj = XPIC_PROJ_VR_VPHI;
       else throw std::runtime_error("Unkown projector name " + projector);
       const auto& geometry = info.at("geometry");
-      const std::string gname = geometry.at("name").as_string();
-      int gkind;
-      double geom[7] = {0, 0, 0, 0, 0, 0, 0};
-      if (gname == "BoxGeometry") { // Builder::load_geometry (src/interfaces/builder.cpp:83-94): the whole box by default
-        gkind = XPIC_GEOM_BOX;
-        Vector3R mn, mx;
-        mx[0] = geom_x; mx[1] = geom_y; mx[2] = geom_z;
-        if (geometry.contains("min")) mn = Builder::parse_vector(geometry, "min");
-        if (geometry.contains("max")) mx = Builder::parse_vector(geometry, "max");
-        for (int i = 0; i < 3; ++i) { geom[i] = mn[i]; geom[3 + i] = mx[i]; }
-      }
-      else if (gname == "CylinderGeometry") { // (:96-113): centred, radius min(geom_x, geom_y) / 2, height geom_z
-        gkind = XPIC_GEOM_CYLINDER;
-        Vector3R c;
-        c[0] = 0.5 * geom_x; c[1] = 0.5 * geom_y; c[2] = 0.5 * geom_z;
-        if (geometry.contains("center")) c = Builder::parse_vector(geometry, "center");
-        for (int i = 0; i < 3; ++i) geom[i] = c[i];
-        geom[3] = geometry.contains("radius") ? geometry.at("radius").as_double() : 0.5 * std::min(geom_x, geom_y);
-        geom[4] = geometry.contains("height") ? geometry.at("height").as_double() : geom_z;
-      }
-      else throw std::runtime_error("Unknown geometry name " + gname);
+      const int gkind = geometry_kind(geometry.at("name").as_string());
+      double geom[7];
+      load_geometry(geometry, gkind, geom);
       double vreg[6] = {-1, -1, +1, +1, 0, 0}; // vx_min, vy_min, vx_max, vy_max, dvx, dvy
       const auto& dv = info.at("dv");
       vreg[4] = dv.arr.at(0).as_double();
@@ -1032,6 +1237,22 @@ PetscErrorCode Energy::diagnose(PetscInt t)
   for (size_t i = 0; i < K.size(); ++i) {
     energy_cons.add(13, "dK_" + particles[i]->parameters.sort_name, "% .6e", K[i] - K0[i]);
     dK += K[i] - K0[i];
+  }
+  for (const auto& command : simulation.step_presets()) { // energy.cpp:156-178, in the step presets' order
+    if (auto* damp = dynamic_cast<FieldsDamping*>(command.get())) {
+      energy_cons.add(13, "Damped(E+B)", "% .6e", damp->get_damped_energy());
+      dF += damp->get_damped_energy();
+    }
+    if (auto* injection = dynamic_cast<InjectParticles*>(command.get())) {
+      const PetscReal wi = injection->get_ionized_energy(), we = injection->get_ejected_energy();
+      energy_cons.add(13, "Inj_" + injection->get_ionized_name(), "% .6e", wi);
+      energy_cons.add(13, "Inj_" + injection->get_ejected_name(), "% .6e", we);
+      dK -= wi + we;
+    }
+    if (auto* remove = dynamic_cast<RemoveParticles*>(command.get())) {
+      energy_cons.add(13, "Rm_" + remove->get_particles_name(), "% .6e", remove->get_removed_energy());
+      dK += remove->get_removed_energy();
+    }
   }
   energy_cons.add(13, "dE+dB+dK", "% .6e", dF + dK);
   if (simulation.scheme() == XPIC_ECSIMCORR) {

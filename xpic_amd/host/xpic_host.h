@@ -153,6 +153,11 @@ protected:
   virtual PetscErrorCode timestep_implementation(PetscInt timestep);
 
   std::vector<std::unique_ptr<Command>> step_presets_;
+
+public:
+  const std::vector<std::unique_ptr<Command>>& step_presets() const { return step_presets_; }
+
+protected:
   std::vector<std::unique_ptr<Diagnostic>> diagnostics_;
   friend class ::Configuration;
 };
@@ -209,12 +214,76 @@ private:
 class SetMagneticField : public interfaces::Command {
 public:
   SetMagneticField(interfaces::Simulation& sim, int field, int field_axpy, const Vector3R& uniform_value);
+  // SetCoilsField (set_magnetic_field.cpp:38-150): coils3 = {z0, R, I} per coil, added to the field
+  SetMagneticField(interfaces::Simulation& sim, int field, int field_axpy, std::vector<double> coils3);
   PetscErrorCode execute(PetscInt t) override;
 
 private:
   interfaces::Simulation& sim_;
   int field_, field_axpy_;
   Vector3R value_;
+  std::vector<double> coils_; // empty: SetUniformField
+};
+
+// Builder::load_geometry (src/interfaces/builder.cpp:83-113) of a "BoxGeometry" / "CylinderGeometry" entry ->
+// enum xpic_vgeometry and the geom[7] layout of the C ABI
+int geometry_kind(const std::string& name); // "BoxGeometry" / "CylinderGeometry"
+void load_geometry(const Configuration::json_t& info, int kind, double geom[7]);
+
+// src/commands/remove_particles.cpp:11-40 (xpic_remove_particles)
+class RemoveParticles : public interfaces::Command {
+public:
+  RemoveParticles(interfaces::Simulation& sim, interfaces::Particles& particles, int kind, const double geom[7]);
+  PetscErrorCode execute(PetscInt t) override;
+  const std::string& get_particles_name() const { return particles_.parameters.sort_name; }
+  PetscReal get_removed_energy() const { return removed_energy_; }
+
+private:
+  interfaces::Simulation& sim_;
+  interfaces::Particles& particles_;
+  int kind_;
+  double geom_[7];
+  PetscReal removed_energy_ = 0;
+};
+
+// src/commands/fields_damping.cpp:15-111 (xpic_fields_damping)
+class FieldsDamping : public interfaces::Command {
+public:
+  FieldsDamping(interfaces::Simulation& sim, int E, int B, int B0, int kind, const double geom[7], PetscReal coefficient);
+  PetscErrorCode execute(PetscInt t) override;
+  PetscReal get_damped_energy() const { return damped_energy_; }
+
+private:
+  interfaces::Simulation& sim_;
+  int E_, B_, B0_, kind_;
+  double geom_[7];
+  PetscReal coefficient_, damped_energy_ = 0;
+};
+
+// InjectParticlesBuilder::build (src/commands/builders/inject_particles_builder.cpp:11-71): the window and the pairs per step
+struct InjectionSchedule {
+  PetscInt start = 0, end = 1, per_step = 0;
+};
+InjectionSchedule injection_schedule(const Configuration::json_t& info, PetscInt ionized_Np);
+
+// src/commands/inject_particles.cpp:26-63 (xpic_inject_particles: the pairs are drawn on the device from a stream keyed by
+// (seed, step, pair), not from the host's mt19937)
+class InjectParticles : public interfaces::Command {
+public:
+  InjectParticles(interfaces::Simulation& sim, interfaces::Particles& ionized, interfaces::Particles& ejected,
+    const InjectionSchedule& schedule, const xpic_inject_params& params);
+  PetscErrorCode execute(PetscInt t) override;
+  const std::string& get_ionized_name() const { return ionized_.parameters.sort_name; }
+  const std::string& get_ejected_name() const { return ejected_.parameters.sort_name; }
+  PetscReal get_ionized_energy() const { return energy_i_; }
+  PetscReal get_ejected_energy() const { return energy_e_; }
+
+private:
+  interfaces::Simulation& sim_;
+  interfaces::Particles &ionized_, &ejected_;
+  InjectionSchedule schedule_;
+  xpic_inject_params params_;
+  PetscReal energy_i_ = 0, energy_e_ = 0;
 };
 
 PetscErrorCode build_commands(interfaces::Simulation& simulation, const std::string& name,
