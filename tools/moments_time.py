@@ -1,8 +1,7 @@
 #!/usr/bin/env python3
-"""Times the particle diagnostics (xpic_moment, xpic_velocity_distribution) against the existing xpic_moment_density on
-the headline state: ECSIM, 256^3 x 64 per cell from load_synthetic, after one step (the records in the step's own order).
+"""Times the particle diagnostics (xpic_moment, xpic_velocity_distribution) on the headline state: ECSIM, 256^3 x 64 per cell from load_synthetic, after one step (the records in the step's own order).
 
-Kernel time only, from the context's named profile sections ("moment", "velocity_distribution", "moment_density"); the
+Kernel time only, from the context's named profile sections ("moment", "velocity_distribution"); the
 copy-out to the host is not counted.  Each time is also given as a multiple of the floor = the bytes of one read of the
 records (24 B per particle for the density: r; 48 B for the other moments: r and v; 24 B for vx_vy: v) at the measured
 device copy rate.  Prints
@@ -71,7 +70,6 @@ def main():
     out = {}
     for name in MOMENTS:
         out[name] = timed("moment", lambda: ctx.moment(s, name), npart * (24 if name == "density" else 48))
-    out["moment_density (existing)"] = timed("moment_density", lambda: ctx.moment_density(s), npart * 24)
     box = {"name": "box", "min": (0.0, 0.0, 0.0), "max": (n * 0.5,) * 3}
     v = 4 * args.vth
     for label, dv in (("vx_vy, LDS path", v / 20), ("vx_vy, global path", v / 200)):

@@ -847,26 +847,22 @@ static double* sort_current(xpic_ctx* ctx, Sort& s)
   return ctx->scheme == XPIC_BASIC ? s.J : (ctx->scheme == XPIC_ECSIM ? s.currI : s.currJe);
 }
 
+// the first nc components of a stored vector, per owned node: out[i * stride + j]
+static int export_components(xpic_ctx* ctx, const double* vec, int nc, int stride, double* out)
+{
+  std::vector<double> v3((size_t)ctx->g.nown * 3);
+  XPIC_CALL(field_export(ctx, vec, v3.data()));
+  for (long i = 0; i < ctx->g.nown; ++i)
+    for (int j = 0; j < nc; ++j) out[i * stride + j] = v3[3 * i + j];
+  return 0;
+}
+
 int xpic_charge_density(xpic_ctx* ctx, int sort, double* rho_zyx)
 {
   CTX_CHECK(ctx); SORT_CHECK(sort);
   double* tmp = ctx->field[XPIC_W2];
   XPIC_CALL(charge_density(ctx, ctx->sorts[sort], tmp));
-  std::vector<double> v3((size_t)ctx->g.nown * 3);
-  XPIC_CALL(field_export(ctx, tmp, v3.data()));
-  for (long i = 0; i < ctx->g.nown; ++i) rho_zyx[i] = v3[3 * i];
-  return 0;
-}
-
-int xpic_moment_density(xpic_ctx* ctx, int sort, double* out_zyx)
-{
-  CTX_CHECK(ctx); SORT_CHECK(sort);
-  double* tmp = ctx->field[XPIC_W2];
-  XPIC_CALL(moment_density(ctx, ctx->sorts[sort], tmp));
-  std::vector<double> v3((size_t)ctx->g.nown * 3);
-  XPIC_CALL(field_export(ctx, tmp, v3.data()));
-  for (long i = 0; i < ctx->g.nown; ++i) out_zyx[i] = v3[3 * i];
-  return 0;
+  return export_components(ctx, tmp, 1, 1, rho_zyx);
 }
 
 int xpic_moment(xpic_ctx* ctx, int sort, int kind, const int region6[6], double* out)
@@ -879,14 +875,14 @@ int xpic_moment(xpic_ctx* ctx, int sort, int kind, const int region6[6], double*
   double* comp[6];
   for (int j = 0; j < 6; ++j) comp[j] = ctx->field[D > 3 ? XPIC_W1 + j / 3 : XPIC_W2] + (long)(j % 3) * g.cstride;
   XPIC_CALL(moment_region(ctx, ctx->sorts[sort], kind, region6, comp));
-  std::vector<double> v3((size_t)g.nown * 3);
-  for (int v = 0; v < (D + 2) / 3; ++v) {
-    XPIC_CALL(field_export(ctx, comp[3 * v], v3.data()));
-    const int nc = std::min(3, D - 3 * v);
-    for (long i = 0; i < g.nown; ++i)
-      for (int j = 0; j < nc; ++j) out[i * D + 3 * v + j] = v3[3 * i + j];
-  }
+  for (int v = 0; v < (D + 2) / 3; ++v) XPIC_CALL(export_components(ctx, comp[3 * v], std::min(3, D - 3 * v), D, out + 3 * v));
   return 0;
+}
+
+// DistributionMoment "density" over the whole grid
+int xpic_moment_density(xpic_ctx* ctx, int sort, double* out_zyx)
+{
+  return xpic_moment(ctx, sort, XPIC_MOMENT_DENSITY, nullptr, out_zyx);
 }
 
 int xpic_velocity_distribution(xpic_ctx* ctx, int sort, int projector, int geometry, const double geom[7],

@@ -25,6 +25,9 @@ namespace {
 
 constexpr int kBlock = 256;
 constexpr int kWaves = kBlock / 64;
+// workgroup size of the reductions' second stage (reduce_to_host) in this file: one wave, lane l sums the partials l,
+// l + 64, ...  The other files run it with 256 threads; that is a different order, and 64 is these results' order.
+constexpr int kSumThreads = 64;
 constexpr double kMec2 = 511.0;        // src/constants.h:30 (keV)
 constexpr int kCoilN = 2000;           // SetCoilsField::N (set_magnetic_field.h:42)
 constexpr double kCoilTol = 1e-10;     // SetCoilsField::denominator_tolerance (:40)
@@ -49,18 +52,6 @@ struct CmdGeom {
   double a[7];
 };
 
-// WithinBox / WithinCylinder (src/utils/geometries.cpp:3-19)
-__device__ inline bool within(const CmdGeom& G, double x, double y, double z)
-{
-  if (G.kind == XPIC_GEOM_BOX)
-    return (G.a[0] <= x && x < G.a[3]) && (G.a[1] <= y && y < G.a[4]) && (G.a[2] <= z && z < G.a[5]);
-  if (G.kind == XPIC_GEOM_CYLINDER) {
-    const double px = x - G.a[0], py = y - G.a[1], pz = z - G.a[2];
-    return (fabs(pz) < 0.5 * G.a[4]) && ((px * px + py * py) <= G.a[3] * G.a[3]);
-  }
-  return true;
-}
-
 __device__ inline void cell_xyz(const GridDev& g, long c, int* x, int* y, int* zl)
 {
   *x = (int)(c % g.nx);
@@ -74,30 +65,7 @@ __device__ inline bool keep_cell(const GridDev& g, const CmdGeom& G, long c)
   if (G.kind < 0) return true;
   int x, y, zl;
   cell_xyz(g, c, &x, &y, &zl);
-  return within(G, x * g.dx, y * g.dy, (g.z0 + zl) * g.dz);
-}
-
-__device__ inline double block_sum(double v, double* sm)
-{
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-  if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double t = 0;
-  if (threadIdx.x == 0)
-    for (int w = 0; w < kWaves; ++w) t += sm[w];
-  __syncthreads();
-  return t;
-}
-
-// partial[row * nblocks + b] -> out[row], one wave per row: lane l sums the blocks l, l + 64, ..., then the lanes are
-// folded (a fixed order)
-__global__ void __launch_bounds__(64) k_cmd_sum(const double* partial, int nblocks, double* out)
-{
-  const double* p = partial + (long)blockIdx.x * nblocks;
-  double t = 0;
-  for (int b = threadIdx.x; b < nblocks; b += 64) t += p[b];
-  for (int o = 32; o > 0; o >>= 1) t += __shfl_down(t, o, 64);
-  if (threadIdx.x == 0) out[blockIdx.x] = t;
+  return within(G.kind, G.a, x * g.dx, y * g.dy, (g.z0 + zl) * g.dz);
 }
 
 // new counts: the old ones of the cells that are kept (cell_start differences: cell_count may already hold a pre-binning
@@ -105,16 +73,14 @@ __global__ void __launch_bounds__(64) k_cmd_sum(const double* partial, int nbloc
 __global__ void __launch_bounds__(kBlock) k_cmd_count(GridDev g, const int* __restrict__ cs, CmdGeom G, const int* __restrict__ add,
   int* count, long ncell, double* partial)
 {
-  __shared__ double sm[kWaves];
-  double gone = 0;
+  double gone[1] = {0.0};
   for (long c = (long)blockIdx.x * kBlock + threadIdx.x; c < ncell; c += (long)gridDim.x * kBlock) {
     const int oc = cs[c + 1] - cs[c];
     const bool keep = oc == 0 || keep_cell(g, G, c);
     count[c] = (keep ? oc : 0) + (add ? add[c] : 0);
-    if (!keep) gone += oc;
+    if (!keep) gone[0] += oc;
   }
-  const double t = block_sum(gone, sm);
-  if (threadIdx.x == 0) partial[blockIdx.x] = t;
+  block_reduce_store<1, kBlock>(gone, partial, 0, blockIdx.x);
 }
 
 // One wave per cell (grid-stride over the cells): a kept cell's records are copied, coalesced, from cell_start[c] to
@@ -122,10 +88,9 @@ __global__ void __launch_bounds__(kBlock) k_cmd_count(GridDev g, const int* __re
 __global__ void __launch_bounds__(kBlock) k_cmd_move(GridDev g, SortDev s, const int* __restrict__ ns, CmdGeom G, double m,
   double mpw, long ncell, double* partial)
 {
-  __shared__ double sm[kWaves];
   const int lane = threadIdx.x & 63;
   const long nw = (long)gridDim.x * kWaves;
-  double e = 0;
+  double e[1] = {0.0};
   for (long c = (long)blockIdx.x * kWaves + (threadIdx.x >> 6); c < ncell; c += nw) {
     const int b = s.cell_start[c], cnt = s.cell_start[c + 1] - b;
     if (cnt == 0) continue;
@@ -142,12 +107,11 @@ __global__ void __launch_bounds__(kBlock) k_cmd_move(GridDev g, SortDev s, const
     else {
       for (int j = lane; j < cnt; j += 64) {
         const double vx = s.v[0][b + j], vy = s.v[1][b + j], vz = s.v[2][b + j];
-        e += 0.5 * (m * (vx * vx + vy * vy + vz * vz)) * mpw;
+        e[0] += 0.5 * (m * (vx * vx + vy * vy + vz * vz)) * mpw;
       }
     }
   }
-  const double t = block_sum(e, sm);
-  if (threadIdx.x == 0) partial[blockIdx.x] = t;
+  block_reduce_store<1, kBlock>(e, partial, 0, blockIdx.x);
 }
 
 // ---- InjectParticles ------------------------------------------------------------------------------------------------
@@ -217,8 +181,7 @@ template <int K>
 __global__ void __launch_bounds__(kBlock) k_inj_write(GridDev g, SortDev s, InjDev P, int64_t pairs, const int* __restrict__ ns,
   const int* __restrict__ count, const int* __restrict__ add, const int* __restrict__ prank, double mpw, double* partial)
 {
-  __shared__ double sm[kWaves];
-  double e = 0;
+  double e[1] = {0.0};
   for (int64_t p = (int64_t)blockIdx.x * kBlock + threadIdx.x; p < pairs; p += (int64_t)gridDim.x * kBlock) {
     const int rk = prank[p];
     if (rk < 0) continue;
@@ -235,10 +198,9 @@ __global__ void __launch_bounds__(kBlock) k_inj_write(GridDev g, SortDev s, InjD
       s.v2[a][d] = pm[K][a];
     }
     const double* v = pm[K];
-    e += 0.5 * (P.m[K] * (v[0] * v[0] + v[1] * v[1] + v[2] * v[2])) * mpw;
+    e[0] += 0.5 * (P.m[K] * (v[0] * v[0] + v[1] * v[1] + v[2] * v[2])) * mpw;
   }
-  const double t = block_sum(e, sm);
-  if (threadIdx.x == 0) partial[blockIdx.x] = t;
+  block_reduce_store<1, kBlock>(e, partial, 0, blockIdx.x);
 }
 
 // ---- FieldsDamping ---------------------------------------------------------------------------------------------------
@@ -275,8 +237,7 @@ __device__ inline double damp_factor(const GridDev& g, const CmdGeom& G, double 
 __global__ void __launch_bounds__(kBlock) k_damp(GridDev g, double* E, double* B, const double* __restrict__ B0, CmdGeom G,
   double coef, double* partial)
 {
-  __shared__ double sm[kWaves];
-  double e = 0;
+  double e[1] = {0.0};
   for (long i = (long)blockIdx.x * kBlock + threadIdx.x; i < g.nown; i += (long)gridDim.x * kBlock) {
     int x, y, zl;
     cell_xyz(g, i, &x, &y, &zl);
@@ -288,11 +249,11 @@ __global__ void __launch_bounds__(kBlock) k_damp(GridDev g, double* E, double* B
       b0[a] = B0[a * g.cstride + nd];
       fb[a] = B[a * g.cstride + nd] + (-1.0 * b0[a]);
     }
-    if (!within(G, r[0], r[1], r[2])) {
+    if (!within(G.kind, G.a, r[0], r[1], r[2])) {
       const double d = damp_factor(g, G, coef, r);
       const double k = 1.0 - d * d;
-      e += (0.5 * (fe[0] * fe[0] + fe[1] * fe[1] + fe[2] * fe[2])) * k;
-      e += (0.5 * (fb[0] * fb[0] + fb[1] * fb[1] + fb[2] * fb[2])) * k;
+      e[0] += (0.5 * (fe[0] * fe[0] + fe[1] * fe[1] + fe[2] * fe[2])) * k;
+      e[0] += (0.5 * (fb[0] * fb[0] + fb[1] * fb[1] + fb[2] * fb[2])) * k;
       for (int a = 0; a < 3; ++a) {
         fe[a] *= d;
         fb[a] *= d;
@@ -301,8 +262,7 @@ __global__ void __launch_bounds__(kBlock) k_damp(GridDev g, double* E, double* B
     }
     for (int a = 0; a < 3; ++a) B[a * g.cstride + nd] = fb[a] + 1.0 * b0[a];
   }
-  const double t = block_sum(e, sm);
-  if (threadIdx.x == 0) partial[blockIdx.x] = t;
+  block_reduce_store<1, kBlock>(e, partial, 0, blockIdx.x);
 }
 
 // ---- SetCoilsField ---------------------------------------------------------------------------------------------------
@@ -390,17 +350,6 @@ int cmd_scratch(xpic_ctx* c)
   return 0;
 }
 
-// partial rows -> host values (one synchronisation)
-int cmd_sums(xpic_ctx* c, int nblocks, int rows, double* out)
-{
-  hipLaunchKernelGGL(k_cmd_sum, dim3(rows), dim3(64), 0, c->stream, c->red_partial, nblocks, c->red_out);
-  XPIC_HIP(hipGetLastError());
-  XPIC_HIP(hipMemcpyAsync(c->red_host, c->red_out, sizeof(double) * rows, hipMemcpyDeviceToHost, c->stream));
-  XPIC_HIP(hipStreamSynchronize(c->stream));
-  for (int i = 0; i < rows; ++i) out[i] = c->red_host[i];
-  return 0;
-}
-
 // the new order of a sort whose new counts are in cell_count: scan, move the kept records (energy of the others into
 // partial[0 .. nblocks)), then `extra` writes the new records into r2 / v2 before the buffers are swapped
 template <class Extra>
@@ -439,11 +388,11 @@ int remove_particles(xpic_ctx* c, Sort& s, int geometry, const double* geom, int
     hipLaunchKernelGGL(k_cmd_count, dim3(nb), dim3(kBlock), 0, c->stream, c->g, s.d.cell_start, G, (const int*)nullptr,
       s.d.cell_count, (long)c->ncell, c->red_partial);
     XPIC_HIP(hipGetLastError());
-    XPIC_CALL(cmd_sums(c, nb, 1, res));
+    XPIC_CALL(reduce_to_host(c, 1, nb, 1, false, res, kSumThreads));
     if (res[0] > 0) { // (otherwise no record is touched)
       int total = 0;
       XPIC_CALL(cmd_rebuild(c, s, G, &total, [] { return 0; }));
-      XPIC_CALL(cmd_sums(c, kRedBlocks, 1, res + 1));
+      XPIC_CALL(reduce_to_host(c, 1, kRedBlocks, 1, false, res + 1, kSumThreads));
     }
   }
   XPIC_CALL(comm_allreduce_sum_host(c, res, 2)); // (log_statistics, remove_particles.cpp:47-48)
@@ -523,7 +472,7 @@ int inject_particles(xpic_ctx* c, Sort& si, Sort& se, const xpic_inject_params& 
         XPIC_HIP(hipGetLastError());
         return 0;
       }));
-      XPIC_CALL(cmd_sums(c, nw, 1, res + 1 + k));
+      XPIC_CALL(reduce_to_host(c, 1, nw, 1, false, res + 1 + k, kSumThreads));
     }
   }
   XPIC_CALL(comm_allreduce_sum_host(c, res, 3)); // (log_statistics, inject_particles.cpp:70-84)
@@ -542,7 +491,7 @@ int fields_damping(xpic_ctx* c, double* E, double* B, const double* B0, int geom
   hipLaunchKernelGGL(k_damp, dim3(nb), dim3(kBlock), 0, c->stream, c->g, E, B, B0, G, coefficient, c->red_partial);
   XPIC_HIP(hipGetLastError());
   double e[1];
-  XPIC_CALL(cmd_sums(c, nb, 1, e));
+  XPIC_CALL(reduce_to_host(c, 1, nb, 1, false, e, kSumThreads));
   XPIC_CALL(comm_allreduce_sum_host(c, e, 1)); // (execute, fields_damping.cpp:29)
   if (energy) *energy = e[0];
   return 0;

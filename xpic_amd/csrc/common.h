@@ -114,6 +114,8 @@ struct GridDev {
     if (G == 0) return z < 0 ? z + nzl : (z >= nzl ? z - nzl : z);
     return z + G;
   }
+  // any signed index folded into [0, n) (wx / wy / wz fold one box length)
+  __host__ __device__ static inline int wrap(int i, int n) { return ((i % n) + n) % n; }
   __host__ __device__ inline long node(int x, int y, int zs) const { return ((long)zs * ny + y) * nx + x; }
   // wrapped access: x,y,z are local signed indices
   __host__ __device__ inline long nodew(int x, int y, int z) const { return node(wx(x), wy(y), wz(z)); }
@@ -329,6 +331,10 @@ int scalar_norm12_host(xpic_ctx* c, const double* f, double* out2);
 int field_import(xpic_ctx* c, double* dst_soa, const double* src_aos_host);
 int field_export(xpic_ctx* c, const double* src_soa, double* dst_aos_host);
 int field_stats_host(xpic_ctx* c, const double* f, double* sumsq, double* mean3);
+// Second stage of every two-stage reduction: host_out[j * nseg + s] = sum over segment s of the nblocks partials of row j
+// in red_partial (device_common.h: block_reduce_store), one synchronisation.  allreduce: summed over the slabs on the
+// device first.  threads: workgroup size of the second stage, 256 or 64; it fixes the summation order.
+int reduce_to_host(xpic_ctx* c, int rows, int nblocks, int nseg, bool allreduce, double* host_out, int threads = 256);
 int halo_fill(xpic_ctx* c, double* f, int width = 3); // ghost planes <- neighbours' owned planes (no-op when G == 0)
 int halo_fill2(xpic_ctx* c, double* f0, double* f1, int width = 3); // two vectors, one message per neighbour
 int halo_add(xpic_ctx* c, double* f, int width);      // owned planes += neighbours' ghost planes (DMLocalToGlobal ADD)
@@ -352,7 +358,6 @@ int sort_occupancy(xpic_ctx* c, Sort& s, int64_t* out8);
 int exclusive_scan(xpic_ctx* c, const int* in, long n, int* out, int* total_host); // out[n] = total
 int ecsim_second_push(xpic_ctx* c, Sort& s, const double* E, const double* B, bool prebin = false);
 int charge_density(xpic_ctx* c, Sort& s, double* rho_vec);
-int moment_density(xpic_ctx* c, Sort& s, double* vec);
 int kinetic_sums_host(xpic_ctx* c, Sort& s, double* out5);   // local sums of vx, vy, vz, v^2 and the count
 int kinetic_sums_global(xpic_ctx* c, Sort& s, double* out5); // summed over the slabs
 int scale_velocities(xpic_ctx* c, Sort& s, double lambda);

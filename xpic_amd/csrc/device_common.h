@@ -1,4 +1,4 @@
-// device_common.h -- device-side helpers shared by the particle kernels.
+// device_common.h -- device-side helpers shared by the kernel files.
 #pragma once
 
 #include "common.h"
@@ -129,6 +129,56 @@ __device__ inline void update_vEB(double dt, double qm, const double* E, const d
   const double rden = 1.0 / den;
 #pragma unroll
   for (int c = 0; c < 3; ++c) v[c] += a[c] + (bw[c] + 0.5 * bbw[c]) * rden;
+}
+
+// ---- two-stage reductions: every kernel leaves one partial per workgroup and value, fields.hip's reduce_to_host sums
+// them.  The order is fixed (lanes folded 32, 16, .. 1, then the waves 0, 1, ..): the results do not depend on timing.
+__device__ inline double wave_sum(double v)
+{
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+  return v;
+}
+
+// block-reduce NV values of a workgroup of BLOCK threads, thread j writes partial[j*nblocks + block]
+template <int NV, int BLOCK>
+__device__ inline void block_reduce_store(double (&acc)[NV], double* partial, int nblocks, int block)
+{
+  __shared__ double sm[NV][BLOCK / 64];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int j = 0; j < NV; ++j) {
+    double v = wave_sum(acc[j]);
+    if (lane == 0) sm[j][wave] = v;
+  }
+  __syncthreads();
+  if (threadIdx.x < NV) {
+    double v = 0;
+#pragma unroll
+    for (int w = 0; w < BLOCK / 64; ++w) v += sm[threadIdx.x][w];
+    partial[(long)threadIdx.x * nblocks + block] = v;
+  }
+}
+
+// spline_of_2nd_order (src/interfaces/sort_parameters.cpp:21) in the reference's three-branch form, for the diagnostics and eccapfim
+// (esirkepov.hip's branch-free spline2 is a different expression)
+__device__ inline double spline2_ref(double s)
+{
+  s = fabs(s);
+  if (s <= 0.5) return (0.75 - s * s);
+  if (0.5 < s && s < 1.5) return 0.5 * (1.5 - s) * (1.5 - s);
+  return 0.0;
+}
+
+// WithinBox / WithinCylinder (src/utils/geometries.cpp:3-19).  a: box min xyz, max xyz; cylinder centre xyz, radius,
+// height.  Compiled without contraction whatever the including file's setting: px * px + py * py is rounded step by
+// step as in the reference, so a restatement of the test (tests/commands_ref.py, tests/moments_ref.py) decides the
+// same cells.
+__device__ inline bool within(int kind, const double* a, double x, double y, double z)
+{
+#pragma clang fp contract(off)
+  if (kind == XPIC_GEOM_BOX) return (a[0] <= x && x < a[3]) && (a[1] <= y && y < a[4]) && (a[2] <= z && z < a[5]);
+  const double px = x - a[0], py = y - a[1], pz = z - a[2];
+  return (fabs(pz) < 0.5 * a[4]) && ((px * px + py * py) <= a[3] * a[3]);
 }
 
 

@@ -22,14 +22,6 @@ __device__ inline double ie_sfunc_2(int j, double s)
   s = fabs(s);
   return j == 1 ? (0.75 - s * s) : 0.5 * (1.5 - s) * (1.5 - s);
 }
-__device__ inline double spline2_e(double s)
-{
-  s = fabs(s);
-  if (s <= 0.5) return (0.75 - s * s);
-  if (0.5 < s && s < 1.5) return 0.5 * (1.5 - s) * (1.5 - s);
-  return 0.0;
-}
-
 struct IEShape {
   int start[3];
   double cache[54];
@@ -73,8 +65,8 @@ struct IEShape {
 // node (gx, gy, gz) in global numbering -> element of component c of a field vector
 __device__ inline long ie_node(const GridDev& g, int gx, int gy, int gz)
 {
-  const int x = ((gx % g.nx) + g.nx) % g.nx, y = ((gy % g.ny) + g.ny) % g.ny;
-  const int zl = g.G == 0 ? ((gz % g.nzl) + g.nzl) % g.nzl : gz - g.z0;
+  const int x = g.wrap(gx, g.nx), y = g.wrap(gy, g.ny);
+  const int zl = g.G == 0 ? g.wrap(gz, g.nzl) : gz - g.z0;
   return g.node(x, y, g.wz(zl));
 }
 
@@ -98,8 +90,8 @@ __global__ void __launch_bounds__(kBlock) k_ie_interpolate(GridDev g, const doub
 #pragma unroll
       for (int t = 0; t < 4; ++t) {
         const double gx = (double)(st[a] + t);
-        No[a][t] = spline2_e(pr - gx);
-        Sh[a][t] = spline2_e(pr - (gx + 0.5));
+        No[a][t] = spline2_ref(pr - gx);
+        Sh[a][t] = spline2_ref(pr - (gx + 0.5));
       }
     }
     for (int kz = 0; kz < sz[2]; ++kz)

@@ -128,12 +128,6 @@ __device__ inline double spline2(double s)
   return s <= 0.5 ? (0.75 - s * s) : 0.5 * t * t;
 }
 
-__device__ inline double wave_sum_b(double v)
-{
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-  return v;
-}
-
 // value of lane `src` (wave-uniform) for every lane: v_readlane on the two halves
 __device__ inline double lane_value(double v, int src)
 {
@@ -1002,7 +996,7 @@ __global__ void __launch_bounds__(kThreadsB, MODE == 1 ? ESK_OCC1 : 2) k_esirkep
     for (int k = 0; k < 10; ++k) atomicAdd(&g_esk_stamps[k], stamp_acc_[k]);
 #endif
   if (MODE == 2) {
-    pw = wave_sum_b(pw);
+    pw = wave_sum(pw);
     if (lane == 0) pwsum[wave] = pw;
     __syncthreads();
     // pred_w: one partial per workgroup, summed by k_sum_partials in a fixed order (atomics of every wave on one
@@ -1018,7 +1012,7 @@ __global__ void __launch_bounds__(1024) k_sum_partials(const double* __restrict_
   double v = 0.0;
   for (long i = threadIdx.x; i < n; i += 1024) v += part[i];
   __shared__ double sm[16];
-  v = wave_sum_b(v);
+  v = wave_sum(v);
   if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = v;
   __syncthreads();
   if (threadIdx.x == 0) {

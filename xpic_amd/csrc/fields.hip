@@ -5,6 +5,7 @@
 #include <utility>
 
 #include "common.h"
+#include "device_common.h"
 #include "lstencil.h"
 
 namespace xpic {
@@ -48,33 +49,7 @@ int launch_ew(xpic_ctx* c, F f)
   return 0;
 }
 
-// ---- reductions -------------------------------------------------------------------------------------
-__device__ inline double wave_sum(double v)
-{
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-  return v;
-}
-
-// block-reduce NV values, thread 0 writes partial[j*nblocks + block]
-template <int NV>
-__device__ inline void block_reduce_store(double (&acc)[NV], double* partial, int nblocks, int block)
-{
-  __shared__ double sm[NV][kBlock / 64];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int j = 0; j < NV; ++j) {
-    double v = wave_sum(acc[j]);
-    if (lane == 0) sm[j][wave] = v;
-  }
-  __syncthreads();
-  if (threadIdx.x < NV) {
-    double v = 0;
-#pragma unroll
-    for (int w = 0; w < kBlock / 64; ++w) v += sm[threadIdx.x][w];
-    partial[(long)threadIdx.x * nblocks + block] = v;
-  }
-}
-
+// ---- reductions (device_common.h: block_reduce_store) ------------------------------------------------
 struct VPtrs { const double* p[8]; };
 struct HVals { double h[8]; };
 
@@ -94,7 +69,7 @@ __global__ void __launch_bounds__(kBlock) k_mdot(GridDev g, const double* w, VPt
     for (int j = 0; j < NV; ++j) acc[j] += wi * V.p[j][off + i];
     if (WW) acc[NV] += wi * wi;
   }
-  block_reduce_store<NV + (WW ? 1 : 0)>(acc, partial, gridDim.x * gridDim.y, blockIdx.y * gridDim.x + blockIdx.x);
+  block_reduce_store<NV + (WW ? 1 : 0), kBlock>(acc, partial, gridDim.x * gridDim.y, blockIdx.y * gridDim.x + blockIdx.x);
 }
 
 // out = (w - sum_j h_j V_j) * scale (out may be w itself); optionally partial[blk] = sum out^2
@@ -113,7 +88,7 @@ __global__ void __launch_bounds__(kBlock) k_maxpy(GridDev g, const double* w, VP
     out[off + i] = wi;
     if (NORM) acc[0] += wi * wi;
   }
-  if (NORM) block_reduce_store<1>(acc, partial, gridDim.x * gridDim.y, blockIdx.y * gridDim.x + blockIdx.x);
+  if (NORM) block_reduce_store<1, kBlock>(acc, partial, gridDim.x * gridDim.y, blockIdx.y * gridDim.x + blockIdx.x);
 }
 
 // sum of squares and per-component sums of one field: partial rows {sq, sum_c} per component block
@@ -127,25 +102,19 @@ __global__ void __launch_bounds__(kBlock) k_stats(GridDev g, const double* f, do
     acc[0] += v * v;
     acc[1] += v;
   }
-  block_reduce_store<2>(acc, partial, gridDim.x * gridDim.y, blockIdx.y * gridDim.x + blockIdx.x);
+  block_reduce_store<2, kBlock>(acc, partial, gridDim.x * gridDim.y, blockIdx.y * gridDim.x + blockIdx.x);
 }
 
-// out[j*nseg + s] = sum over segment s of partial[j*nblocks + ...]; one block per (j, s)
-__global__ void __launch_bounds__(kBlock) k_reduce_final(const double* partial, int nblocks, int nseg, double* out)
+// out[j*nseg + s] = sum over segment s of partial[j*nblocks + ...]; one block of THREADS per (j, s): thread t sums the
+// partials t, t + THREADS, ..., then the block is folded as in the first stage
+template <int THREADS>
+__global__ void __launch_bounds__(THREADS) k_reduce_final(const double* partial, int nblocks, int nseg, double* out)
 {
   const int j = blockIdx.x / nseg, s = blockIdx.x % nseg;
   const int seg = nblocks / nseg;
-  double v = 0;
-  for (int i = threadIdx.x; i < seg; i += kBlock) v += partial[(long)j * nblocks + s * seg + i];
-  __shared__ double sm[kBlock / 64];
-  v = wave_sum(v);
-  if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = v;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double t = 0;
-    for (int w = 0; w < kBlock / 64; ++w) t += sm[w];
-    out[blockIdx.x] = t;
-  }
+  double v[1] = {0.0};
+  for (int i = threadIdx.x; i < seg; i += THREADS) v[0] += partial[(long)j * nblocks + s * seg + i];
+  block_reduce_store<1, THREADS>(v, out, 0, blockIdx.x);
 }
 
 inline dim3 red_grid(const GridDev& g)
@@ -155,17 +124,6 @@ inline dim3 red_grid(const GridDev& g)
   if (blocks > cap) blocks = cap;
   if (blocks < 1) blocks = 1;
   return dim3((unsigned)blocks, 3, 1);
-}
-
-int finish_reduce(xpic_ctx* c, int nv, int nblocks, int nseg, double* host_out)
-{
-  hipLaunchKernelGGL(k_reduce_final, dim3(nv * nseg), dim3(kBlock), 0, c->stream, c->red_partial, nblocks, nseg, c->red_out);
-  XPIC_HIP(hipGetLastError());
-  XPIC_CALL(comm_allreduce_sum(c, c->red_out, nv * nseg)); // the MPI_Allreduce inside VecDot/VecMDot/VecNorm
-  XPIC_HIP(hipMemcpyAsync(c->red_host, c->red_out, sizeof(double) * nv * nseg, hipMemcpyDeviceToHost, c->stream));
-  XPIC_HIP(hipStreamSynchronize(c->stream));
-  for (int i = 0; i < nv * nseg; ++i) host_out[i] = c->red_host[i];
-  return 0;
 }
 
 // ---- curl: Rotor::fill_stencil + values (src/utils/operators.cpp:155-215) ---------------------------
@@ -275,7 +233,7 @@ __global__ void __launch_bounds__(kBlock) k_cg_apply_dot(GridDev g, const double
       acc[0] += p[o + c * g.cstride] * m[c];
     }
   }
-  block_reduce_store<1>(acc, partial, gridDim.x, blockIdx.x);
+  block_reduce_store<1, kBlock>(acc, partial, gridDim.x, blockIdx.x);
 }
 
 // x += alpha p ; r -= alpha Ap ; partial[blk] = sum r . r (after the update)
@@ -291,7 +249,7 @@ __global__ void __launch_bounds__(kBlock) k_cg_update(GridDev g, double alpha, c
     r[off + i] = rv;
     acc[0] += rv * rv;
   }
-  block_reduce_store<1>(acc, partial, gridDim.x * gridDim.y, blockIdx.y * gridDim.x + blockIdx.x);
+  block_reduce_store<1, kBlock>(acc, partial, gridDim.x * gridDim.y, blockIdx.y * gridDim.x + blockIdx.x);
 }
 
 // ---- Chebyshev step on matM: res = r - matM z_in ; d = cd d + cr res ; z_out = z_in + d.
@@ -566,7 +524,7 @@ __global__ void __launch_bounds__(kBlock) k_norm12(GridDev g, const double* f, d
     acc[0] += fabs(v);
     acc[1] += v * v;
   }
-  block_reduce_store<2>(acc, partial, gridDim.x, blockIdx.x);
+  block_reduce_store<2, kBlock>(acc, partial, gridDim.x, blockIdx.x);
 }
 
 // ---- boundary layout conversion: [z][y][x][3] (reference DMDA order) <-> SoA with ghost planes ----
@@ -593,6 +551,19 @@ __global__ void __launch_bounds__(kBlock) k_export(GridDev g, const double* soa,
 }
 
 }  // namespace
+
+int reduce_to_host(xpic_ctx* c, int rows, int nblocks, int nseg, bool allreduce, double* host_out, int threads)
+{
+  const int n = rows * nseg;
+  if (threads == 64) hipLaunchKernelGGL(k_reduce_final<64>, dim3(n), dim3(64), 0, c->stream, c->red_partial, nblocks, nseg, c->red_out);
+  else hipLaunchKernelGGL(k_reduce_final<kBlock>, dim3(n), dim3(kBlock), 0, c->stream, c->red_partial, nblocks, nseg, c->red_out);
+  XPIC_HIP(hipGetLastError());
+  if (allreduce) XPIC_CALL(comm_allreduce_sum(c, c->red_out, n)); // the MPI_Allreduce inside VecDot/VecMDot/VecNorm
+  XPIC_HIP(hipMemcpyAsync(c->red_host, c->red_out, sizeof(double) * n, hipMemcpyDeviceToHost, c->stream));
+  XPIC_HIP(hipStreamSynchronize(c->stream));
+  for (int i = 0; i < n; ++i) host_out[i] = c->red_host[i];
+  return 0;
+}
 
 int vec_set(xpic_ctx* c, double* y, double a) { return launch_ew(c, FSet{y, a}); }
 int vec_copy(xpic_ctx* c, double* y, const double* x) { return launch_ew(c, FCopy{y, x}); }
@@ -624,9 +595,9 @@ int vec_mdot_ww_host(xpic_ctx* c, const double* w, const double* V, int nv, doub
     }
     XPIC_HIP(hipGetLastError());
   }
-  if (!ww) return finish_reduce(c, nv, nblocks, 1, out);
+  if (!ww) return reduce_to_host(c, nv, nblocks, 1, true, out);
   double tmp[kMaxDots + 1];
-  XPIC_CALL(finish_reduce(c, nv + 1, nblocks, 1, tmp));
+  XPIC_CALL(reduce_to_host(c, nv + 1, nblocks, 1, true, tmp));
   for (int i = 0; i < nv; ++i) out[i] = tmp[i];
   *ww = tmp[nv];
   return 0;
@@ -670,7 +641,7 @@ int vec_maxpy_scaled(xpic_ctx* c, const double* w, const double* V, int nv, cons
     XPIC_HIP(hipGetLastError());
     src = out; // later groups continue on the partial result
   }
-  if (nrm2) return finish_reduce(c, 1, nblocks, 1, nrm2);
+  if (nrm2) return reduce_to_host(c, 1, nblocks, 1, true, nrm2);
   return 0;
 }
 
@@ -693,7 +664,7 @@ int field_stats_host(xpic_ctx* c, const double* f, double* sumsq, double* mean3)
   hipLaunchKernelGGL(k_stats, grid, dim3(kBlock), 0, c->stream, c->g, f, c->red_partial);
   XPIC_HIP(hipGetLastError());
   double out[6];
-  XPIC_CALL(finish_reduce(c, 2, nblocks, 3, out)); // out[j*3 + comp]
+  XPIC_CALL(reduce_to_host(c, 2, nblocks, 3, true, out)); // out[j*3 + comp]
   *sumsq = out[0] + out[1] + out[2];
   mean3[0] = out[3]; mean3[1] = out[4]; mean3[2] = out[5];
   return 0;
@@ -707,7 +678,7 @@ int cg_apply_dot_host(xpic_ctx* c, const double* p, double* Ap, double* pAp)
   if (blocks > kRedBlocks) blocks = kRedBlocks;
   hipLaunchKernelGGL(k_cg_apply_dot, dim3((unsigned)blocks), dim3(kBlock), 0, c->stream, c->g, p, Ap, c->red_partial);
   XPIC_HIP(hipGetLastError());
-  return finish_reduce(c, 1, (int)blocks, 1, pAp);
+  return reduce_to_host(c, 1, (int)blocks, 1, true, pAp);
 }
 
 // x += alpha p ; r -= alpha Ap ; *rr = r . r
@@ -716,7 +687,7 @@ int cg_update_host(xpic_ctx* c, double alpha, const double* p, const double* Ap,
   dim3 grid = red_grid(c->g);
   hipLaunchKernelGGL(k_cg_update, grid, dim3(kBlock), 0, c->stream, c->g, alpha, p, Ap, x, r, c->red_partial);
   XPIC_HIP(hipGetLastError());
-  return finish_reduce(c, 1, grid.x * grid.y, 1, rr);
+  return reduce_to_host(c, 1, grid.x * grid.y, 1, true, rr);
 }
 
 int rot_apply(xpic_ctx* c, int sign, double alpha, const double* x, double* y, bool add)
@@ -898,7 +869,7 @@ int scalar_norm12_host(xpic_ctx* c, const double* f, double* out2) // VecNorm(NO
   if (blocks < 1) blocks = 1;
   hipLaunchKernelGGL(k_norm12, dim3((unsigned)blocks), dim3(kBlock), 0, c->stream, c->g, f, c->red_partial);
   XPIC_HIP(hipGetLastError());
-  XPIC_CALL(finish_reduce(c, 2, (int)blocks, 1, out2));
+  XPIC_CALL(reduce_to_host(c, 2, (int)blocks, 1, true, out2));
   out2[1] = std::sqrt(out2[1]);
   return 0;
 }

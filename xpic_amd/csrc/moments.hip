@@ -217,14 +217,6 @@ struct VdParams {
   double n_Np;
 };
 
-__device__ inline bool vd_within(const VdParams& P, double x, double y, double z)
-{
-  if (P.geom == XPIC_GEOM_BOX) // WithinBox (src/utils/geometries.cpp:3-9)
-    return (P.gp[0] <= x && x < P.gp[3]) && (P.gp[1] <= y && y < P.gp[4]) && (P.gp[2] <= z && z < P.gp[5]);
-  const double px = x - P.gp[0], py = y - P.gp[1], pz = z - P.gp[2]; // WithinCylinder (:12-19)
-  return (fabs(pz) < 0.5 * P.gp[4]) && ((px * px + py * py) <= P.gp[3] * P.gp[3]);
-}
-
 template <bool LDS>
 __global__ void __launch_bounds__(kVdThreads) k_vdist(GridDev g, SortDev s, VdParams P, double* hist)
 {
@@ -242,7 +234,7 @@ __global__ void __launch_bounds__(kVdThreads) k_vdist(GridDev g, SortDev s, VdPa
     __syncthreads();
     const double cy = (yy + 0.5) * g.dy, cz = (zz + g.z0 + 0.5) * g.dz;
     for (int x = xa + threadIdx.x; x < xb; x += kVdThreads)
-      if (vd_within(P, (x + 0.5) * g.dx, cy, cz)) {
+      if (within(P.geom, P.gp, (x + 0.5) * g.dx, cy, cz)) {
         atomicMin(&xr[0], x);
         atomicMax(&xr[1], x);
       }

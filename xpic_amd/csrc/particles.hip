@@ -489,12 +489,6 @@ __global__ void __launch_bounds__(kSPRound) k_second_push(GridDev g, SortDev s, 
   }
 }
 
-__device__ inline double wave_sum(double v)
-{
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-  return v;
-}
-
 // sums of vx, vy, vz, v^2 (Energy::calculate_kinetic, src/diagnostics/energy.cpp:61-108)
 __global__ void __launch_bounds__(kBlock) k_kinetic(SortDev s, int64_t n, double* partial, int nblocks)
 {
@@ -505,32 +499,7 @@ __global__ void __launch_bounds__(kBlock) k_kinetic(SortDev s, int64_t n, double
     a[0] += vx; a[1] += vy; a[2] += vz;
     a[3] += vx * vx + vy * vy + vz * vz;
   }
-  __shared__ double sm[4][kBlock / 64];
-  for (int j = 0; j < 4; ++j) {
-    double v = wave_sum(a[j]);
-    if ((threadIdx.x & 63) == 0) sm[j][threadIdx.x >> 6] = v;
-  }
-  __syncthreads();
-  if (threadIdx.x < 4) {
-    double v = 0;
-    for (int w = 0; w < kBlock / 64; ++w) v += sm[threadIdx.x][w];
-    partial[(long)threadIdx.x * nblocks + blockIdx.x] = v;
-  }
-}
-
-__global__ void __launch_bounds__(kBlock) k_sum_rows(const double* partial, int nblocks, double* out)
-{
-  double v = 0;
-  for (int i = threadIdx.x; i < nblocks; i += kBlock) v += partial[(long)blockIdx.x * nblocks + i];
-  __shared__ double sm[kBlock / 64];
-  v = wave_sum(v);
-  if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = v;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double t = 0;
-    for (int w = 0; w < kBlock / 64; ++w) t += sm[w];
-    out[blockIdx.x] = t;
-  }
+  block_reduce_store<4, kBlock>(a, partial, nblocks, blockIdx.x);
 }
 
 // BorisPush::update_r (src/algorithms/boris_push.cpp:19-22) over a whole sort
@@ -551,15 +520,7 @@ __global__ void __launch_bounds__(kBlock) k_scale_v(SortDev s, int64_t n, double
 }
 
 // ParticlesChargeDensity::collect (src/diagnostics/charge_conservation.cpp:34-97): 3 x 3 x 3 nodes from
-// ceil(r/dx - 1.5), weight spline2 x spline2 x spline2, value q * n/Np.  Diagnostic, off the hot path: plain atomics.
-__device__ inline double spline2_d(double s)
-{
-  s = fabs(s);
-  if (s <= 0.5) return (0.75 - s * s);
-  if (0.5 < s && s < 1.5) return 0.5 * (1.5 - s) * (1.5 - s);
-  return 0.0;
-}
-
+// ceil(r/dx - 1.5), weight spline2_ref in x, y and z, value q * n/Np.  Diagnostic, off the hot path: plain atomics.
 __global__ void __launch_bounds__(kBlock) k_charge_density(GridDev g, SortDev s, int64_t n, double qn, double* rho)
 {
   const int64_t p = (int64_t)blockIdx.x * kBlock + threadIdx.x;
@@ -571,7 +532,7 @@ __global__ void __launch_bounds__(kBlock) k_charge_density(GridDev g, SortDev s,
   for (int a = 0; a < 3; ++a) {
     st[a] = (int)ceil(pr[a] - 1.5);
 #pragma unroll
-    for (int t = 0; t < 3; ++t) w[a][t] = spline2_d(pr[a] - (double)(st[a] + t));
+    for (int t = 0; t < 3; ++t) w[a][t] = spline2_ref(pr[a] - (double)(st[a] + t));
   }
   st[2] -= g.z0;
 #pragma unroll
@@ -581,38 +542,10 @@ __global__ void __launch_bounds__(kBlock) k_charge_density(GridDev g, SortDev s,
 #pragma unroll
       for (int i = 0; i < 3; ++i) {
         // cache[i] = sfunc(x) * sfunc(y) * sfunc(z); arr += q * cache * n_Np   (:57, :90)
-        const int x = ((st[0] + i) % g.nx + g.nx) % g.nx, y = ((st[1] + j) % g.ny + g.ny) % g.ny;
+        const int x = g.wrap(st[0] + i, g.nx), y = g.wrap(st[1] + j, g.ny);
         const double v = w[0][i] * w[1][j] * w[2][k];
         if (v != 0.0) unsafeAtomicAdd(&rho[g.node(x, y, g.wz(st[2] + k))], qn * v);
       }
-}
-
-// DistributionMoment::collect, moment "density" (src/diagnostics/distribution_moment.cpp:125-216): cell-centred,
-// 2 x 2 x 2 cells from round(r/dx - 1), spline_of_1st_order, value n/Np
-__global__ void __launch_bounds__(kBlock) k_moment_density(GridDev g, SortDev s, int64_t n, double n_Np, double* out)
-{
-  const int64_t p = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-  if (p >= n) return;
-  const double pr[3] = {s.r[0][p] / g.dx, s.r[1][p] / g.dy, s.r[2][p] / g.dz};
-  int st[3];
-  double w[3][2];
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    st[a] = (int)round(pr[a] - 1.0);
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-      const double d = fabs(pr[a] - ((double)(st[a] + t) + 0.5));
-      w[a][t] = d <= 1.0 ? 1.0 - d : 0.0;
-    }
-  }
-  st[2] -= g.z0;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    const int ix = i % 2, iy = (i / 2) % 2, iz = i / 4;
-    const int x = ((st[0] + ix) % g.nx + g.nx) % g.nx, y = ((st[1] + iy) % g.ny + g.ny) % g.ny;
-    const double c = w[0][ix] * w[1][iy] * w[2][iz];
-    if (c != 0.0) unsafeAtomicAdd(&out[g.node(x, y, g.wz(st[2] + iz))], c * n_Np);
-  }
 }
 
 // MomentumConservation::calculate (src/diagnostics/momentum_conservation.cpp:77-131): per particle the 2nd-order
@@ -637,8 +570,8 @@ __global__ void __launch_bounds__(kBlock) k_momentum(GridDev g, SortDev s, int64
 #pragma unroll
       for (int t = 0; t < 4; ++t) {
         const double gx = (double)(st[c] + t);
-        No[c][t] = spline2_d(pr - gx);
-        Sh[c][t] = spline2_d(pr - (gx + 0.5));
+        No[c][t] = spline2_ref(pr - gx);
+        Sh[c][t] = spline2_ref(pr - (gx + 0.5));
       }
     }
     st[2] -= g.z0;
@@ -656,17 +589,7 @@ __global__ void __launch_bounds__(kBlock) k_momentum(GridDev g, SortDev s, int64
           a[5] += q * E[2 * g.cstride + node] * (Sh[2][kz] * No[1][jy] * No[0][ix]);
         }
   }
-  __shared__ double sm[6][kBlock / 64];
-  for (int j = 0; j < 6; ++j) {
-    double v = wave_sum(a[j]);
-    if ((threadIdx.x & 63) == 0) sm[j][threadIdx.x >> 6] = v;
-  }
-  __syncthreads();
-  if (threadIdx.x < 6) {
-    double v = 0;
-    for (int w = 0; w < kBlock / 64; ++w) v += sm[threadIdx.x][w];
-    partial[(long)threadIdx.x * nblocks + blockIdx.x] = v;
-  }
+  block_reduce_store<6, kBlock>(a, partial, nblocks, blockIdx.x);
 }
 
 // AoS Point records (host staging buffer on device) -> SoA tail of the sort
@@ -1243,19 +1166,6 @@ int charge_density(xpic_ctx* c, Sort& s, double* rho_vec)
   return halo_add(c, rho_vec, 3); // DMLocalToGlobal(ADD) :95
 }
 
-int moment_density(xpic_ctx* c, Sort& s, double* vec)
-{
-  XPIC_CALL(sort_materialize(c, s)); // (a deferred re-binning whose assembly has not run)
-  XPIC_HIP(hipMemsetAsync(vec, 0, sizeof(double) * c->nvec, c->stream));
-  if (s.n > 0) {
-    Timed t(c, "moment_density");
-    hipLaunchKernelGGL(k_moment_density, dim3(pgrid(s.n)), dim3(kBlock), 0, c->stream, c->g, s.d, s.n,
-      s.par.n / s.par.Np, vec);
-    XPIC_HIP(hipGetLastError());
-  }
-  return halo_add(c, vec, 3);
-}
-
 int kinetic_sums_host(xpic_ctx* c, Sort& s, double* out5)
 {
   XPIC_CALL(sort_materialize(c, s)); // (a deferred re-binning whose assembly has not run)
@@ -1265,12 +1175,8 @@ int kinetic_sums_host(xpic_ctx* c, Sort& s, double* out5)
   int nblocks = (int)pgrid(s.n, 8);
   if (nblocks > kRedBlocks) nblocks = kRedBlocks;
   hipLaunchKernelGGL(k_kinetic, dim3(nblocks), dim3(kBlock), 0, c->stream, s.d, s.n, c->red_partial, nblocks);
-  hipLaunchKernelGGL(k_sum_rows, dim3(4), dim3(kBlock), 0, c->stream, c->red_partial, nblocks, c->red_out);
   XPIC_HIP(hipGetLastError());
-  XPIC_HIP(hipMemcpyAsync(c->red_host, c->red_out, sizeof(double) * 4, hipMemcpyDeviceToHost, c->stream));
-  XPIC_HIP(hipStreamSynchronize(c->stream));
-  for (int i = 0; i < 4; ++i) out5[i] = c->red_host[i];
-  return 0;
+  return reduce_to_host(c, 4, nblocks, 1, false, out5); // (the slabs are summed on the host: kinetic_sums_global)
 }
 
 // the MPI_Allreduce of Energy::calculate_kinetic / calculate_energy (energy.cpp:92-93, ecsimcorr/particles.cpp:148)
@@ -1290,11 +1196,8 @@ int momentum_sums_global(xpic_ctx* c, Sort& s, const double* E, double* out6)
     if (nblocks > kRedBlocks) nblocks = kRedBlocks;
     hipLaunchKernelGGL(k_momentum, dim3(nblocks), dim3(kBlock), 0, c->stream, c->g, s.d, s.n, E, s.par.m / s.par.Np,
       s.par.q / s.par.Np, c->red_partial, nblocks);
-    hipLaunchKernelGGL(k_sum_rows, dim3(6), dim3(kBlock), 0, c->stream, c->red_partial, nblocks, c->red_out);
     XPIC_HIP(hipGetLastError());
-    XPIC_HIP(hipMemcpyAsync(c->red_host, c->red_out, sizeof(double) * 6, hipMemcpyDeviceToHost, c->stream));
-    XPIC_HIP(hipStreamSynchronize(c->stream));
-    for (int i = 0; i < 6; ++i) out6[i] = c->red_host[i];
+    XPIC_CALL(reduce_to_host(c, 6, nblocks, 1, false, out6));
   }
   return comm_allreduce_sum_host(c, out6, 6);
 }
