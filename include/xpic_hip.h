@@ -71,7 +71,7 @@ const char* xpic_last_error(void);
 /* XPIC_VERSION, with XPIC_VERSION_EXPERIMENT_BIT set when any object of the library was built with -DXPIC_EXPERIMENT
  * (ablation switches and in-kernel timers of the kernels; some produce wrong physics by design): refuse such a library
  * for production runs. */
-#define XPIC_VERSION 4
+#define XPIC_VERSION 5
 #define XPIC_VERSION_EXPERIMENT_BIT 0x40000000
 int xpic_version(void);
 
@@ -368,6 +368,37 @@ int xpic_implicit_esirkepov_interpolate(xpic_ctx* ctx, int64_t n, const double* 
  * DMLocalToGlobal(ADD_VALUES).  Uses the scratch vector XPIC_W2. */
 int xpic_implicit_esirkepov_decompose(xpic_ctx* ctx, int64_t n, const double* alpha, const double* v3, const double* rn3,
   const double* r03, int field);
+
+/* ---- drift-kinetic (guiding-centre) pusher on the context's static fields, batch form over n particles (host arrays).
+ * A particle is six doubles {x, y, z, p_parallel, p_perp, mu_p} (PointByField, src/interfaces/point.h:37-58).
+ * gradB_field: any xpic_field id whose vector the caller has filled with grad |B| (a scratch vector such as XPIC_W0), or
+ * -1 for the reference's gradB_g == nullptr (grad B = 0).  Positions are not folded into the box: the gathers wrap
+ * their node indices, folding is the caller's business as correct_coordinates is in the reference.  Single z-slab
+ * contexts only (nranks == 1, no self_ring).  n == 0 succeeds and touches nothing.
+ * xpic_drift_kinetic_interpolate: DriftKineticEsirkepov::interpolate (src/algorithms/drift_kinetic_implicit.cpp:11-31):
+ * E_p with the segment shape of (rn, r0) as xpic_implicit_esirkepov_interpolate, B_p and gradB_p with Shape(rn) (radius
+ * 1.5, 2nd-order spline) + SimpleInterpolation's magnetic products -- at rn, not at the midpoint. */
+typedef struct xpic_dk_params {
+  double qm, mp;     /* DriftKineticPush::set_qm / set_mp */
+  double dt;
+  double eps, delta; /* set_tolerances: residual bounds of the position and of p_parallel (reference default 1e-12) */
+  int maxit;         /* >= 1 (reference default 30) */
+} xpic_dk_params;
+int xpic_drift_kinetic_interpolate(xpic_ctx* ctx, int64_t n, const double* rn3, const double* r03, int gradB_field,
+  double* Ep3, double* Bp3, double* gradBp3);
+/* DriftKineticPush::process (src/algorithms/drift_kinetic_push.cpp:48-108) from the initial guess pn = p0, with the fields
+ * of xpic_drift_kinetic_interpolate(p0.r -> pn.r).  iterations[q] is the reference's get_iteration_number(): the updates
+ * made, >= 1; == maxit for a particle that did not meet the tolerances (the reference aborts there; here the caller
+ * decides). */
+int xpic_drift_kinetic_push(xpic_ctx* ctx, int64_t n, const xpic_dk_params* params, int gradB_field, const double* p0_6,
+  double* pn_6, int* iterations);
+/* `steps` pushes in a row with the particles kept on the device, in launches of at most XPIC_DK_LAUNCH_STEPS steps:
+ * state_6 is read and overwritten with the result, bit for bit that of `steps` calls of xpic_drift_kinetic_push.  samples
+ * (or NULL): the state after every sample_every-th step (>= 1), samples[(k * n + q) * 6 ..] for k < steps / sample_every.
+ * iterations_total[q] / iterations_max[q]: sum and maximum of the particle's iteration counts over the steps. */
+#define XPIC_DK_LAUNCH_STEPS 64
+int xpic_drift_kinetic_trace(xpic_ctx* ctx, int64_t n, const xpic_dk_params* params, int gradB_field, int64_t steps,
+  int64_t sample_every, double* state_6, double* samples, int64_t* iterations_total, int* iterations_max);
 
 /* ---- z-slab decomposition (DMDA da_processors_z = nranks; src/utils/world.cpp:36-38).  A context created with
  * nranks > 1 owns planes [rank*nz/nranks, (rank+1)*nz/nranks) and must be given a communicator before any

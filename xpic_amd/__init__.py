@@ -30,7 +30,8 @@ SYMBOLS = [
     "xpic_calculate_energy", "xpic_ecsimcorr_scalars", "xpic_solve", "xpic_set_tolerances", "xpic_set_preconditioner", "xpic_set_overlap", "xpic_comm_stats", "xpic_set_fill_kernel", "xpic_set_fused_rebin", "xpic_get_fill_variant", "xpic_debug_set", "xpic_step",
     "xpic_energy", "xpic_momentum", "xpic_charge_density", "xpic_moment_density", "xpic_moment", "xpic_velocity_distribution", "xpic_remove_particles", "xpic_fields_damping",
     "xpic_inject_particles", "xpic_set_coils_field", "xpic_cell_traversal", "xpic_implicit_esirkepov_interpolate",
-    "xpic_implicit_esirkepov_decompose", "xpic_charge_collect", "xpic_charge_columns", "xpic_comm_rccl_unique_id", "xpic_comm_init_rccl", "xpic_comm_init_callbacks", "xpic_comm_size", "xpic_comm_peer_export", "xpic_comm_peer_import",
+    "xpic_implicit_esirkepov_decompose", "xpic_drift_kinetic_interpolate", "xpic_drift_kinetic_push",
+    "xpic_drift_kinetic_trace", "xpic_charge_collect", "xpic_charge_columns", "xpic_comm_rccl_unique_id", "xpic_comm_init_rccl", "xpic_comm_init_callbacks", "xpic_comm_size", "xpic_comm_peer_export", "xpic_comm_peer_import",
     "xpic_profile_enable", "xpic_profile_reset", "xpic_profile_get", "xpic_probe_copy_bandwidth",
 ]
 
@@ -105,6 +106,31 @@ LOAD_PROFILES = {"poisson": 0, "uniform": 0, "regular": 1, "gradient": 2, "blob"
 
 class SortParams(C.Structure):
     _fields_ = [("Np", C.c_int32), ("n", C.c_double), ("q", C.c_double), ("m", C.c_double)]
+
+
+class DkParams(C.Structure):  # include/xpic_hip.h: xpic_dk_params
+    _fields_ = [("qm", C.c_double), ("mp", C.c_double), ("dt", C.c_double), ("eps", C.c_double), ("delta", C.c_double),
+                ("maxit", C.c_int32)]
+
+
+DK_LAUNCH_STEPS = 64  # include/xpic_hip.h: XPIC_DK_LAUNCH_STEPS
+
+
+def guiding_centre(points6, B3, mp, qm):
+    """PointByField(point, Bp, mp, qm) (src/interfaces/point.h:52-58) for records {r, p} and the field B3 at each of them
+    -> records {guiding centre xyz, p_parallel, p_perp, mu_p}, the particles of Context.drift_kinetic_push"""
+    pts = np.asarray(points6, dtype=np.float64).reshape(-1, 6)
+    Bp = np.broadcast_to(np.asarray(B3, dtype=np.float64), (pts.shape[0], 3))
+    r, p = pts[:, :3], pts[:, 3:]
+    lB = np.sqrt((Bp * Bp).sum(axis=1))[:, None]
+    b = np.divide(Bp, lB, out=np.zeros_like(p), where=lB > 0)  # Vector3::normalized
+    par = (p * Bp).sum(axis=1)[:, None] * Bp / (Bp * Bp).sum(axis=1)[:, None]  # Vector3::parallel_to
+    out = np.empty((pts.shape[0], 6))
+    out[:, :3] = r - np.cross(p, b) / (qm * lB)
+    out[:, 3] = np.sqrt((par * par).sum(axis=1))
+    out[:, 4] = np.sqrt(((p - par) ** 2).sum(axis=1))
+    out[:, 5] = mp * out[:, 4] * out[:, 4] / (2.0 * lB[:, 0])
+    return out
 
 
 _lib = None
@@ -524,6 +550,46 @@ class Context:
         alpha, v = np.ascontiguousarray(alpha, dtype=np.float64), np.ascontiguousarray(v, dtype=np.float64)
         rn, r0 = np.ascontiguousarray(rn, dtype=np.float64), np.ascontiguousarray(r0, dtype=np.float64)
         self._ck(self.L.xpic_implicit_esirkepov_decompose(self.h, C.c_int64(rn.shape[0]), _dp(alpha), _dp(v), _dp(rn), _dp(r0), field))
+
+    # ---- drift-kinetic pusher (include/xpic_hip.h: xpic_drift_kinetic_*); particles are records {x, y, z, p_parallel,
+    # p_perp, mu_p} (guiding_centre), gradB_field a field id filled with grad |B| or None
+    @staticmethod
+    def _dk_params(qm, mp, dt, eps, delta, maxit):
+        return DkParams(float(qm), float(mp), float(dt), float(eps), float(delta), int(maxit))
+
+    def drift_kinetic_interpolate(self, rn, r0, gradB_field=None):
+        """DriftKineticEsirkepov::interpolate -> (E_p, B_p, gradB_p): E over the segment r0 -> rn, B and grad B at rn"""
+        rn, r0 = np.ascontiguousarray(rn, dtype=np.float64), np.ascontiguousarray(r0, dtype=np.float64)
+        Ep, Bp, gBp = np.zeros_like(rn), np.zeros_like(rn), np.zeros_like(rn)
+        self._ck(self.L.xpic_drift_kinetic_interpolate(self.h, C.c_int64(rn.shape[0]), _dp(rn), _dp(r0),
+                                                       -1 if gradB_field is None else int(gradB_field), _dp(Ep), _dp(Bp), _dp(gBp)))
+        return Ep, Bp, gBp
+
+    def drift_kinetic_push(self, p0, qm, mp, dt, gradB_field=None, eps=1e-12, delta=1e-12, maxit=30):
+        """DriftKineticPush::process of every particle -> (pn, iterations); iterations == maxit: not converged"""
+        p0 = np.ascontiguousarray(p0, dtype=np.float64).reshape(-1, 6)
+        pn = np.zeros_like(p0)
+        its = np.zeros(p0.shape[0], dtype=np.int32)
+        P = self._dk_params(qm, mp, dt, eps, delta, maxit)
+        self._ck(self.L.xpic_drift_kinetic_push(self.h, C.c_int64(p0.shape[0]), C.byref(P),
+                                                -1 if gradB_field is None else int(gradB_field), _dp(p0), _dp(pn),
+                                                its.ctypes.data_as(C.POINTER(C.c_int))))
+        return pn, its
+
+    def drift_kinetic_trace(self, state, steps, qm, mp, dt, gradB_field=None, sample_every=0, eps=1e-12, delta=1e-12, maxit=30):
+        """`steps` pushes with the particles kept on the device -> (state, samples [steps // sample_every][n][6] or None,
+        iterations_total, iterations_max)"""
+        state = np.array(state, dtype=np.float64).reshape(-1, 6)  # a copy: the call works in place
+        n = state.shape[0]
+        nsamp = int(steps) // int(sample_every) if sample_every else 0
+        samples = np.zeros((nsamp, n, 6)) if sample_every else None
+        tot, mx = np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int32)
+        P = self._dk_params(qm, mp, dt, eps, delta, maxit)
+        self._ck(self.L.xpic_drift_kinetic_trace(self.h, C.c_int64(n), C.byref(P), -1 if gradB_field is None else int(gradB_field),
+                                                 C.c_int64(int(steps)), C.c_int64(int(sample_every)), _dp(state),
+                                                 _dp(samples) if sample_every else None, tot.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                 mx.ctypes.data_as(C.POINTER(C.c_int))))
+        return state, samples, tot, mx
 
     def charge_collect(self):
         self._ck(self.L.xpic_charge_collect(self.h))

@@ -944,6 +944,69 @@ int xpic_set_coils_field(xpic_ctx* ctx, int field, int ncoils, const double* coi
   return set_coils_field(ctx, ctx->field[field], ncoils, coils3);
 }
 
+// the checks the three drift-kinetic calls share; *gradB: the vector of gradB_field, null for -1
+static int dk_check(xpic_ctx* ctx, int64_t n, int gradB_field, const double** gradB)
+{
+  CTX_CHECK(ctx);
+  XPIC_CHECK(n >= 0, "drift_kinetic: n is negative");
+  XPIC_CHECK(ctx->geom.nranks == 1 && ctx->g.G == 0,
+    "drift_kinetic: a context of several z-slabs (or a self_ring one) is not supported: the gathers wrap z in the kernel");
+  XPIC_CHECK(gradB_field == -1 || (valid_field(gradB_field) && ctx->field[gradB_field]),
+    "drift_kinetic: gradB_field is neither -1 nor an allocated field id");
+  *gradB = gradB_field == -1 ? nullptr : ctx->field[gradB_field];
+  return 0;
+}
+
+static int dk_check_params(const xpic_dk_params* P)
+{
+  XPIC_CHECK(P, "drift_kinetic: params is null");
+  XPIC_CHECK(P->maxit >= 1, "drift_kinetic: maxit must be >= 1");
+  XPIC_CHECK(P->mp != 0.0, "drift_kinetic: mp must not be 0");
+  return 0;
+}
+
+int xpic_drift_kinetic_interpolate(xpic_ctx* ctx, int64_t n, const double* rn3, const double* r03, int gradB_field,
+  double* Ep3, double* Bp3, double* gradBp3)
+{ // DriftKineticEsirkepov::interpolate, drift_kinetic_implicit.cpp:11-31
+  const double* gradB;
+  XPIC_CALL(dk_check(ctx, n, gradB_field, &gradB));
+  XPIC_CHECK(rn3, "drift_kinetic_interpolate: rn3 is null");
+  XPIC_CHECK(r03, "drift_kinetic_interpolate: r03 is null");
+  XPIC_CHECK(Ep3, "drift_kinetic_interpolate: Ep3 is null");
+  XPIC_CHECK(Bp3, "drift_kinetic_interpolate: Bp3 is null");
+  XPIC_CHECK(gradBp3, "drift_kinetic_interpolate: gradBp3 is null");
+  if (n == 0) return 0;
+  return dk_interpolate(ctx, n, rn3, r03, gradB, Ep3, Bp3, gradBp3);
+}
+
+int xpic_drift_kinetic_push(xpic_ctx* ctx, int64_t n, const xpic_dk_params* params, int gradB_field, const double* p0_6,
+  double* pn_6, int* iterations)
+{ // DriftKineticPush::process, drift_kinetic_push.cpp:48-108
+  const double* gradB;
+  XPIC_CALL(dk_check(ctx, n, gradB_field, &gradB));
+  XPIC_CALL(dk_check_params(params));
+  XPIC_CHECK(p0_6, "drift_kinetic_push: p0_6 is null");
+  XPIC_CHECK(pn_6, "drift_kinetic_push: pn_6 is null");
+  XPIC_CHECK(iterations, "drift_kinetic_push: iterations is null");
+  if (n == 0) return 0;
+  return dk_push(ctx, n, *params, gradB, p0_6, pn_6, iterations);
+}
+
+int xpic_drift_kinetic_trace(xpic_ctx* ctx, int64_t n, const xpic_dk_params* params, int gradB_field, int64_t steps,
+  int64_t sample_every, double* state_6, double* samples, int64_t* iterations_total, int* iterations_max)
+{
+  const double* gradB;
+  XPIC_CALL(dk_check(ctx, n, gradB_field, &gradB));
+  XPIC_CALL(dk_check_params(params));
+  XPIC_CHECK(steps >= 0, "drift_kinetic_trace: steps is negative");
+  XPIC_CHECK(!samples || sample_every >= 1, "drift_kinetic_trace: sample_every must be >= 1 when samples are asked for");
+  XPIC_CHECK(state_6, "drift_kinetic_trace: state_6 is null");
+  XPIC_CHECK(iterations_total, "drift_kinetic_trace: iterations_total is null");
+  XPIC_CHECK(iterations_max, "drift_kinetic_trace: iterations_max is null");
+  if (n == 0) return 0;
+  return dk_trace(ctx, n, *params, gradB, steps, sample_every, state_6, samples, iterations_total, iterations_max);
+}
+
 int xpic_charge_collect(xpic_ctx* ctx) // ChargeConservation::initialize, charge_conservation.cpp:117-123
 {
   CTX_CHECK(ctx);
