@@ -71,7 +71,7 @@ const char* xpic_last_error(void);
 /* XPIC_VERSION, with XPIC_VERSION_EXPERIMENT_BIT set when any object of the library was built with -DXPIC_EXPERIMENT
  * (ablation switches and in-kernel timers of the kernels; some produce wrong physics by design): refuse such a library
  * for production runs. */
-#define XPIC_VERSION 5
+#define XPIC_VERSION 6
 #define XPIC_VERSION_EXPERIMENT_BIT 0x40000000
 int xpic_version(void);
 
@@ -399,6 +399,47 @@ int xpic_drift_kinetic_push(xpic_ctx* ctx, int64_t n, const xpic_dk_params* para
 #define XPIC_DK_LAUNCH_STEPS 64
 int xpic_drift_kinetic_trace(xpic_ctx* ctx, int64_t n, const xpic_dk_params* params, int gradB_field, int64_t steps,
   int64_t sample_every, double* state_6, double* samples, int64_t* iterations_total, int* iterations_max);
+
+/* ---- full-orbit pusher on the context's static XPIC_E / XPIC_B, batch form over n particles (host arrays).  A particle
+ * is a `Point` record: six doubles {x, y, z, px, py, pz} (src/interfaces/point.h:7-35).  The companion of the
+ * drift-kinetic calls above: the reference's grid tests (tests/drift_kinetic_push/drift_kinetic_grid_boris_ex1..4) run
+ * the two side by side on the same grid fields.  Positions are not folded into the box: the gathers wrap their node
+ * indices.  Single z-slab contexts only (nranks == 1, no self_ring).  n == 0 succeeds and touches nothing.
+ * Schemes 0..16 are the Chin ids of BorisPush as tests/boris_push/boris_push.h:20-228 composes them (process_<id>):
+ * update_r (src/algorithms/boris_push.cpp:19-22), a gather at the particle with Shape::setup(r) (radius 1.5, 2nd-order
+ * spline) and SimpleInterpolation's electric and magnetic products -- what basic::Particles::push gathers
+ * (src/impls/basic/particles.cpp:32-37) --, and update_vM / vB / vC1 / vC2 / vEB (boris_push.cpp:24-91).  update_v_impl
+ * normalises B_p: where |B_p| is 0 the reference divides by zero; here such a particle keeps its v in the magnetic ids.
+ * The LF ids are the 1B step: the half step back that starts a leap-frog run is the caller's.
+ * XPIC_FO_CN is CrankNicolsonPush::process (src/algorithms/crank_nicolson_push.cpp:31-71) from the initial guess
+ * pn = p0, with the gather of ImplicitEsirkepov::interpolate (src/algorithms/implicit_esirkepov.cpp:63-91). */
+enum xpic_fo_scheme {
+  XPIC_FO_M1A = 0, XPIC_FO_M1B = 1, XPIC_FO_MLF = 2, XPIC_FO_B1A = 3, XPIC_FO_B1B = 4, XPIC_FO_BLF = 5, XPIC_FO_C1A = 6,
+  XPIC_FO_C1B = 7, XPIC_FO_CLF = 8, XPIC_FO_M2A = 9, XPIC_FO_M2B = 10, XPIC_FO_C2A = 11, XPIC_FO_B2B = 12,
+  XPIC_FO_EB1A = 13, XPIC_FO_EB1B = 14, XPIC_FO_EBLF = 15, XPIC_FO_EB2B = 16, XPIC_FO_CN = 17, XPIC_FO_NSCHEMES = 18
+};
+typedef struct xpic_fo_params {
+  double qm, dt;
+  double atol, rtol; /* XPIC_FO_CN: CrankNicolsonPush::set_tolerances (reference default 1e-7, 1e-7) */
+  int32_t scheme;    /* enum xpic_fo_scheme */
+  int32_t maxit;     /* XPIC_FO_CN: 1 .. XPIC_FO_MAXIT (reference default 30); ignored by the other schemes */
+} xpic_fo_params;
+#define XPIC_FO_MAXIT 64
+#define XPIC_FO_LAUNCH_STEPS 64
+/* One step: process_<id> (tests/boris_push/boris_push.h:20-198) or CrankNicolsonPush::process
+ * (crank_nicolson_push.cpp:31-71).  iterations (XPIC_FO_CN: required; otherwise it may be NULL and is zeroed if given):
+ * the reference's get_iteration_number(), the index of the iteration whose residual met atol + rtol * r0, or maxit for a
+ * particle that ran out of iterations (the reference aborts there; here the caller decides). */
+int xpic_full_orbit_push(xpic_ctx* ctx, int64_t n, const xpic_fo_params* params, const double* p0_6, double* pn_6,
+  int* iterations);
+/* `steps` pushes in a row with the particles kept on the device, in launches of at most XPIC_FO_LAUNCH_STEPS steps (the
+ * time loops of tests/boris_push/boris_push_ex1.cpp:51-60 and tests/crank_nicolson_push/crank_nicolson_push_ex2.cpp:43-56):
+ * p_6 is read and overwritten with the result, bit for bit that of `steps` calls of xpic_full_orbit_push.  samples (or
+ * NULL): the state after every sample_every-th step (>= 1), samples[(k * n + q) * 6 ..] for k < steps / sample_every, so
+ * sample 0 is the state after step sample_every, as in xpic_drift_kinetic_trace.  iterations_sum[q] / iterations_max[q]
+ * (XPIC_FO_CN: required; otherwise optional and zeroed): sum and maximum of the particle's iteration counts. */
+int xpic_full_orbit_trace(xpic_ctx* ctx, int64_t n, const xpic_fo_params* params, int64_t steps, int64_t sample_every,
+  double* p_6, double* samples, int64_t* iterations_sum, int* iterations_max);
 
 /* ---- z-slab decomposition (DMDA da_processors_z = nranks; src/utils/world.cpp:36-38).  A context created with
  * nranks > 1 owns planes [rank*nz/nranks, (rank+1)*nz/nranks) and must be given a communicator before any

@@ -1,0 +1,300 @@
+"""The full-orbit pusher on the device (xpic_amd/csrc/full_orbit.hip) against the numpy restatement of the reference's
+algorithms in tests/full_orbit_ref.py (pinned by tests/test_full_orbit_ref.py): an 8 x 8 x 8 grid, d = 1, smooth
+periodic fields, 1001 particles (four workgroups with a ragged tail) spread over -1 .. 9 cells on every axis.  The
+tolerances are those of tests/test_gpu_drift_kinetic.py for the same kind of comparison: 1e-13 of the field maximum for
+a gather (here reached through one step), 1e-13 of the state's magnitude for one step."""
+import os
+
+import numpy as np
+import pytest
+
+import full_orbit_ref as R
+
+pytestmark = pytest.mark.gpu
+EPS = np.finfo(float).eps
+GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+
+
+@pytest.fixture(scope="module")
+def X():
+    import xpic_amd
+
+    return xpic_amd
+
+
+@pytest.fixture(scope="module")
+def fields():
+    return R.case_fields()
+
+
+def make_ctx(X, E, B, **kw):
+    g = X.Context("basic", R.N, R.D, 0.7, **kw)
+    g.set_field(X.E, E)
+    g.set_field(X.B, B)
+    return g
+
+
+@pytest.fixture(scope="module")
+def ctx(X, fields):
+    return make_ctx(X, *fields)
+
+
+@pytest.fixture(scope="module")
+def particles():
+    p = R.case_particles()
+    r = p[:, :3]
+    assert ((r < 0).any(axis=0) & (r > 8).any(axis=0)).all()  # beyond both faces on every axis: the seam is exercised
+    return p
+
+
+def _same(name, got, ref, rel=1e-13):
+    assert np.isfinite(got).all(), name
+    for cols, what in ((slice(0, 3), "r"), (slice(3, 6), "p")):
+        err, scale = np.abs(got[:, cols] - ref[:, cols]).max(), np.abs(ref[:, cols]).max()
+        print(name, what, "max |gpu - restatement| =", err, "scale", scale)
+        assert err <= rel * scale, (name, what)
+
+
+@pytest.mark.parametrize("sid", R.SCHEMES)
+def test_one_push_per_scheme(ctx, fields, particles, sid):
+    E, B = fields
+    got, its = ctx.full_orbit_push(particles, sid, R.QM, R.DT)
+    assert not its.any()
+    _same(sid, got, R.step(sid, E, B, R.D, particles, R.QM, R.DT))
+
+
+def test_gather_through_a_step(ctx, fields, particles):
+    """from rest, with qm = dt = 1, EB1A returns a v that is a fixed function of E_p and B_p alone (a = E_p, b = -B_p):
+    the gather itself, to 1e-13 of the field maximum"""
+    E, B = fields
+    p = particles.copy()
+    p[:, 3:] = 0.0
+    got, _ = ctx.full_orbit_push(p, "EB1A", 1.0, 1.0)
+    ref = R.step("EB1A", E, B, R.D, p, 1.0, 1.0)
+    err = np.abs(got[:, 3:] - ref[:, 3:]).max()
+    print("v after EB1A from rest: max |gpu - restatement| =", err)
+    assert err <= 1e-13 * max(np.abs(E).max(), np.abs(B).max())
+
+
+def test_zero_field_patch(X, fields, particles):
+    """a 4 x 4 x 4 block of B nodes set to 0 and 16 particles at its centre (within 0.4 cells of it: their footprints,
+    3 or 4 nodes an axis, stay inside the block), where B_p is exactly 0: the magnetic ids leave v unchanged there, and
+    nothing is NaN anywhere"""
+    E, B = fields
+    B = B.copy()
+    B[2:6, 2:6, 2:6, :] = 0.0
+    p = particles.copy()
+    rng = np.random.default_rng(7)
+    p[:16, :3] = 4.0 + (rng.random((16, 3)) * 2 - 1) * 0.4
+    p[0, :3] = 4.0
+    assert not R.gather(E, B, R.D, p[:16, :3])[1].any()
+    g = make_ctx(X, E, B)
+    for sid in R.MAGNETIC:
+        got, _ = g.full_orbit_push(p, sid, R.QM, R.DT)
+        assert np.isfinite(got).all(), sid
+        assert np.array_equal(got[:16, 3:], p[:16, 3:]), sid
+        _same(sid, got, R.step(sid, E, B, R.D, p, R.QM, R.DT))
+    for sid in R.SCHEMES[13:] + ["CN"]:
+        got, _ = g.full_orbit_push(p, sid, R.QM, R.DT)
+        assert np.isfinite(got).all(), sid
+
+
+@pytest.mark.parametrize("k", [1, 2, 5])
+def test_crank_nicolson_with_pinned_iterations(ctx, fields, particles, k):
+    """atol = rtol = 0: no residual is < 0, so both sides make exactly k updates and nothing depends on a data-dependent
+    exit"""
+    E, B = fields
+    ref, its_ref = R.cn_step(E, B, R.D, particles, R.QM, R.DT, atol=0.0, rtol=0.0, maxit=k)
+    got, its = ctx.full_orbit_push(particles, "CN", R.QM, R.DT, atol=0.0, rtol=0.0, maxit=k)
+    assert (its_ref == k).all() and (its == k).all()
+    _same("CN maxit=%d" % k, got, ref)
+
+
+def test_crank_nicolson_default_tolerances(ctx, fields, particles):
+    """counts within one of the restatement's; the exit test of the restatement, evaluated at the device's state, holds
+    (cn_residual: rn < atol + rtol r0 with the fields the first iteration sees)"""
+    E, B = fields
+    ref, its_ref = R.cn_step(E, B, R.D, particles, R.QM, R.DT)
+    got, its = ctx.full_orbit_push(particles, "CN", R.QM, R.DT)
+    assert its_ref.max() < R.CN_MAXIT and its.max() < R.CN_MAXIT
+    assert np.abs(its.astype(int) - its_ref).max() <= 1
+    assert not its_ref.any()  # cn_residual's premise: the restatement leaves in its first iteration
+    rn, bound = R.cn_residual(E, B, R.D, particles, got, R.QM, R.DT)
+    print("residual at the device's state: max", rn.max(), "smallest bound", bound.min())
+    assert (rn < bound).all()
+    _same("CN", got, ref)
+
+
+@pytest.mark.parametrize("sid", ["EB2B", "C2A", "CN"])
+def test_trace_equals_repeated_pushes(X, ctx, particles, sid):
+    steps = X.FO_LAUNCH_STEPS + 6  # 70: two launches
+    states, counts = [], []
+    p = particles
+    for _ in range(steps):
+        p, its = ctx.full_orbit_push(p, sid, R.QM, R.DT)
+        states.append(p)
+        counts.append(its.astype(np.int64))
+    out, samples, tot, mx = ctx.full_orbit_trace(particles, steps, sid, R.QM, R.DT, sample_every=7)
+    assert np.array_equal(out, states[-1])
+    assert samples.shape == (10, R.NPART, 6)
+    for k in range(10):
+        assert np.array_equal(samples[k], states[7 * (k + 1) - 1]), k
+    assert np.array_equal(tot, np.sum(counts, axis=0)) and np.array_equal(mx, np.max(counts, axis=0))
+    # one sample, taken in the second launch
+    out, samples, _, _ = ctx.full_orbit_trace(particles, steps, sid, R.QM, R.DT, sample_every=X.FO_LAUNCH_STEPS + 1)
+    assert np.array_equal(out, states[-1])
+    assert samples.shape[0] == 1 and np.array_equal(samples[0], states[X.FO_LAUNCH_STEPS])
+    out, samples, _, _ = ctx.full_orbit_trace(particles, steps, sid, R.QM, R.DT)
+    assert samples is None and np.array_equal(out, states[-1])
+    out, _, _, _ = ctx.full_orbit_trace(particles, 0, sid, R.QM, R.DT)
+    assert np.array_equal(out, particles)
+
+
+@pytest.mark.parametrize("ex,sid", [(R.EX4, "EB2B"), (R.EX1, "B2B")])
+def test_uniform_fields_against_the_golden_tables(X, oracle, ex, sid):
+    """rows 1 .. 5 of the reference's table (ex4 / EB2B: 160 steps, ex1 / B2B: 2715 steps) through full_orbit_trace, for
+    the example's particle and 255 copies of it shifted by whole cells (up to 16 either way on every axis).
+
+    The table: the CPU test's bound (tests/test_full_orbit_ref.py), half a unit of the table's last digit plus the floor
+    measured there.  The copies: in a uniform field a shift changes only how the positions round.  Each of the two
+    update_r of a step rounds at the position's magnitude, half an ulp of at most rmax each, and the gathered constants
+    differ by rounding of the weights' sum, a few ulp of the field that act on v like one more rounding per step: 4 ulp
+    of rmax per step in all, rmax the largest coordinate met."""
+    rows = 6
+    steps = (rows - 1) * ex["every"]
+    g = make_ctx(X, *R.uniform_fields(ex["E0"], ex["B0"]))
+    rng = np.random.default_rng(3)
+    shift = rng.integers(-16, 17, (256, 3)).astype(np.float64)
+    shift[0] = 0.0
+    p = np.zeros((256, 6))
+    p[:, :3] = np.array(ex["r0"]) + shift
+    p[:, 3:] = ex["v0"]
+    out, samples, _, _ = g.full_orbit_trace(p, steps, sid, ex["qm"], ex["dt"], sample_every=ex["every"])
+    assert samples.shape == (rows - 1, 256, 6) and np.array_equal(samples[-1], out)
+    gold = R.read_table(GOLD, ex, sid, rows)
+    mine = R.run_example(ex, sid, rows)
+    _, floor = R.table_floor(oracle, ex, sid, mine)
+    err = np.abs(samples[:, 0, :] - gold[1:, 1:])
+    print(sid, "max |gpu - table| =", err.max(), "floor", floor)
+    assert (err <= R.table_bound(gold[1:, 1:], floor)).all()
+    back = samples.copy()
+    back[:, :, :3] -= shift
+    spread = np.abs(back - back[:, :1, :]).max()
+    rmax = np.abs(samples[:, :, :3]).max()
+    print("copies: spread", spread, "bound", 4 * EPS * rmax * steps)
+    assert spread <= 4 * EPS * rmax * steps
+
+
+def test_argument_checks(X, ctx, particles):
+    import ctypes as C
+
+    p0 = particles
+    # n = 0: success, nothing touched
+    pn, its = ctx.full_orbit_push(np.zeros((0, 6)), "EB2B", R.QM, R.DT)
+    assert pn.shape == (0, 6) and its.shape == (0,)
+    out, samples, tot, mx = ctx.full_orbit_trace(np.zeros((0, 6)), 5, "CN", R.QM, R.DT, sample_every=2)
+    assert out.shape == (0, 6) and samples.shape == (2, 0, 6)
+    # n = 1 is the first particle of the batch
+    all_, _ = ctx.full_orbit_push(p0, "EB2B", R.QM, R.DT)
+    one, _ = ctx.full_orbit_push(p0[:1], "EB2B", R.QM, R.DT)
+    assert np.array_equal(one[0], all_[0])
+    # bad arguments name themselves
+    for scheme in (-1, 18, 1000):
+        with pytest.raises(X.XpicError, match="scheme"):
+            ctx.full_orbit_push(p0, scheme, R.QM, R.DT)
+        with pytest.raises(X.XpicError, match="scheme"):
+            ctx.full_orbit_trace(p0, 2, scheme, R.QM, R.DT)
+    for maxit in (0, 65, -3):
+        with pytest.raises(X.XpicError, match="maxit"):
+            ctx.full_orbit_push(p0, "CN", R.QM, R.DT, maxit=maxit)
+        with pytest.raises(X.XpicError, match="maxit"):
+            ctx.full_orbit_trace(p0, 2, "CN", R.QM, R.DT, maxit=maxit)
+    ctx.full_orbit_push(p0[:4], "CN", R.QM, R.DT, maxit=64)
+    with pytest.raises(X.XpicError, match="steps"):
+        ctx.full_orbit_trace(p0, -1, "EB2B", R.QM, R.DT)
+    L_, dp, n1 = ctx.L, C.POINTER(C.c_double), C.c_int64(1)
+    buf = np.zeros(6)
+    ptr = buf.ctypes.data_as(dp)
+    it1, tot1 = (C.c_int * 1)(), (C.c_int64 * 1)()
+    P = X.FoParams(R.QM, R.DT, 1e-7, 1e-7, X.FO_SCHEMES["EB2B"], 30)
+    PC = X.FoParams(R.QM, R.DT, 1e-7, 1e-7, X.FO_SCHEMES["CN"], 30)
+    one, big = C.c_int64(1), C.c_int64(1 << 62)
+    calls = [
+        (lambda: L_.xpic_full_orbit_push(ctx.h, n1, None, ptr, ptr, it1), "params"),
+        (lambda: L_.xpic_full_orbit_push(ctx.h, n1, C.byref(P), None, ptr, it1), "p0_6"),
+        (lambda: L_.xpic_full_orbit_push(ctx.h, n1, C.byref(P), ptr, None, it1), "pn_6"),
+        (lambda: L_.xpic_full_orbit_push(ctx.h, n1, C.byref(PC), ptr, ptr, None), "iterations"),
+        (lambda: L_.xpic_full_orbit_push(ctx.h, C.c_int64(-1), C.byref(P), ptr, ptr, it1), "negative"),
+        (lambda: L_.xpic_full_orbit_trace(ctx.h, n1, None, one, one, ptr, None, tot1, it1), "params"),
+        (lambda: L_.xpic_full_orbit_trace(ctx.h, n1, C.byref(P), one, one, None, None, tot1, it1), "p_6"),
+        (lambda: L_.xpic_full_orbit_trace(ctx.h, n1, C.byref(P), one, C.c_int64(0), ptr, ptr, tot1, it1), "sample_every"),
+        (lambda: L_.xpic_full_orbit_trace(ctx.h, n1, C.byref(PC), one, one, ptr, None, None, it1), "iterations_sum"),
+        (lambda: L_.xpic_full_orbit_trace(ctx.h, n1, C.byref(PC), one, one, ptr, None, tot1, None), "iterations_max"),
+        # a sample buffer whose size overflows 64 bits is refused before anything is allocated
+        (lambda: L_.xpic_full_orbit_trace(ctx.h, C.c_int64(1 << 30), C.byref(P), big, one, ptr, ptr, tot1, it1), "sample buffer"),
+    ]
+    for call, word in calls:
+        assert call() != 0
+        assert word in L_.xpic_last_error().decode(), word
+    assert L_.xpic_full_orbit_push(None, n1, C.byref(P), ptr, ptr, it1) != 0
+    # a Chin id takes no iteration counters
+    assert L_.xpic_full_orbit_push(ctx.h, n1, C.byref(P), ptr, ptr, None) == 0
+    assert L_.xpic_full_orbit_trace(ctx.h, n1, C.byref(P), one, one, ptr, None, None, None) == 0
+    # contexts with ghost planes are refused with a message
+    ring = X.Context("basic", R.N, R.D, 0.7, self_ring=True)
+    with pytest.raises(X.XpicError, match="self_ring"):
+        ring.full_orbit_push(p0[:4], "EB2B", R.QM, R.DT)
+    with pytest.raises(X.XpicError, match="self_ring"):
+        ring.full_orbit_trace(p0[:4], 2, "CN", R.QM, R.DT)
+    two = X.Context("basic", (8, 8, 12), (0.5, 0.5, 0.5), 0.7, rank=0, nranks=2)
+    with pytest.raises(X.XpicError, match="z-slab"):
+        two.full_orbit_push(p0[:4], "EB2B", R.QM, R.DT)
+
+
+def _pair(X, orbit_centre):
+    """B = (0, 0, 1), E = (0, 0.01, 0), qm = -1, 200 steps of dt = 0.1: 64 EB2B orbits beside the drift-kinetic trace from
+    guiding_centre(..., orbit_centre=orbit_centre) of the same initial points -> the largest and smallest distance, in
+    Larmor radii rho = |v_perp| / (|qm| |B|), between the two positions averaged over a gyro-period (63 steps:
+    2 pi / (|qm| |B| dt) = 62.8).  rho >= 0.3 by the choice of v_perp.  The velocities along B are >= 0: PointByField
+    keeps |p_parallel| only."""
+    E0, B0 = np.array([0.0, 0.01, 0.0]), np.array([0.0, 0.0, 1.0])
+    g = make_ctx(X, *R.uniform_fields(E0, B0))
+    qm, mp, dt, steps, n = -1.0, 1.0, 0.1, 200, 64
+    rng = np.random.default_rng(9)
+    ang = rng.random(n) * 2 * np.pi
+    vperp = 0.3 + 0.7 * rng.random(n)
+    p = np.column_stack([rng.random((n, 3)) * 8.0, vperp * np.cos(ang), vperp * np.sin(ang), np.abs(rng.normal(0, 0.3, n))])
+    rho = vperp / (abs(qm) * np.sqrt(B0.dot(B0)))
+    start = X.guiding_centre(p, B0, mp, qm, orbit_centre=orbit_centre)
+    _, fo, _, _ = g.full_orbit_trace(p, steps, "EB2B", qm, dt, sample_every=1)
+    _, gc, _, mx = g.drift_kinetic_trace(start, steps, qm, mp, dt, sample_every=1)
+    assert mx.max() < 30
+    w = 63
+    csum = lambda a: np.cumsum(np.concatenate([np.zeros((1,) + a.shape[1:]), a]), axis=0)  # noqa: E731
+    avg = lambda a: (csum(a)[w:] - csum(a)[:-w]) / w  # noqa: E731
+    dist = np.sqrt(((avg(fo[:, :, :3]) - avg(gc[:, :, :3])) ** 2).sum(axis=2)) / rho  # [window][particle]
+    print("orbit_centre", orbit_centre, "distance / Larmor radius: largest", dist.max(), "smallest", dist.min())
+    return dist.max(), dist.min()
+
+
+def test_full_orbit_follows_the_guiding_centre(X):
+    """The gyro-averaged full-orbit position stays within one Larmor radius of the drift-kinetic trace started from
+    guiding_centre(..., orbit_centre=True) of the same points, because an orbit never leaves its circle.  That start, the
+    centre of the orbit's circle, moves with E x B / B^2 and the parallel velocity exactly as the orbit's centre does,
+    so the two averages differ only by the remainder of a period that is not a whole number of steps (0.8 steps of 63)
+    and by the orbit centre's |E x B| / (B^2 omega) = 0.01 shift in the drift frame: a tenth of a radius covers both
+    with rho >= 0.3, which the second assertion holds the pair to."""
+    largest, _ = _pair(X, True)
+    assert largest <= 1.0
+    assert largest <= 0.1
+
+
+def test_the_reference_constructor_starts_two_radii_from_the_orbit(X):
+    """guiding_centre's default restates PointByField's constructor (src/interfaces/point.h:52-58), r - p x b / (qm |B|),
+    the mirror image about the particle of the centre of its circle under the force qm v x B of BorisPush.  In uniform
+    fields the drift-kinetic pusher moves both starts alike, so that trace stays exactly two radii from the other one,
+    and by the tenth of a radius of the test above between 1.9 and 2.1 radii from the gyro-averaged orbit, for every
+    particle and window.  One radius does not hold for it; the reference's grid tests compare z, p_parallel, mu and energy
+    of the pair and never the perpendicular position."""
+    largest, smallest = _pair(X, False)
+    assert 1.9 <= smallest and largest <= 2.1

@@ -31,7 +31,7 @@ SYMBOLS = [
     "xpic_energy", "xpic_momentum", "xpic_charge_density", "xpic_moment_density", "xpic_moment", "xpic_velocity_distribution", "xpic_remove_particles", "xpic_fields_damping",
     "xpic_inject_particles", "xpic_set_coils_field", "xpic_cell_traversal", "xpic_implicit_esirkepov_interpolate",
     "xpic_implicit_esirkepov_decompose", "xpic_drift_kinetic_interpolate", "xpic_drift_kinetic_push",
-    "xpic_drift_kinetic_trace", "xpic_charge_collect", "xpic_charge_columns", "xpic_comm_rccl_unique_id", "xpic_comm_init_rccl", "xpic_comm_init_callbacks", "xpic_comm_size", "xpic_comm_peer_export", "xpic_comm_peer_import",
+    "xpic_drift_kinetic_trace", "xpic_full_orbit_push", "xpic_full_orbit_trace", "xpic_charge_collect", "xpic_charge_columns", "xpic_comm_rccl_unique_id", "xpic_comm_init_rccl", "xpic_comm_init_callbacks", "xpic_comm_size", "xpic_comm_peer_export", "xpic_comm_peer_import",
     "xpic_profile_enable", "xpic_profile_reset", "xpic_profile_get", "xpic_probe_copy_bandwidth",
 ]
 
@@ -116,9 +116,28 @@ class DkParams(C.Structure):  # include/xpic_hip.h: xpic_dk_params
 DK_LAUNCH_STEPS = 64  # include/xpic_hip.h: XPIC_DK_LAUNCH_STEPS
 
 
-def guiding_centre(points6, B3, mp, qm):
+class FoParams(C.Structure):  # include/xpic_hip.h: xpic_fo_params
+    _fields_ = [("qm", C.c_double), ("dt", C.c_double), ("atol", C.c_double), ("rtol", C.c_double), ("scheme", C.c_int32),
+                ("maxit", C.c_int32)]
+
+
+# include/xpic_hip.h: enum xpic_fo_scheme -- the 17 Chin ids of tests/boris_push/boris_push.h, then Crank-Nicolson
+FO_SCHEMES = {name: i for i, name in enumerate(
+    ["M1A", "M1B", "MLF", "B1A", "B1B", "BLF", "C1A", "C1B", "CLF", "M2A", "M2B", "C2A", "B2B", "EB1A", "EB1B", "EBLF",
+     "EB2B", "CN"])}
+FO_LAUNCH_STEPS = 64  # include/xpic_hip.h: XPIC_FO_LAUNCH_STEPS
+FO_MAXIT = 64         # include/xpic_hip.h: XPIC_FO_MAXIT
+
+
+def guiding_centre(points6, B3, mp, qm, *, orbit_centre=False):
     """PointByField(point, Bp, mp, qm) (src/interfaces/point.h:52-58) for records {r, p} and the field B3 at each of them
-    -> records {guiding centre xyz, p_parallel, p_perp, mu_p}, the particles of Context.drift_kinetic_push"""
+    -> records {guiding centre xyz, p_parallel, p_perp, mu_p}, the particles of Context.drift_kinetic_push.
+
+    That constructor places the centre at r - p x b / (qm |B|).  Under the force qm v x B of BorisPush (and of
+    Context.full_orbit_*) a particle circles r + p x b / (qm |B|), the point on the other side of it, two Larmor radii
+    away; the reference's tests compare only z, p_parallel, mu and energy between the two pushers and do not see it.
+    The default keeps the constructor as it is.  orbit_centre=True returns the centre of the particle's own circle, the
+    start from which a drift-kinetic trace can be laid beside a full orbit of the same particle."""
     pts = np.asarray(points6, dtype=np.float64).reshape(-1, 6)
     Bp = np.broadcast_to(np.asarray(B3, dtype=np.float64), (pts.shape[0], 3))
     r, p = pts[:, :3], pts[:, 3:]
@@ -126,7 +145,8 @@ def guiding_centre(points6, B3, mp, qm):
     b = np.divide(Bp, lB, out=np.zeros_like(p), where=lB > 0)  # Vector3::normalized
     par = (p * Bp).sum(axis=1)[:, None] * Bp / (Bp * Bp).sum(axis=1)[:, None]  # Vector3::parallel_to
     out = np.empty((pts.shape[0], 6))
-    out[:, :3] = r - np.cross(p, b) / (qm * lB)
+    rho = np.cross(p, b) / (qm * lB)
+    out[:, :3] = r + rho if orbit_centre else r - rho
     out[:, 3] = np.sqrt((par * par).sum(axis=1))
     out[:, 4] = np.sqrt(((p - par) ** 2).sum(axis=1))
     out[:, 5] = mp * out[:, 4] * out[:, 4] / (2.0 * lB[:, 0])
@@ -589,6 +609,37 @@ class Context:
                                                  C.c_int64(int(steps)), C.c_int64(int(sample_every)), _dp(state),
                                                  _dp(samples) if sample_every else None, tot.ctypes.data_as(C.POINTER(C.c_int64)),
                                                  mx.ctypes.data_as(C.POINTER(C.c_int))))
+        return state, samples, tot, mx
+
+    # ---- full-orbit pusher (include/xpic_hip.h: xpic_full_orbit_*); particles are Point records {x, y, z, px, py, pz},
+    # scheme a key of FO_SCHEMES (a Chin id or "CN") or its number
+    @staticmethod
+    def _fo_params(scheme, qm, dt, atol, rtol, maxit):
+        return FoParams(float(qm), float(dt), float(atol), float(rtol), int(FO_SCHEMES.get(scheme, scheme)), int(maxit))
+
+    def full_orbit_push(self, p0, scheme, qm, dt, atol=1e-7, rtol=1e-7, maxit=30):
+        """one step of every particle -> (pn, iterations): process_<id> of tests/boris_push/boris_push.h (iterations 0), or
+        CrankNicolsonPush::process for "CN" (iterations == maxit: not converged)"""
+        p0 = np.ascontiguousarray(p0, dtype=np.float64).reshape(-1, 6)
+        pn = np.zeros_like(p0)
+        its = np.zeros(p0.shape[0], dtype=np.int32)
+        P = self._fo_params(scheme, qm, dt, atol, rtol, maxit)
+        self._ck(self.L.xpic_full_orbit_push(self.h, C.c_int64(p0.shape[0]), C.byref(P), _dp(p0), _dp(pn),
+                                             its.ctypes.data_as(C.POINTER(C.c_int))))
+        return pn, its
+
+    def full_orbit_trace(self, state, steps, scheme, qm, dt, sample_every=0, atol=1e-7, rtol=1e-7, maxit=30):
+        """`steps` pushes with the particles kept on the device -> (state, samples [steps // sample_every][n][6] or None,
+        iterations_sum, iterations_max); sample k is the state after step (k + 1) * sample_every"""
+        state = np.array(state, dtype=np.float64).reshape(-1, 6)  # a copy: the call works in place
+        n = state.shape[0]
+        nsamp = max(int(steps), 0) // int(sample_every) if sample_every else 0
+        samples = np.zeros((nsamp, n, 6)) if sample_every else None
+        tot, mx = np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int32)
+        P = self._fo_params(scheme, qm, dt, atol, rtol, maxit)
+        self._ck(self.L.xpic_full_orbit_trace(self.h, C.c_int64(n), C.byref(P), C.c_int64(int(steps)),
+                                              C.c_int64(int(sample_every)), _dp(state), _dp(samples) if sample_every else None,
+                                              tot.ctypes.data_as(C.POINTER(C.c_int64)), mx.ctypes.data_as(C.POINTER(C.c_int))))
         return state, samples, tot, mx
 
     def charge_collect(self):

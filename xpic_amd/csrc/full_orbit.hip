@@ -1,0 +1,240 @@
+// full_orbit.hip -- full orbits of a batch of particles on the context's static E and B, the companion of
+// drift_kinetic.hip (the reference's grid tests run the two side by side):
+//   process_<id> for the 17 Chin ids     tests/boris_push/boris_push.h:20-198   (BorisPush, src/algorithms/boris_push.cpp)
+//   CrankNicolsonPush::process           src/algorithms/crank_nicolson_push.cpp:31-71
+// with the gathers of basic::Particles::push (src/impls/basic/particles.cpp:32-37) and ImplicitEsirkepov::interpolate
+// (src/algorithms/implicit_esirkepov.cpp:63-91).  One lane per particle, fp64, no cross-lane operation, no atomics, no
+// deposition: a lane reads the field vectors and writes its own six state slots, its own sample rows and its own
+// iteration counters.  The state {x, y, z, px, py, pz} lives in structure-of-arrays device buffers (s[k * n + q]).
+// Positions are not folded into the box: the gathers wrap their node indices (ie_node).  Single z-slab contexts only
+// (G == 0: every index wraps, so no position, however far out, reads outside a field vector).
+// Every loop is bounded by a constant or by an argument the entry points have range-checked: at most 4 nodes per axis,
+// maxit <= XPIC_FO_MAXIT iterations, at most XPIC_FO_LAUNCH_STEPS steps per launch.
+#include <algorithm>
+#include <cmath>
+#include <vector>
+
+#include "common.h"
+#include "device_common.h"
+#include "ie_shape.h"
+
+// contracted per source expression only (not across statements), so k_fo_push and k_fo_trace, which inline the same
+// fo_step / fo_cn_process, round identically whatever surrounds the call
+#pragma clang fp contract(on)
+
+#include "full_orbit_step.h"
+
+namespace xpic {
+
+namespace {
+
+constexpr int kBlock = 256;
+constexpr int kLaunchSteps = XPIC_FO_LAUNCH_STEPS;
+
+__device__ inline void fo_load(const double* __restrict__ s, long n, long q, FOPoint& p)
+{
+  p.r[0] = s[q]; p.r[1] = s[n + q]; p.r[2] = s[2 * n + q];
+  p.p[0] = s[3 * n + q]; p.p[1] = s[4 * n + q]; p.p[2] = s[5 * n + q];
+}
+__device__ inline void fo_store(double* __restrict__ s, long n, long q, const FOPoint& p)
+{
+  s[q] = p.r[0]; s[n + q] = p.r[1]; s[2 * n + q] = p.r[2];
+  s[3 * n + q] = p.p[0]; s[4 * n + q] = p.p[1]; s[5 * n + q] = p.p[2];
+}
+
+// one step of P.scheme; CN: CrankNicolsonPush::process from the guess pn = p0, -> its iteration number
+template <bool CN>
+__device__ inline int fo_one(const GridDev& g, const double* __restrict__ E, const double* __restrict__ B,
+  const xpic_fo_params& P, FOPoint& pn)
+{
+  if (CN) {
+    const FOPoint p0 = pn;
+    return fo_cn_process(g, E, B, P.qm, P.dt, P.atol, P.rtol, P.maxit, pn, p0);
+  }
+  fo_step(P.scheme, g, E, B, P.qm, P.dt, pn);
+  return 0;
+}
+
+// iterations: written by the CN instance only
+template <bool CN>
+__global__ void __launch_bounds__(kBlock) k_fo_push(GridDev g, const double* __restrict__ E, const double* __restrict__ B,
+  xpic_fo_params P, long n, const double* __restrict__ s0, double* __restrict__ sn, int* __restrict__ iterations)
+{
+  const long q = (long)blockIdx.x * kBlock + threadIdx.x;
+  if (q >= n) return;
+  FOPoint pn;
+  fo_load(s0, n, q, pn);
+  const int it = fo_one<CN>(g, E, B, P, pn);
+  if (CN) iterations[q] = it;
+  fo_store(sn, n, q, pn);
+}
+
+// steps first + 1 .. first + nsteps of a trace, in place; nsteps <= kLaunchSteps.  Step k (counted from 1) is sampled
+// when sample_every divides it: sample k / sample_every - 1 of samples[sample][6][n], < nsamp by construction and
+// checked again here.
+template <bool CN>
+__global__ void __launch_bounds__(kBlock) k_fo_trace(GridDev g, const double* __restrict__ E, const double* __restrict__ B,
+  xpic_fo_params P, long n, double* __restrict__ s, long first, int nsteps, long sample_every, long nsamp,
+  double* __restrict__ samples, long long* __restrict__ it_sum, int* __restrict__ it_max)
+{
+  const long q = (long)blockIdx.x * kBlock + threadIdx.x;
+  if (q >= n) return;
+  FOPoint pn;
+  fo_load(s, n, q, pn);
+  long long total = CN ? it_sum[q] : 0;
+  int most = CN ? it_max[q] : 0;
+  const int ns = nsteps < kLaunchSteps ? nsteps : kLaunchSteps;
+  for (int k = 1; k <= ns; ++k) {
+    const int it = fo_one<CN>(g, E, B, P, pn);
+    total += it;
+    most = it > most ? it : most;
+    const long step = first + k;
+    if (samples && step % sample_every == 0) {
+      const long row = step / sample_every - 1;
+      if (row < nsamp) fo_store(samples + row * 6 * n, n, q, pn);
+    }
+  }
+  fo_store(s, n, q, pn);
+  if (CN) { it_sum[q] = total; it_max[q] = most; }
+}
+
+struct DevBuf { // device scratch of one call, freed on scope exit
+  void* p = nullptr;
+  ~DevBuf() { if (p) (void)hipFree(p); }
+};
+
+inline dim3 fo_grid(int64_t n) { return dim3((unsigned)((n + kBlock - 1) / kBlock)); }
+
+// [n][6] host records -> [6][n], and back
+void to_soa(const double* aos, int64_t n, std::vector<double>& soa)
+{
+  soa.resize((size_t)6 * n);
+  for (int64_t q = 0; q < n; ++q)
+    for (int k = 0; k < 6; ++k) soa[(size_t)k * n + q] = aos[6 * q + k];
+}
+void to_aos(const double* soa, int64_t n, double* aos)
+{
+  for (int64_t q = 0; q < n; ++q)
+    for (int k = 0; k < 6; ++k) aos[6 * q + k] = soa[(size_t)k * n + q];
+}
+
+// the checks the two calls share
+int fo_check(xpic_ctx* ctx, int64_t n, const xpic_fo_params* P)
+{
+  XPIC_CHECK(ctx != nullptr, "null context");
+  XPIC_CHECK(n >= 0, "full_orbit: n is negative");
+  XPIC_CHECK(n <= ((int64_t)1 << 36), "full_orbit: n is larger than 2^36");
+  XPIC_CHECK(ctx->geom.nranks == 1 && ctx->g.G == 0,
+    "full_orbit: a context of several z-slabs (or a self_ring one) is not supported: the gathers wrap z in the kernel");
+  XPIC_CHECK(P, "full_orbit: params is null");
+  XPIC_CHECK(P->scheme >= 0 && P->scheme < XPIC_FO_NSCHEMES, "full_orbit: unknown scheme id");
+  if (P->scheme == XPIC_FO_CN)
+    XPIC_CHECK(P->maxit >= 1 && P->maxit <= XPIC_FO_MAXIT, "full_orbit: maxit must be within 1 .. 64");
+  XPIC_CHECK(ctx->field[XPIC_E] && ctx->field[XPIC_B], "full_orbit: the context has no E or B");
+  return 0;
+}
+
+}  // namespace
+
+}  // namespace xpic
+
+using namespace xpic;
+
+extern "C" {
+
+int xpic_full_orbit_push(xpic_ctx* ctx, int64_t n, const xpic_fo_params* params, const double* p0_6, double* pn_6,
+  int* iterations)
+{ // process_<id>, tests/boris_push/boris_push.h:20-198; CrankNicolsonPush::process, crank_nicolson_push.cpp:31-71
+  XPIC_CALL(fo_check(ctx, n, params));
+  const bool cn = params->scheme == XPIC_FO_CN;
+  XPIC_CHECK(p0_6, "full_orbit_push: p0_6 is null");
+  XPIC_CHECK(pn_6, "full_orbit_push: pn_6 is null");
+  XPIC_CHECK(iterations || !cn, "full_orbit_push: iterations is null");
+  if (n == 0) return 0;
+  std::vector<double> h;
+  to_soa(p0_6, n, h);
+  DevBuf s0, sn, it;
+  XPIC_HIP(hipMalloc(&s0.p, 48 * n)); XPIC_HIP(hipMalloc(&sn.p, 48 * n));
+  if (cn) XPIC_HIP(hipMalloc(&it.p, 4 * n));
+  XPIC_HIP(hipMemcpyAsync(s0.p, h.data(), 48 * n, hipMemcpyHostToDevice, ctx->stream));
+  {
+    Timed t(ctx, "fo_push");
+    if (cn)
+      hipLaunchKernelGGL(k_fo_push<true>, fo_grid(n), dim3(kBlock), 0, ctx->stream, ctx->g, ctx->field[XPIC_E],
+        ctx->field[XPIC_B], *params, (long)n, (const double*)s0.p, (double*)sn.p, (int*)it.p);
+    else
+      hipLaunchKernelGGL(k_fo_push<false>, fo_grid(n), dim3(kBlock), 0, ctx->stream, ctx->g, ctx->field[XPIC_E],
+        ctx->field[XPIC_B], *params, (long)n, (const double*)s0.p, (double*)sn.p, (int*)nullptr);
+    XPIC_HIP(hipGetLastError());
+  }
+  XPIC_HIP(hipMemcpyAsync(h.data(), sn.p, 48 * n, hipMemcpyDeviceToHost, ctx->stream));
+  if (cn) XPIC_HIP(hipMemcpyAsync(iterations, it.p, 4 * n, hipMemcpyDeviceToHost, ctx->stream));
+  XPIC_HIP(hipStreamSynchronize(ctx->stream));
+  if (!cn && iterations) std::fill(iterations, iterations + n, 0);
+  to_aos(h.data(), n, pn_6);
+  return 0;
+}
+
+int xpic_full_orbit_trace(xpic_ctx* ctx, int64_t n, const xpic_fo_params* params, int64_t steps, int64_t sample_every,
+  double* p_6, double* samples, int64_t* iterations_sum, int* iterations_max)
+{ // the time loops of boris_push_ex1.cpp:51-60 and crank_nicolson_push_ex2.cpp:43-56
+  XPIC_CALL(fo_check(ctx, n, params));
+  const bool cn = params->scheme == XPIC_FO_CN;
+  XPIC_CHECK(steps >= 0, "full_orbit_trace: steps is negative");
+  XPIC_CHECK(!samples || sample_every >= 1, "full_orbit_trace: sample_every must be >= 1 when samples are asked for");
+  XPIC_CHECK(p_6, "full_orbit_trace: p_6 is null");
+  XPIC_CHECK(iterations_sum || !cn, "full_orbit_trace: iterations_sum is null");
+  XPIC_CHECK(iterations_max || !cn, "full_orbit_trace: iterations_max is null");
+  // the sample buffer in 64-bit: 48 n bytes a sample; a size that does not fit is refused
+  const int64_t nsamp = samples ? steps / sample_every : 0;
+  int64_t row_bytes = 0, sample_bytes = 0;
+  XPIC_CHECK(!__builtin_mul_overflow((int64_t)48, n, &row_bytes) && !__builtin_mul_overflow(row_bytes, nsamp, &sample_bytes) &&
+      sample_bytes <= ((int64_t)1 << 46),
+    "full_orbit_trace: the sample buffer (48 n steps / sample_every bytes) is too large");
+  if (n == 0) return 0;
+  std::vector<double> h;
+  to_soa(p_6, n, h);
+  DevBuf s, sm, tot, mx;
+  XPIC_HIP(hipMalloc(&s.p, 48 * n));
+  if (cn) {
+    XPIC_HIP(hipMalloc(&tot.p, 8 * n)); XPIC_HIP(hipMalloc(&mx.p, 4 * n));
+    XPIC_HIP(hipMemsetAsync(tot.p, 0, 8 * n, ctx->stream));
+    XPIC_HIP(hipMemsetAsync(mx.p, 0, 4 * n, ctx->stream));
+  }
+  if (nsamp > 0) XPIC_HIP(hipMalloc(&sm.p, (size_t)sample_bytes));
+  XPIC_HIP(hipMemcpyAsync(s.p, h.data(), 48 * n, hipMemcpyHostToDevice, ctx->stream));
+  // one launch covers at most kLaunchSteps steps, so no launch runs for seconds however long the trace
+  for (int64_t first = 0; first < steps; first += kLaunchSteps) {
+    const int ns = (int)std::min<int64_t>(kLaunchSteps, steps - first);
+    Timed t(ctx, "fo_trace");
+    if (cn)
+      hipLaunchKernelGGL(k_fo_trace<true>, fo_grid(n), dim3(kBlock), 0, ctx->stream, ctx->g, ctx->field[XPIC_E],
+        ctx->field[XPIC_B], *params, (long)n, (double*)s.p, (long)first, ns, (long)sample_every, (long)nsamp, (double*)sm.p,
+        (long long*)tot.p, (int*)mx.p);
+    else
+      hipLaunchKernelGGL(k_fo_trace<false>, fo_grid(n), dim3(kBlock), 0, ctx->stream, ctx->g, ctx->field[XPIC_E],
+        ctx->field[XPIC_B], *params, (long)n, (double*)s.p, (long)first, ns, (long)sample_every, (long)nsamp, (double*)sm.p,
+        (long long*)nullptr, (int*)nullptr);
+    XPIC_HIP(hipGetLastError());
+  }
+  XPIC_HIP(hipMemcpyAsync(h.data(), s.p, 48 * n, hipMemcpyDeviceToHost, ctx->stream));
+  if (cn) {
+    XPIC_HIP(hipMemcpyAsync(iterations_sum, tot.p, 8 * n, hipMemcpyDeviceToHost, ctx->stream));
+    XPIC_HIP(hipMemcpyAsync(iterations_max, mx.p, 4 * n, hipMemcpyDeviceToHost, ctx->stream));
+  }
+  std::vector<double> hs;
+  if (nsamp > 0) {
+    hs.resize((size_t)6 * n * nsamp);
+    XPIC_HIP(hipMemcpyAsync(hs.data(), sm.p, (size_t)sample_bytes, hipMemcpyDeviceToHost, ctx->stream)); // the samples, once
+  }
+  XPIC_HIP(hipStreamSynchronize(ctx->stream));
+  if (!cn) {
+    if (iterations_sum) std::fill(iterations_sum, iterations_sum + n, (int64_t)0);
+    if (iterations_max) std::fill(iterations_max, iterations_max + n, 0);
+  }
+  to_aos(h.data(), n, p_6);
+  for (int64_t k = 0; k < nsamp; ++k) to_aos(hs.data() + (size_t)6 * n * k, n, samples + (size_t)6 * n * k);
+  return 0;
+}
+
+}  // extern "C"
