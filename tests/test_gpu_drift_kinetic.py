@@ -242,6 +242,8 @@ def test_edges(X, ctx, fields):
         (lambda: L_.xpic_drift_kinetic_trace(ctx.h, n1, C.byref(P), -1, C.c_int64(1), C.c_int64(0), None, None, tot1, it1), "state_6"),
         (lambda: L_.xpic_drift_kinetic_trace(ctx.h, n1, C.byref(P), -1, C.c_int64(1), C.c_int64(0), ptr, ptr, tot1, it1), "sample_every"),
         (lambda: L_.xpic_drift_kinetic_trace(ctx.h, n1, C.byref(P), -1, C.c_int64(1), C.c_int64(0), ptr, None, None, it1), "iterations_total"),
+        # a sample buffer whose size overflows 64 bits is refused before anything is allocated or launched
+        (lambda: L_.xpic_drift_kinetic_trace(ctx.h, n1, C.byref(P), -1, C.c_int64(1 << 62), C.c_int64(1), ptr, ptr, tot1, it1), "sample buffer"),
     ]
     for call, word in calls:
         assert call() != 0

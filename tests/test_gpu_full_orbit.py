@@ -185,6 +185,56 @@ def test_uniform_fields_against_the_golden_tables(X, oracle, ex, sid):
     assert spread <= 4 * EPS * rmax * steps
 
 
+def test_staging_at_ragged_sizes(X, fields, particles):
+    """The host staging the batch calls share (transposition, byte counts, launch grid) at n = 1, 255, 257: one record
+    tiled n times, so every lane of every call must return the bits of the n = 1 call, iteration counts included, and a
+    5-step trace sampled every 2 steps the bits of 2, 4 and 5 single pushes.  The drift-kinetic pusher runs on the same
+    8 x 8 x 8 fields with a grad |B| vector in W0, and reads the record as {r, p_parallel, p_perp, mu_p}."""
+    E, B = fields
+    g = make_ctx(X, E, B)
+    g.set_field(X.W0, 0.1 * E)
+    one = particles[3:4].copy()
+    one[0, 3:] = (0.4, 0.3, 0.05)
+    cn = dict(atol=0.0, rtol=0.0, maxit=3)  # exactly 3 iterations a step
+    pushes = {
+        "dk": lambda p: g.drift_kinetic_push(p, R.QM, 1.0, R.DT, X.W0),
+        "EB2B": lambda p: g.full_orbit_push(p, "EB2B", R.QM, R.DT),
+        "CN": lambda p: g.full_orbit_push(p, "CN", R.QM, R.DT, **cn),
+    }
+    traces = {
+        "dk": lambda p: g.drift_kinetic_trace(p, 5, R.QM, 1.0, R.DT, X.W0, sample_every=2),
+        "EB2B": lambda p: g.full_orbit_trace(p, 5, "EB2B", R.QM, R.DT, sample_every=2),
+        "CN": lambda p: g.full_orbit_trace(p, 5, "CN", R.QM, R.DT, sample_every=2, **cn),
+    }
+    states, counts = {}, {}
+    for name, push in pushes.items():
+        p, states[name], counts[name] = one, [], []
+        for _ in range(5):
+            p, its = push(p)
+            assert np.isfinite(p).all(), name
+            states[name].append(p[0])
+            counts[name].append(int(its[0]))
+    assert min(counts["dk"]) >= 1 and counts["CN"] == [3] * 5 and counts["EB2B"] == [0] * 5
+    rn, r0 = one[:, :3] + 0.3, one[:, :3]
+    E1, B1 = g.implicit_esirkepov_interpolate(rn, r0)
+    for n in (255, 257):
+        tiled = np.tile(one, (n, 1))
+        for name, push in pushes.items():
+            pn, its = push(tiled)
+            assert pn.shape == (n, 6) and np.array_equal(pn, np.tile(states[name][0], (n, 1))), (name, n)
+            assert np.array_equal(its, np.full(n, counts[name][0])), (name, n)
+        En, Bn = g.implicit_esirkepov_interpolate(np.tile(rn, (n, 1)), np.tile(r0, (n, 1)))
+        assert np.array_equal(En, np.tile(E1, (n, 1))) and np.array_equal(Bn, np.tile(B1, (n, 1))), n
+    n = 257
+    for name, trace in traces.items():
+        out, samples, tot, mx = trace(np.tile(one, (n, 1)))
+        assert samples.shape == (2, n, 6), name
+        assert np.array_equal(samples[0], np.tile(states[name][1], (n, 1))), name
+        assert np.array_equal(samples[1], np.tile(states[name][3], (n, 1))), name
+        assert np.array_equal(out, np.tile(states[name][4], (n, 1))), name
+        assert np.array_equal(tot, np.full(n, sum(counts[name]))) and np.array_equal(mx, np.full(n, max(counts[name]))), name
+
+
 def test_argument_checks(X, ctx, particles):
     import ctypes as C
 
@@ -232,6 +282,7 @@ def test_argument_checks(X, ctx, particles):
         (lambda: L_.xpic_full_orbit_trace(ctx.h, n1, C.byref(PC), one, one, ptr, None, tot1, None), "iterations_max"),
         # a sample buffer whose size overflows 64 bits is refused before anything is allocated
         (lambda: L_.xpic_full_orbit_trace(ctx.h, C.c_int64(1 << 30), C.byref(P), big, one, ptr, ptr, tot1, it1), "sample buffer"),
+        (lambda: L_.xpic_full_orbit_trace(ctx.h, n1, C.byref(P), big, one, ptr, ptr, tot1, it1), "sample buffer"),
     ]
     for call, word in calls:
         assert call() != 0

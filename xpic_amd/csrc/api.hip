@@ -5,6 +5,7 @@
 #include <cstdlib>
 #include <cstring>
 
+#include "batch.h"
 #include "common.h"
 #include "lstencil.h"
 
@@ -899,20 +900,13 @@ int xpic_velocity_distribution(xpic_ctx* ctx, int sort, int projector, int geome
   const long nb = (long)vn * vn;
   // the scratch vector XPIC_W0 when it holds the histogram; a finer histogram than a (small) field vector holds takes a
   // buffer of its own for the call
-  double* hist = ctx->field[XPIC_W0];
-  const bool own = nb > ctx->nvec;
-  if (own) XPIC_HIP(hipMalloc(&hist, sizeof(double) * nb));
-  int rc = velocity_distribution(ctx, ctx->sorts[sort], projector, geometry, geom, vreg, hist);
-  if (rc == 0) {
-    hipError_t e = hipMemcpyAsync(out, hist, sizeof(double) * nb, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) {
-      set_error(std::string("velocity distribution read-back: ") + hipGetErrorString(e));
-      rc = 1;
-    }
-  }
-  if (own) (void)hipFree(hist);
-  return rc;
+  DevScratch<double> own;
+  if (nb > ctx->nvec) XPIC_CALL(own.alloc(nb));
+  double* hist = own.p ? own.p : ctx->field[XPIC_W0];
+  XPIC_CALL(velocity_distribution(ctx, ctx->sorts[sort], projector, geometry, geom, vreg, hist));
+  XPIC_HIP(hipMemcpyAsync(out, hist, sizeof(double) * nb, hipMemcpyDeviceToHost, ctx->stream));
+  XPIC_HIP(hipStreamSynchronize(ctx->stream));
+  return 0;
 }
 
 // ---- the per-step commands (commands.hip)
@@ -942,69 +936,6 @@ int xpic_set_coils_field(xpic_ctx* ctx, int field, int ncoils, const double* coi
 { // SetCoilsField::operator(), set_magnetic_field.cpp:38-150
   CTX_CHECK(ctx); FIELD_CHECK(field);
   return set_coils_field(ctx, ctx->field[field], ncoils, coils3);
-}
-
-// the checks the three drift-kinetic calls share; *gradB: the vector of gradB_field, null for -1
-static int dk_check(xpic_ctx* ctx, int64_t n, int gradB_field, const double** gradB)
-{
-  CTX_CHECK(ctx);
-  XPIC_CHECK(n >= 0, "drift_kinetic: n is negative");
-  XPIC_CHECK(ctx->geom.nranks == 1 && ctx->g.G == 0,
-    "drift_kinetic: a context of several z-slabs (or a self_ring one) is not supported: the gathers wrap z in the kernel");
-  XPIC_CHECK(gradB_field == -1 || (valid_field(gradB_field) && ctx->field[gradB_field]),
-    "drift_kinetic: gradB_field is neither -1 nor an allocated field id");
-  *gradB = gradB_field == -1 ? nullptr : ctx->field[gradB_field];
-  return 0;
-}
-
-static int dk_check_params(const xpic_dk_params* P)
-{
-  XPIC_CHECK(P, "drift_kinetic: params is null");
-  XPIC_CHECK(P->maxit >= 1, "drift_kinetic: maxit must be >= 1");
-  XPIC_CHECK(P->mp != 0.0, "drift_kinetic: mp must not be 0");
-  return 0;
-}
-
-int xpic_drift_kinetic_interpolate(xpic_ctx* ctx, int64_t n, const double* rn3, const double* r03, int gradB_field,
-  double* Ep3, double* Bp3, double* gradBp3)
-{ // DriftKineticEsirkepov::interpolate, drift_kinetic_implicit.cpp:11-31
-  const double* gradB;
-  XPIC_CALL(dk_check(ctx, n, gradB_field, &gradB));
-  XPIC_CHECK(rn3, "drift_kinetic_interpolate: rn3 is null");
-  XPIC_CHECK(r03, "drift_kinetic_interpolate: r03 is null");
-  XPIC_CHECK(Ep3, "drift_kinetic_interpolate: Ep3 is null");
-  XPIC_CHECK(Bp3, "drift_kinetic_interpolate: Bp3 is null");
-  XPIC_CHECK(gradBp3, "drift_kinetic_interpolate: gradBp3 is null");
-  if (n == 0) return 0;
-  return dk_interpolate(ctx, n, rn3, r03, gradB, Ep3, Bp3, gradBp3);
-}
-
-int xpic_drift_kinetic_push(xpic_ctx* ctx, int64_t n, const xpic_dk_params* params, int gradB_field, const double* p0_6,
-  double* pn_6, int* iterations)
-{ // DriftKineticPush::process, drift_kinetic_push.cpp:48-108
-  const double* gradB;
-  XPIC_CALL(dk_check(ctx, n, gradB_field, &gradB));
-  XPIC_CALL(dk_check_params(params));
-  XPIC_CHECK(p0_6, "drift_kinetic_push: p0_6 is null");
-  XPIC_CHECK(pn_6, "drift_kinetic_push: pn_6 is null");
-  XPIC_CHECK(iterations, "drift_kinetic_push: iterations is null");
-  if (n == 0) return 0;
-  return dk_push(ctx, n, *params, gradB, p0_6, pn_6, iterations);
-}
-
-int xpic_drift_kinetic_trace(xpic_ctx* ctx, int64_t n, const xpic_dk_params* params, int gradB_field, int64_t steps,
-  int64_t sample_every, double* state_6, double* samples, int64_t* iterations_total, int* iterations_max)
-{
-  const double* gradB;
-  XPIC_CALL(dk_check(ctx, n, gradB_field, &gradB));
-  XPIC_CALL(dk_check_params(params));
-  XPIC_CHECK(steps >= 0, "drift_kinetic_trace: steps is negative");
-  XPIC_CHECK(!samples || sample_every >= 1, "drift_kinetic_trace: sample_every must be >= 1 when samples are asked for");
-  XPIC_CHECK(state_6, "drift_kinetic_trace: state_6 is null");
-  XPIC_CHECK(iterations_total, "drift_kinetic_trace: iterations_total is null");
-  XPIC_CHECK(iterations_max, "drift_kinetic_trace: iterations_max is null");
-  if (n == 0) return 0;
-  return dk_trace(ctx, n, *params, gradB, steps, sample_every, state_6, samples, iterations_total, iterations_max);
 }
 
 int xpic_charge_collect(xpic_ctx* ctx) // ChargeConservation::initialize, charge_conservation.cpp:117-123
@@ -1077,10 +1008,11 @@ __global__ void __launch_bounds__(256) k_copy8(const double* __restrict__ in, do
 int xpic_probe_copy_bandwidth(xpic_ctx* ctx, int64_t bytes, int reps, double* bytes_per_s)
 {
   CTX_CHECK(ctx);
-  double2 *a = nullptr, *b = nullptr;
+  DevScratch<double2> da, db;
   const long n = bytes / 16;
-  XPIC_HIP(hipMalloc(&a, n * 16));
-  XPIC_HIP(hipMalloc(&b, n * 16));
+  XPIC_CALL(da.alloc(n));
+  XPIC_CALL(db.alloc(n));
+  double2 *a = da.p, *b = db.p;
   XPIC_HIP(hipMemsetAsync(a, 1, n * 16, ctx->stream));
   hipEvent_t e0 = get_event(ctx), e1 = get_event(ctx);
   hipLaunchKernelGGL(k_copy16, dim3(2048), dim3(256), 0, ctx->stream, a, b, n);
@@ -1096,8 +1028,6 @@ int xpic_probe_copy_bandwidth(xpic_ctx* ctx, int64_t bytes, int reps, double* by
   *bytes_per_s = 2.0 * n * 16 * reps / (ms * 1e-3);
   ctx->event_pool.push_back(e0);
   ctx->event_pool.push_back(e1);
-  XPIC_HIP(hipFree(a));
-  XPIC_HIP(hipFree(b));
   return 0;
 }
 

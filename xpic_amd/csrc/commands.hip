@@ -14,6 +14,7 @@
 #include <cmath>
 #include <vector>
 
+#include "batch.h"
 #include "common.h"
 #include "device_common.h"
 
@@ -505,23 +506,21 @@ int set_coils_field(xpic_ctx* c, double* F, int ncoils, const double* coils3)
   std::vector<double> h(kCoilN + 3 * (size_t)ncoils);
   for (int i = 0; i < kCoilN; ++i) h[i] = std::cos(i * (2 * M_PI / kCoilN));
   for (int i = 0; i < 3 * ncoils; ++i) h[kCoilN + i] = coils3[i];
-  double* d = nullptr;
-  XPIC_HIP(hipMalloc(&d, sizeof(double) * h.size()));
+  DevScratch<double> d;
+  XPIC_CALL(d.alloc(h.size()));
   Timed t(c, "cmd_coils");
-  hipError_t e = hipMemcpyAsync(d, h.data(), sizeof(double) * h.size(), hipMemcpyHostToDevice, c->stream);
+  XPIC_CALL(upload(d, h.data(), h.size(), c->stream));
   // 6000 fp64 divisions and square roots per node and coil: ~0.23 s for two coils at 256^3, linear in nodes x coils.
   // The launch is split into groups of whole planes of at most ~2^21 nodes x coils (~14 ms each at 256^3), so no single
   // kernel runs for seconds on a larger grid or with more coils.
   const long plane = c->g.plane;
   const long per = std::max(1L, (1L << 21) / (plane * ncoils)) * plane;
-  for (long i0 = 0; e == hipSuccess && i0 < c->g.nown; i0 += per) {
+  for (long i0 = 0; i0 < c->g.nown; i0 += per) {
     const long i1 = std::min(c->g.nown, i0 + per);
-    hipLaunchKernelGGL(k_coils, dim3(cgrid(i1 - i0)), dim3(kBlock), 0, c->stream, c->g, F, d, d + kCoilN, ncoils, i0, i1);
-    e = hipGetLastError();
+    hipLaunchKernelGGL(k_coils, dim3(cgrid(i1 - i0)), dim3(kBlock), 0, c->stream, c->g, F, d.p, d.p + kCoilN, ncoils, i0, i1);
+    XPIC_HIP(hipGetLastError());
   }
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  (void)hipFree(d);
-  XPIC_HIP(e);
+  XPIC_HIP(hipStreamSynchronize(c->stream));
   return 0;
 }
 

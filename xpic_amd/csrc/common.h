@@ -378,14 +378,6 @@ int inject_particles(xpic_ctx* c, Sort& si, Sort& se, const xpic_inject_params& 
   int64_t* added, double* energy2);
 int set_coils_field(xpic_ctx* c, double* F, int ncoils, const double* coils3);
 
-// drift_kinetic.hip (the reference's DriftKineticEsirkepov / DriftKineticPush); gradB: a field vector or null (grad B = 0)
-int dk_interpolate(xpic_ctx* c, int64_t n, const double* rn3, const double* r03, const double* gradB, double* Ep3,
-  double* Bp3, double* gradBp3);
-int dk_push(xpic_ctx* c, int64_t n, const xpic_dk_params& P, const double* gradB, const double* p0_6, double* pn_6,
-  int* iterations);
-int dk_trace(xpic_ctx* c, int64_t n, const xpic_dk_params& P, const double* gradB, int64_t steps, int64_t sample_every,
-  double* state_6, double* samples, int64_t* iterations_total, int* iterations_max);
-
 // ecsim.hip
 int ecsim_fill_sort(xpic_ctx* c, Sort& s, const double* B, double* currI_sort, double* matL, bool first_sort, bool post_ghost_rows);
 int ecsim_fill_check(xpic_ctx* c); // the assembly's device-side error word, agreed on by all slabs (once per assembly)

@@ -6,10 +6,9 @@
 // state {x, y, z, p_parallel, p_perp, mu_p} lives in structure-of-arrays device buffers (s[k * n + q]).  Positions are
 // not folded into the box: the gathers wrap their node indices (ie_node), folding is the caller's business as
 // correct_coordinates is in the reference.  Single z-slab contexts only (G == 0: every index wraps, so no position,
-// however far out, reads outside a field vector).
-#include <algorithm>
-#include <vector>
-
+// however far out, reads outside a field vector).  The C entry points and their argument checks are at the end of the
+// file; the staging of the host records, the push and trace drivers and the sample buffer's size are batch.h's.
+#include "batch.h"
 #include "common.h"
 #include "device_common.h"
 #include "ie_shape.h"
@@ -23,8 +22,7 @@ namespace xpic {
 
 namespace {
 
-constexpr int kBlock = 256;
-constexpr int kLaunchSteps = XPIC_DK_LAUNCH_STEPS;
+constexpr int kBlock = kLaneBlock; // batch.h: lane_grid launches workgroups of this size
 
 struct DKPoint {
   double r[3], ppar, pperp, mu;
@@ -279,114 +277,100 @@ __global__ void __launch_bounds__(kBlock) k_dk_trace(GridDev g, const double* __
   it_max[q] = most;
 }
 
-struct DevBuf { // device scratch of one call, freed on scope exit
-  void* p = nullptr;
-  ~DevBuf() { if (p) (void)hipFree(p); }
-};
-
-inline dim3 dk_grid(int64_t n) { return dim3((unsigned)((n + kBlock - 1) / kBlock)); }
-
-// [n][6] host records -> [6][n], and back
-void to_soa(const double* aos, int64_t n, std::vector<double>& soa)
+// the checks the three calls share; *gradB: the vector of gradB_field, null for -1 (grad B = 0)
+int dk_check(xpic_ctx* ctx, int64_t n, int gradB_field, const double** gradB)
 {
-  soa.resize((size_t)6 * n);
-  for (int64_t q = 0; q < n; ++q)
-    for (int k = 0; k < 6; ++k) soa[(size_t)k * n + q] = aos[6 * q + k];
+  XPIC_CHECK(ctx != nullptr, "null context");
+  XPIC_CHECK(n >= 0, "drift_kinetic: n is negative");
+  XPIC_CHECK(ctx->geom.nranks == 1 && ctx->g.G == 0,
+    "drift_kinetic: a context of several z-slabs (or a self_ring one) is not supported: the gathers wrap z in the kernel");
+  XPIC_CHECK(gradB_field == -1 || (gradB_field >= 0 && gradB_field < XPIC_NFIELDS && ctx->field[gradB_field]),
+    "drift_kinetic: gradB_field is neither -1 nor an allocated field id");
+  *gradB = gradB_field == -1 ? nullptr : ctx->field[gradB_field];
+  return 0;
 }
-void to_aos(const double* soa, int64_t n, double* aos)
+
+int dk_check_params(const xpic_dk_params* P)
 {
-  for (int64_t q = 0; q < n; ++q)
-    for (int k = 0; k < 6; ++k) aos[6 * q + k] = soa[(size_t)k * n + q];
+  XPIC_CHECK(P, "drift_kinetic: params is null");
+  XPIC_CHECK(P->maxit >= 1, "drift_kinetic: maxit must be >= 1");
+  XPIC_CHECK(P->mp != 0.0, "drift_kinetic: mp must not be 0");
+  return 0;
 }
 
 }  // namespace
 
-int dk_interpolate(xpic_ctx* c, int64_t n, const double* rn3, const double* r03, const double* gradB, double* Ep3,
-  double* Bp3, double* gradBp3)
-{
-  DevBuf a, b, o;
-  XPIC_HIP(hipMalloc(&a.p, 24 * n)); XPIC_HIP(hipMalloc(&b.p, 24 * n)); XPIC_HIP(hipMalloc(&o.p, 72 * n));
-  XPIC_HIP(hipMemcpyAsync(a.p, rn3, 24 * n, hipMemcpyHostToDevice, c->stream));
-  XPIC_HIP(hipMemcpyAsync(b.p, r03, 24 * n, hipMemcpyHostToDevice, c->stream));
-  double* out = (double*)o.p;
-  {
-    Timed t(c, "dk_interpolate");
-    if (gradB)
-      hipLaunchKernelGGL(k_dk_interpolate<true>, dk_grid(n), dim3(kBlock), 0, c->stream, c->g, c->field[XPIC_E], c->field[XPIC_B],
-        gradB, (long)n, (const double*)a.p, (const double*)b.p, out, out + 3 * n, out + 6 * n);
-    else
-      hipLaunchKernelGGL(k_dk_interpolate<false>, dk_grid(n), dim3(kBlock), 0, c->stream, c->g, c->field[XPIC_E], c->field[XPIC_B],
-        gradB, (long)n, (const double*)a.p, (const double*)b.p, out, out + 3 * n, out + 6 * n);
-    XPIC_HIP(hipGetLastError());
-  }
-  XPIC_HIP(hipMemcpyAsync(Ep3, out, 24 * n, hipMemcpyDeviceToHost, c->stream));
-  XPIC_HIP(hipMemcpyAsync(Bp3, out + 3 * n, 24 * n, hipMemcpyDeviceToHost, c->stream));
-  XPIC_HIP(hipMemcpyAsync(gradBp3, out + 6 * n, 24 * n, hipMemcpyDeviceToHost, c->stream));
-  XPIC_HIP(hipStreamSynchronize(c->stream));
-  return 0;
-}
-
-int dk_push(xpic_ctx* c, int64_t n, const xpic_dk_params& P, const double* gradB, const double* p0_6, double* pn_6,
-  int* iterations)
-{
-  std::vector<double> h;
-  to_soa(p0_6, n, h);
-  DevBuf s0, sn, it;
-  XPIC_HIP(hipMalloc(&s0.p, 48 * n)); XPIC_HIP(hipMalloc(&sn.p, 48 * n)); XPIC_HIP(hipMalloc(&it.p, 4 * n));
-  XPIC_HIP(hipMemcpyAsync(s0.p, h.data(), 48 * n, hipMemcpyHostToDevice, c->stream));
-  {
-    Timed t(c, "dk_push");
-    if (gradB)
-      hipLaunchKernelGGL(k_dk_push<true>, dk_grid(n), dim3(kBlock), 0, c->stream, c->g, c->field[XPIC_E], c->field[XPIC_B], gradB,
-        P, (long)n, (const double*)s0.p, (double*)sn.p, (int*)it.p);
-    else
-      hipLaunchKernelGGL(k_dk_push<false>, dk_grid(n), dim3(kBlock), 0, c->stream, c->g, c->field[XPIC_E], c->field[XPIC_B], gradB,
-        P, (long)n, (const double*)s0.p, (double*)sn.p, (int*)it.p);
-    XPIC_HIP(hipGetLastError());
-  }
-  XPIC_HIP(hipMemcpyAsync(h.data(), sn.p, 48 * n, hipMemcpyDeviceToHost, c->stream));
-  XPIC_HIP(hipMemcpyAsync(iterations, it.p, 4 * n, hipMemcpyDeviceToHost, c->stream));
-  XPIC_HIP(hipStreamSynchronize(c->stream));
-  to_aos(h.data(), n, pn_6);
-  return 0;
-}
-
-int dk_trace(xpic_ctx* c, int64_t n, const xpic_dk_params& P, const double* gradB, int64_t steps, int64_t sample_every,
-  double* state_6, double* samples, int64_t* iterations_total, int* iterations_max)
-{
-  const int64_t nsamp = samples ? steps / sample_every : 0;
-  std::vector<double> h;
-  to_soa(state_6, n, h);
-  DevBuf s, sm, tot, mx;
-  XPIC_HIP(hipMalloc(&s.p, 48 * n)); XPIC_HIP(hipMalloc(&tot.p, 8 * n)); XPIC_HIP(hipMalloc(&mx.p, 4 * n));
-  if (nsamp > 0) XPIC_HIP(hipMalloc(&sm.p, 48 * n * nsamp));
-  XPIC_HIP(hipMemcpyAsync(s.p, h.data(), 48 * n, hipMemcpyHostToDevice, c->stream));
-  XPIC_HIP(hipMemsetAsync(tot.p, 0, 8 * n, c->stream));
-  XPIC_HIP(hipMemsetAsync(mx.p, 0, 4 * n, c->stream));
-  // one launch covers at most kLaunchSteps steps, so no launch runs for seconds however long the trace
-  for (int64_t first = 0; first < steps; first += kLaunchSteps) {
-    const int ns = (int)std::min<int64_t>(kLaunchSteps, steps - first);
-    Timed t(c, "dk_trace");
-    if (gradB)
-      hipLaunchKernelGGL(k_dk_trace<true>, dk_grid(n), dim3(kBlock), 0, c->stream, c->g, c->field[XPIC_E], c->field[XPIC_B], gradB,
-        P, (long)n, (double*)s.p, (long)first, ns, (long)sample_every, (double*)sm.p, (long long*)tot.p, (int*)mx.p);
-    else
-      hipLaunchKernelGGL(k_dk_trace<false>, dk_grid(n), dim3(kBlock), 0, c->stream, c->g, c->field[XPIC_E], c->field[XPIC_B], gradB,
-        P, (long)n, (double*)s.p, (long)first, ns, (long)sample_every, (double*)sm.p, (long long*)tot.p, (int*)mx.p);
-    XPIC_HIP(hipGetLastError());
-  }
-  XPIC_HIP(hipMemcpyAsync(h.data(), s.p, 48 * n, hipMemcpyDeviceToHost, c->stream));
-  XPIC_HIP(hipMemcpyAsync(iterations_total, tot.p, 8 * n, hipMemcpyDeviceToHost, c->stream));
-  XPIC_HIP(hipMemcpyAsync(iterations_max, mx.p, 4 * n, hipMemcpyDeviceToHost, c->stream));
-  std::vector<double> hs;
-  if (nsamp > 0) {
-    hs.resize((size_t)6 * n * nsamp);
-    XPIC_HIP(hipMemcpyAsync(hs.data(), sm.p, 48 * n * nsamp, hipMemcpyDeviceToHost, c->stream)); // the samples, once
-  }
-  XPIC_HIP(hipStreamSynchronize(c->stream));
-  to_aos(h.data(), n, state_6);
-  for (int64_t k = 0; k < nsamp; ++k) to_aos(hs.data() + (size_t)6 * n * k, n, samples + (size_t)6 * n * k);
-  return 0;
-}
-
 }  // namespace xpic
+
+using namespace xpic;
+
+extern "C" {
+
+int xpic_drift_kinetic_interpolate(xpic_ctx* ctx, int64_t n, const double* rn3, const double* r03, int gradB_field,
+  double* Ep3, double* Bp3, double* gradBp3)
+{ // DriftKineticEsirkepov::interpolate, drift_kinetic_implicit.cpp:11-31
+  const double* gradB;
+  XPIC_CALL(dk_check(ctx, n, gradB_field, &gradB));
+  XPIC_CHECK(rn3, "drift_kinetic_interpolate: rn3 is null");
+  XPIC_CHECK(r03, "drift_kinetic_interpolate: r03 is null");
+  XPIC_CHECK(Ep3, "drift_kinetic_interpolate: Ep3 is null");
+  XPIC_CHECK(Bp3, "drift_kinetic_interpolate: Bp3 is null");
+  XPIC_CHECK(gradBp3, "drift_kinetic_interpolate: gradBp3 is null");
+  if (n == 0) return 0;
+  DevScratch<double> a, b, o;
+  XPIC_CALL(a.alloc(3 * n)); XPIC_CALL(b.alloc(3 * n)); XPIC_CALL(o.alloc(9 * n));
+  XPIC_CALL(upload(a, rn3, 3 * n, ctx->stream));
+  XPIC_CALL(upload(b, r03, 3 * n, ctx->stream));
+  {
+    Timed t(ctx, "dk_interpolate");
+    hipLaunchKernelGGL(gradB ? k_dk_interpolate<true> : k_dk_interpolate<false>, lane_grid(n), dim3(kBlock), 0, ctx->stream,
+      ctx->g, ctx->field[XPIC_E], ctx->field[XPIC_B], gradB, (long)n, (const double*)a.p, (const double*)b.p, o.p, o.p + 3 * n,
+      o.p + 6 * n);
+    XPIC_HIP(hipGetLastError());
+  }
+  XPIC_CALL(download(Ep3, o, 3 * n, ctx->stream));
+  XPIC_CALL(download(Bp3, o, 3 * n, ctx->stream, 3 * n));
+  XPIC_CALL(download(gradBp3, o, 3 * n, ctx->stream, 6 * n));
+  XPIC_HIP(hipStreamSynchronize(ctx->stream));
+  return 0;
+}
+
+int xpic_drift_kinetic_push(xpic_ctx* ctx, int64_t n, const xpic_dk_params* params, int gradB_field, const double* p0_6,
+  double* pn_6, int* iterations)
+{ // DriftKineticPush::process, drift_kinetic_push.cpp:48-108
+  const double* gradB;
+  XPIC_CALL(dk_check(ctx, n, gradB_field, &gradB));
+  XPIC_CALL(dk_check_params(params));
+  XPIC_CHECK(p0_6, "drift_kinetic_push: p0_6 is null");
+  XPIC_CHECK(pn_6, "drift_kinetic_push: pn_6 is null");
+  XPIC_CHECK(iterations, "drift_kinetic_push: iterations is null");
+  if (n == 0) return 0;
+  return batch_push(ctx, "dk_push", n, true, p0_6, pn_6, iterations, [&](const double* s0, double* sn, int* it) {
+    hipLaunchKernelGGL(gradB ? k_dk_push<true> : k_dk_push<false>, lane_grid(n), dim3(kBlock), 0, ctx->stream, ctx->g,
+      ctx->field[XPIC_E], ctx->field[XPIC_B], gradB, *params, (long)n, s0, sn, it);
+  });
+}
+
+int xpic_drift_kinetic_trace(xpic_ctx* ctx, int64_t n, const xpic_dk_params* params, int gradB_field, int64_t steps,
+  int64_t sample_every, double* state_6, double* samples, int64_t* iterations_total, int* iterations_max)
+{
+  const double* gradB;
+  XPIC_CALL(dk_check(ctx, n, gradB_field, &gradB));
+  XPIC_CALL(dk_check_params(params));
+  XPIC_CHECK(steps >= 0, "drift_kinetic_trace: steps is negative");
+  XPIC_CHECK(!samples || sample_every >= 1, "drift_kinetic_trace: sample_every must be >= 1 when samples are asked for");
+  XPIC_CHECK(state_6, "drift_kinetic_trace: state_6 is null");
+  XPIC_CHECK(iterations_total, "drift_kinetic_trace: iterations_total is null");
+  XPIC_CHECK(iterations_max, "drift_kinetic_trace: iterations_max is null");
+  int64_t nsamp;
+  XPIC_CHECK(trace_sample_bytes(n, steps, sample_every, samples != nullptr, &nsamp) >= 0,
+    "drift_kinetic_trace: the sample buffer (48 n steps / sample_every bytes) is too large");
+  if (n == 0) return 0;
+  return batch_trace(ctx, "dk_trace", XPIC_DK_LAUNCH_STEPS, n, steps, nsamp, true, state_6, samples, iterations_total,
+    iterations_max, [&](double* s, long first, int ns, double* sm, long long* it_sum, int* it_max) {
+      hipLaunchKernelGGL(gradB ? k_dk_trace<true> : k_dk_trace<false>, lane_grid(n), dim3(kBlock), 0, ctx->stream, ctx->g,
+        ctx->field[XPIC_E], ctx->field[XPIC_B], gradB, *params, (long)n, s, first, ns, (long)sample_every, sm, it_sum, it_max);
+    });
+}
+
+}  // extern "C"

@@ -4,9 +4,11 @@
 //   ImplicitEsirkepov::Shape::setup    src/algorithms/implicit_esirkepov.cpp:11-57
 //   ImplicitEsirkepov::interpolate     :60-90   (E with the segment shape, B with Shape(midpoint) + SimpleInterpolation)
 //   ImplicitEsirkepov::decompose       :92-117
-// One lane per segment.  The scheme's outer loops (Crank-Nicolson sub-stepping, SNES) are not part of this build.
+// One lane per segment, the host arrays staged through batch.h.  The scheme's outer loops (Crank-Nicolson sub-stepping,
+// SNES) are not part of this build.
 #include <cfloat>
 
+#include "batch.h"
 #include "common.h"
 #include "device_common.h"
 #include "ie_shape.h"
@@ -15,7 +17,7 @@ namespace xpic {
 
 namespace {
 
-constexpr int kBlock = 256;
+constexpr int kBlock = kLaneBlock; // batch.h: lane_grid launches workgroups of this size
 
 __global__ void __launch_bounds__(kBlock) k_ie_interpolate(GridDev g, const double* __restrict__ E,
   const double* __restrict__ B, long n, const double* rn3, const double* r03, double* Ep3, double* Bp3)
@@ -141,11 +143,6 @@ __global__ void __launch_bounds__(kBlock) k_cell_traversal(GridDev g, long n, co
   counts[q] = np;
 }
 
-struct DevBuf { // host array <-> device scratch, freed on scope exit
-  void* p = nullptr;
-  ~DevBuf() { if (p) (void)hipFree(p); }
-};
-
 }  // namespace
 
 }  // namespace xpic
@@ -159,17 +156,19 @@ int xpic_cell_traversal(xpic_ctx* ctx, int64_t n, const double* end3, const doub
 {
   XPIC_CHECK(ctx && end3 && start3 && pts && counts && n >= 0 && max_pts >= 2, "bad argument");
   if (n == 0) return 0;
-  DevBuf e, s, p, k;
-  XPIC_HIP(hipMalloc(&e.p, 24 * n)); XPIC_HIP(hipMalloc(&s.p, 24 * n));
-  XPIC_HIP(hipMalloc(&p.p, 24 * n * max_pts)); XPIC_HIP(hipMalloc(&k.p, 4 * n));
-  XPIC_HIP(hipMemcpyAsync(e.p, end3, 24 * n, hipMemcpyHostToDevice, ctx->stream));
-  XPIC_HIP(hipMemcpyAsync(s.p, start3, 24 * n, hipMemcpyHostToDevice, ctx->stream));
-  XPIC_HIP(hipMemsetAsync(p.p, 0, 24 * n * max_pts, ctx->stream));
-  hipLaunchKernelGGL(k_cell_traversal, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, ctx->stream, ctx->g, (long)n,
-    (const double*)e.p, (const double*)s.p, max_pts, (double*)p.p, (int*)k.p);
+  DevScratch<double> e, s, p;
+  DevScratch<int> k;
+  const size_t npts = (size_t)3 * n * max_pts; // doubles
+  XPIC_CALL(e.alloc(3 * n)); XPIC_CALL(s.alloc(3 * n));
+  XPIC_CALL(p.alloc(npts)); XPIC_CALL(k.alloc(n));
+  XPIC_CALL(upload(e, end3, 3 * n, ctx->stream));
+  XPIC_CALL(upload(s, start3, 3 * n, ctx->stream));
+  XPIC_CALL(zero(p, npts, ctx->stream));
+  hipLaunchKernelGGL(k_cell_traversal, lane_grid(n), dim3(kBlock), 0, ctx->stream, ctx->g, (long)n, (const double*)e.p,
+    (const double*)s.p, max_pts, p.p, k.p);
   XPIC_HIP(hipGetLastError());
-  XPIC_HIP(hipMemcpyAsync(pts, p.p, 24 * n * max_pts, hipMemcpyDeviceToHost, ctx->stream));
-  XPIC_HIP(hipMemcpyAsync(counts, k.p, 4 * n, hipMemcpyDeviceToHost, ctx->stream));
+  XPIC_CALL(download(pts, p, npts, ctx->stream));
+  XPIC_CALL(download(counts, k, n, ctx->stream));
   XPIC_HIP(hipStreamSynchronize(ctx->stream));
   return 0;
 }
@@ -181,16 +180,16 @@ int xpic_implicit_esirkepov_interpolate(xpic_ctx* ctx, int64_t n, const double* 
   if (n == 0) return 0;
   XPIC_CALL(halo_fill(ctx, ctx->field[XPIC_E]));
   XPIC_CALL(halo_fill(ctx, ctx->field[XPIC_B]));
-  DevBuf a, b, e, m;
-  XPIC_HIP(hipMalloc(&a.p, 24 * n)); XPIC_HIP(hipMalloc(&b.p, 24 * n));
-  XPIC_HIP(hipMalloc(&e.p, 24 * n)); XPIC_HIP(hipMalloc(&m.p, 24 * n));
-  XPIC_HIP(hipMemcpyAsync(a.p, rn3, 24 * n, hipMemcpyHostToDevice, ctx->stream));
-  XPIC_HIP(hipMemcpyAsync(b.p, r03, 24 * n, hipMemcpyHostToDevice, ctx->stream));
-  hipLaunchKernelGGL(k_ie_interpolate, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, ctx->stream, ctx->g,
-    ctx->field[XPIC_E], ctx->field[XPIC_B], (long)n, (const double*)a.p, (const double*)b.p, (double*)e.p, (double*)m.p);
+  DevScratch<double> a, b, e, m;
+  XPIC_CALL(a.alloc(3 * n)); XPIC_CALL(b.alloc(3 * n));
+  XPIC_CALL(e.alloc(3 * n)); XPIC_CALL(m.alloc(3 * n));
+  XPIC_CALL(upload(a, rn3, 3 * n, ctx->stream));
+  XPIC_CALL(upload(b, r03, 3 * n, ctx->stream));
+  hipLaunchKernelGGL(k_ie_interpolate, lane_grid(n), dim3(kBlock), 0, ctx->stream, ctx->g, ctx->field[XPIC_E],
+    ctx->field[XPIC_B], (long)n, (const double*)a.p, (const double*)b.p, e.p, m.p);
   XPIC_HIP(hipGetLastError());
-  XPIC_HIP(hipMemcpyAsync(Ep3, e.p, 24 * n, hipMemcpyDeviceToHost, ctx->stream));
-  XPIC_HIP(hipMemcpyAsync(Bp3, m.p, 24 * n, hipMemcpyDeviceToHost, ctx->stream));
+  XPIC_CALL(download(Ep3, e, 3 * n, ctx->stream));
+  XPIC_CALL(download(Bp3, m, 3 * n, ctx->stream));
   XPIC_HIP(hipStreamSynchronize(ctx->stream));
   return 0;
 }
@@ -201,20 +200,19 @@ int xpic_implicit_esirkepov_decompose(xpic_ctx* ctx, int64_t n, const double* al
   XPIC_CHECK(ctx && alpha && v3 && rn3 && r03 && n >= 0, "bad argument");
   XPIC_CHECK(field >= 0 && field < XPIC_NFIELDS && ctx->field[field], "no such field vector");
   if (n == 0) return 0;
-  DevBuf al, v, a, b;
-  XPIC_HIP(hipMalloc(&al.p, 8 * n)); XPIC_HIP(hipMalloc(&v.p, 24 * n));
-  XPIC_HIP(hipMalloc(&a.p, 24 * n)); XPIC_HIP(hipMalloc(&b.p, 24 * n));
-  XPIC_HIP(hipMemcpyAsync(al.p, alpha, 8 * n, hipMemcpyHostToDevice, ctx->stream));
-  XPIC_HIP(hipMemcpyAsync(v.p, v3, 24 * n, hipMemcpyHostToDevice, ctx->stream));
-  XPIC_HIP(hipMemcpyAsync(a.p, rn3, 24 * n, hipMemcpyHostToDevice, ctx->stream));
-  XPIC_HIP(hipMemcpyAsync(b.p, r03, 24 * n, hipMemcpyHostToDevice, ctx->stream));
+  DevScratch<double> al, v, a, b;
+  XPIC_CALL(al.alloc(n)); XPIC_CALL(v.alloc(3 * n));
+  XPIC_CALL(a.alloc(3 * n)); XPIC_CALL(b.alloc(3 * n));
+  XPIC_CALL(upload(al, alpha, n, ctx->stream));
+  XPIC_CALL(upload(v, v3, 3 * n, ctx->stream));
+  XPIC_CALL(upload(a, rn3, 3 * n, ctx->stream));
+  XPIC_CALL(upload(b, r03, 3 * n, ctx->stream));
   // deposit into a zeroed scratch vector (ghost planes included), fold the ghosts, then add: DMLocalToGlobal(ADD)
   double* tmp = ctx->field[XPIC_W2];
   XPIC_CHECK(tmp != ctx->field[field], "XPIC_W2 is the scratch vector of this call");
-  XPIC_CALL(vec_set(ctx, tmp, 0.0));
   XPIC_HIP(hipMemsetAsync(tmp, 0, sizeof(double) * ctx->nvec, ctx->stream));
-  hipLaunchKernelGGL(k_ie_decompose, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, ctx->stream, ctx->g, tmp,
-    (long)n, (const double*)al.p, (const double*)v.p, (const double*)a.p, (const double*)b.p);
+  hipLaunchKernelGGL(k_ie_decompose, lane_grid(n), dim3(kBlock), 0, ctx->stream, ctx->g, tmp, (long)n,
+    (const double*)al.p, (const double*)v.p, (const double*)a.p, (const double*)b.p);
   XPIC_HIP(hipGetLastError());
   XPIC_CALL(halo_add(ctx, tmp, 3));
   XPIC_CALL(vec_axpy(ctx, ctx->field[field], 1.0, tmp));

@@ -4,6 +4,7 @@
 #include <cmath>
 #include <utility>
 
+#include "batch.h"
 #include "common.h"
 #include "device_common.h"
 #include "lstencil.h"
@@ -877,30 +878,28 @@ int scalar_norm12_host(xpic_ctx* c, const double* f, double* out2) // VecNorm(NO
 int field_import(xpic_ctx* c, double* dst, const double* src_host)
 {
   const long n = c->g.nown * 3;
-  double* tmp = nullptr;
-  XPIC_HIP(hipMalloc(&tmp, sizeof(double) * n));
-  XPIC_HIP(hipMemcpyAsync(tmp, src_host, sizeof(double) * n, hipMemcpyHostToDevice, c->stream));
+  DevScratch<double> tmp;
+  XPIC_CALL(tmp.alloc(n));
+  XPIC_CALL(upload(tmp, src_host, n, c->stream));
   long blocks = (n + kBlock - 1) / kBlock;
   if (blocks > 65536) blocks = 65536;
-  hipLaunchKernelGGL(k_import, dim3((unsigned)blocks), dim3(kBlock), 0, c->stream, c->g, tmp, dst);
+  hipLaunchKernelGGL(k_import, dim3((unsigned)blocks), dim3(kBlock), 0, c->stream, c->g, tmp.p, dst);
   XPIC_HIP(hipGetLastError());
   XPIC_HIP(hipStreamSynchronize(c->stream));
-  XPIC_HIP(hipFree(tmp));
   return 0; // ghost planes are refreshed by whoever reads them next (halo_fill is collective over the slabs)
 }
 
 int field_export(xpic_ctx* c, const double* src, double* dst_host)
 {
   const long n = c->g.nown * 3;
-  double* tmp = nullptr;
-  XPIC_HIP(hipMalloc(&tmp, sizeof(double) * n));
+  DevScratch<double> tmp;
+  XPIC_CALL(tmp.alloc(n));
   long blocks = (n + kBlock - 1) / kBlock;
   if (blocks > 65536) blocks = 65536;
-  hipLaunchKernelGGL(k_export, dim3((unsigned)blocks), dim3(kBlock), 0, c->stream, c->g, src, tmp);
+  hipLaunchKernelGGL(k_export, dim3((unsigned)blocks), dim3(kBlock), 0, c->stream, c->g, src, tmp.p);
   XPIC_HIP(hipGetLastError());
-  XPIC_HIP(hipMemcpyAsync(dst_host, tmp, sizeof(double) * n, hipMemcpyDeviceToHost, c->stream));
+  XPIC_CALL(download(dst_host, tmp, n, c->stream));
   XPIC_HIP(hipStreamSynchronize(c->stream));
-  XPIC_HIP(hipFree(tmp));
   return 0;
 }
 

@@ -9,11 +9,12 @@
 // Positions are not folded into the box: the gathers wrap their node indices (ie_node).  Single z-slab contexts only
 // (G == 0: every index wraps, so no position, however far out, reads outside a field vector).
 // Every loop is bounded by a constant or by an argument the entry points have range-checked: at most 4 nodes per axis,
-// maxit <= XPIC_FO_MAXIT iterations, at most XPIC_FO_LAUNCH_STEPS steps per launch.
+// maxit <= XPIC_FO_MAXIT iterations, at most XPIC_FO_LAUNCH_STEPS steps per launch.  The staging of the host records, the
+// push and trace drivers and the sample buffer's size are batch.h's, shared with drift_kinetic.hip.
 #include <algorithm>
 #include <cmath>
-#include <vector>
 
+#include "batch.h"
 #include "common.h"
 #include "device_common.h"
 #include "ie_shape.h"
@@ -28,7 +29,7 @@ namespace xpic {
 
 namespace {
 
-constexpr int kBlock = 256;
+constexpr int kBlock = kLaneBlock; // batch.h: lane_grid launches workgroups of this size
 constexpr int kLaunchSteps = XPIC_FO_LAUNCH_STEPS;
 
 __device__ inline void fo_load(const double* __restrict__ s, long n, long q, FOPoint& p)
@@ -98,26 +99,6 @@ __global__ void __launch_bounds__(kBlock) k_fo_trace(GridDev g, const double* __
   if (CN) { it_sum[q] = total; it_max[q] = most; }
 }
 
-struct DevBuf { // device scratch of one call, freed on scope exit
-  void* p = nullptr;
-  ~DevBuf() { if (p) (void)hipFree(p); }
-};
-
-inline dim3 fo_grid(int64_t n) { return dim3((unsigned)((n + kBlock - 1) / kBlock)); }
-
-// [n][6] host records -> [6][n], and back
-void to_soa(const double* aos, int64_t n, std::vector<double>& soa)
-{
-  soa.resize((size_t)6 * n);
-  for (int64_t q = 0; q < n; ++q)
-    for (int k = 0; k < 6; ++k) soa[(size_t)k * n + q] = aos[6 * q + k];
-}
-void to_aos(const double* soa, int64_t n, double* aos)
-{
-  for (int64_t q = 0; q < n; ++q)
-    for (int k = 0; k < 6; ++k) aos[6 * q + k] = soa[(size_t)k * n + q];
-}
-
 // the checks the two calls share
 int fo_check(xpic_ctx* ctx, int64_t n, const xpic_fo_params* P)
 {
@@ -151,27 +132,11 @@ int xpic_full_orbit_push(xpic_ctx* ctx, int64_t n, const xpic_fo_params* params,
   XPIC_CHECK(pn_6, "full_orbit_push: pn_6 is null");
   XPIC_CHECK(iterations || !cn, "full_orbit_push: iterations is null");
   if (n == 0) return 0;
-  std::vector<double> h;
-  to_soa(p0_6, n, h);
-  DevBuf s0, sn, it;
-  XPIC_HIP(hipMalloc(&s0.p, 48 * n)); XPIC_HIP(hipMalloc(&sn.p, 48 * n));
-  if (cn) XPIC_HIP(hipMalloc(&it.p, 4 * n));
-  XPIC_HIP(hipMemcpyAsync(s0.p, h.data(), 48 * n, hipMemcpyHostToDevice, ctx->stream));
-  {
-    Timed t(ctx, "fo_push");
-    if (cn)
-      hipLaunchKernelGGL(k_fo_push<true>, fo_grid(n), dim3(kBlock), 0, ctx->stream, ctx->g, ctx->field[XPIC_E],
-        ctx->field[XPIC_B], *params, (long)n, (const double*)s0.p, (double*)sn.p, (int*)it.p);
-    else
-      hipLaunchKernelGGL(k_fo_push<false>, fo_grid(n), dim3(kBlock), 0, ctx->stream, ctx->g, ctx->field[XPIC_E],
-        ctx->field[XPIC_B], *params, (long)n, (const double*)s0.p, (double*)sn.p, (int*)nullptr);
-    XPIC_HIP(hipGetLastError());
-  }
-  XPIC_HIP(hipMemcpyAsync(h.data(), sn.p, 48 * n, hipMemcpyDeviceToHost, ctx->stream));
-  if (cn) XPIC_HIP(hipMemcpyAsync(iterations, it.p, 4 * n, hipMemcpyDeviceToHost, ctx->stream));
-  XPIC_HIP(hipStreamSynchronize(ctx->stream));
+  XPIC_CALL(batch_push(ctx, "fo_push", n, cn, p0_6, pn_6, iterations, [&](const double* s0, double* sn, int* it) {
+    hipLaunchKernelGGL(cn ? k_fo_push<true> : k_fo_push<false>, lane_grid(n), dim3(kBlock), 0, ctx->stream, ctx->g,
+      ctx->field[XPIC_E], ctx->field[XPIC_B], *params, (long)n, s0, sn, it);
+  }));
   if (!cn && iterations) std::fill(iterations, iterations + n, 0);
-  to_aos(h.data(), n, pn_6);
   return 0;
 }
 
@@ -185,55 +150,21 @@ int xpic_full_orbit_trace(xpic_ctx* ctx, int64_t n, const xpic_fo_params* params
   XPIC_CHECK(p_6, "full_orbit_trace: p_6 is null");
   XPIC_CHECK(iterations_sum || !cn, "full_orbit_trace: iterations_sum is null");
   XPIC_CHECK(iterations_max || !cn, "full_orbit_trace: iterations_max is null");
-  // the sample buffer in 64-bit: 48 n bytes a sample; a size that does not fit is refused
-  const int64_t nsamp = samples ? steps / sample_every : 0;
-  int64_t row_bytes = 0, sample_bytes = 0;
-  XPIC_CHECK(!__builtin_mul_overflow((int64_t)48, n, &row_bytes) && !__builtin_mul_overflow(row_bytes, nsamp, &sample_bytes) &&
-      sample_bytes <= ((int64_t)1 << 46),
+  int64_t nsamp;
+  XPIC_CHECK(trace_sample_bytes(n, steps, sample_every, samples != nullptr, &nsamp) >= 0,
     "full_orbit_trace: the sample buffer (48 n steps / sample_every bytes) is too large");
   if (n == 0) return 0;
-  std::vector<double> h;
-  to_soa(p_6, n, h);
-  DevBuf s, sm, tot, mx;
-  XPIC_HIP(hipMalloc(&s.p, 48 * n));
-  if (cn) {
-    XPIC_HIP(hipMalloc(&tot.p, 8 * n)); XPIC_HIP(hipMalloc(&mx.p, 4 * n));
-    XPIC_HIP(hipMemsetAsync(tot.p, 0, 8 * n, ctx->stream));
-    XPIC_HIP(hipMemsetAsync(mx.p, 0, 4 * n, ctx->stream));
-  }
-  if (nsamp > 0) XPIC_HIP(hipMalloc(&sm.p, (size_t)sample_bytes));
-  XPIC_HIP(hipMemcpyAsync(s.p, h.data(), 48 * n, hipMemcpyHostToDevice, ctx->stream));
-  // one launch covers at most kLaunchSteps steps, so no launch runs for seconds however long the trace
-  for (int64_t first = 0; first < steps; first += kLaunchSteps) {
-    const int ns = (int)std::min<int64_t>(kLaunchSteps, steps - first);
-    Timed t(ctx, "fo_trace");
-    if (cn)
-      hipLaunchKernelGGL(k_fo_trace<true>, fo_grid(n), dim3(kBlock), 0, ctx->stream, ctx->g, ctx->field[XPIC_E],
-        ctx->field[XPIC_B], *params, (long)n, (double*)s.p, (long)first, ns, (long)sample_every, (long)nsamp, (double*)sm.p,
-        (long long*)tot.p, (int*)mx.p);
-    else
-      hipLaunchKernelGGL(k_fo_trace<false>, fo_grid(n), dim3(kBlock), 0, ctx->stream, ctx->g, ctx->field[XPIC_E],
-        ctx->field[XPIC_B], *params, (long)n, (double*)s.p, (long)first, ns, (long)sample_every, (long)nsamp, (double*)sm.p,
-        (long long*)nullptr, (int*)nullptr);
-    XPIC_HIP(hipGetLastError());
-  }
-  XPIC_HIP(hipMemcpyAsync(h.data(), s.p, 48 * n, hipMemcpyDeviceToHost, ctx->stream));
-  if (cn) {
-    XPIC_HIP(hipMemcpyAsync(iterations_sum, tot.p, 8 * n, hipMemcpyDeviceToHost, ctx->stream));
-    XPIC_HIP(hipMemcpyAsync(iterations_max, mx.p, 4 * n, hipMemcpyDeviceToHost, ctx->stream));
-  }
-  std::vector<double> hs;
-  if (nsamp > 0) {
-    hs.resize((size_t)6 * n * nsamp);
-    XPIC_HIP(hipMemcpyAsync(hs.data(), sm.p, (size_t)sample_bytes, hipMemcpyDeviceToHost, ctx->stream)); // the samples, once
-  }
-  XPIC_HIP(hipStreamSynchronize(ctx->stream));
+  // a Chin id has no iterations: its launches get null counters, and the caller's are zeroed here
+  XPIC_CALL(batch_trace(ctx, "fo_trace", kLaunchSteps, n, steps, nsamp, cn, p_6, samples, iterations_sum, iterations_max,
+    [&](double* s, long first, int ns, double* sm, long long* it_sum, int* it_max) {
+      hipLaunchKernelGGL(cn ? k_fo_trace<true> : k_fo_trace<false>, lane_grid(n), dim3(kBlock), 0, ctx->stream, ctx->g,
+        ctx->field[XPIC_E], ctx->field[XPIC_B], *params, (long)n, s, first, ns, (long)sample_every, (long)nsamp, sm, it_sum,
+        it_max);
+    }));
   if (!cn) {
     if (iterations_sum) std::fill(iterations_sum, iterations_sum + n, (int64_t)0);
     if (iterations_max) std::fill(iterations_max, iterations_max + n, 0);
   }
-  to_aos(h.data(), n, p_6);
-  for (int64_t k = 0; k < nsamp; ++k) to_aos(hs.data() + (size_t)6 * n * k, n, samples + (size_t)6 * n * k);
   return 0;
 }
 

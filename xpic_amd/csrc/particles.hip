@@ -4,6 +4,7 @@
 #include <cstdio>
 #include <cstdlib>
 
+#include "batch.h"
 #include "common.h"
 #include "device_common.h"
 
@@ -1011,13 +1012,12 @@ int sort_append_host(xpic_ctx* c, Sort& s, int64_t n, const double* pts6, int64_
   XPIC_CHECK(s.n + n <= s.cap, "sort capacity exceeded in add_particles");
   const int64_t before = s.n;
   if (n > 0) {
-    double* tmp = nullptr;
-    XPIC_HIP(hipMalloc(&tmp, sizeof(double) * 6 * n));
-    XPIC_HIP(hipMemcpyAsync(tmp, pts6, sizeof(double) * 6 * n, hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(k_unpack, dim3(pgrid(n)), dim3(kBlock), 0, c->stream, s.d, s.n, n, tmp);
+    DevScratch<double> tmp;
+    XPIC_CALL(tmp.alloc(6 * n));
+    XPIC_CALL(upload(tmp, pts6, 6 * n, c->stream));
+    hipLaunchKernelGGL(k_unpack, dim3(pgrid(n)), dim3(kBlock), 0, c->stream, s.d, s.n, n, tmp.p);
     XPIC_HIP(hipGetLastError());
     XPIC_HIP(hipStreamSynchronize(c->stream));
-    XPIC_HIP(hipFree(tmp));
     s.n += n;
   }
   // add_particle never wraps: points outside the box are dropped (particles.cpp:55-56)
@@ -1030,33 +1030,30 @@ int sort_download(xpic_ctx* c, Sort& s, double* pts6, int32_t* cell_of_out)
 {
   XPIC_CALL(sort_materialize(c, s)); // (a deferred re-binning whose assembly has not run)
   if (s.n == 0) return 0;
-  double* tmp = nullptr;
-  int* tc = nullptr;
-  XPIC_HIP(hipMalloc(&tmp, sizeof(double) * 6 * s.n));
-  XPIC_HIP(hipMalloc(&tc, sizeof(int) * s.n));
-  hipLaunchKernelGGL(k_pack, dim3(pgrid(s.n)), dim3(kBlock), 0, c->stream, c->g, s.d, s.n, tmp, tc);
+  DevScratch<double> tmp;
+  DevScratch<int32_t> tc;
+  XPIC_CALL(tmp.alloc(6 * s.n));
+  XPIC_CALL(tc.alloc(s.n));
+  hipLaunchKernelGGL(k_pack, dim3(pgrid(s.n)), dim3(kBlock), 0, c->stream, c->g, s.d, s.n, tmp.p, tc.p);
   XPIC_HIP(hipGetLastError());
-  XPIC_HIP(hipMemcpyAsync(pts6, tmp, sizeof(double) * 6 * s.n, hipMemcpyDeviceToHost, c->stream));
-  if (cell_of_out) XPIC_HIP(hipMemcpyAsync(cell_of_out, tc, sizeof(int) * s.n, hipMemcpyDeviceToHost, c->stream));
+  XPIC_CALL(download(pts6, tmp, 6 * s.n, c->stream));
+  if (cell_of_out) XPIC_CALL(download(cell_of_out, tc, s.n, c->stream));
   XPIC_HIP(hipStreamSynchronize(c->stream));
-  XPIC_HIP(hipFree(tmp));
-  XPIC_HIP(hipFree(tc));
   return 0;
 }
 
 int sort_occupancy(xpic_ctx* c, Sort& s, int64_t* out8)
 {
   XPIC_CALL(sort_materialize(c, s));
-  unsigned long long* d = nullptr;
+  DevScratch<unsigned long long> d;
   unsigned long long h[8] = {0, 0, 0, 0, 0, ~0ull, 0, 0};
-  XPIC_HIP(hipMalloc(&d, sizeof(h)));
-  XPIC_HIP(hipMemcpyAsync(d, h, sizeof(h), hipMemcpyHostToDevice, c->stream));
+  XPIC_CALL(d.alloc(8));
+  XPIC_CALL(upload(d, h, 8, c->stream));
   const long npen = c->ncell / c->g.nx;
-  hipLaunchKernelGGL(k_occupancy, dim3(pgrid(npen)), dim3(kBlock), 0, c->stream, s.d.cell_start, c->g.nx, npen, s.d.bucket_cap, d);
+  hipLaunchKernelGGL(k_occupancy, dim3(pgrid(npen)), dim3(kBlock), 0, c->stream, s.d.cell_start, c->g.nx, npen, s.d.bucket_cap, d.p);
   XPIC_HIP(hipGetLastError());
-  XPIC_HIP(hipMemcpyAsync(h, d, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+  XPIC_CALL(download(h, d, 8, c->stream));
   XPIC_HIP(hipStreamSynchronize(c->stream));
-  XPIC_HIP(hipFree(d));
   for (int i = 0; i < 7; ++i) out8[i] = (int64_t)h[i];
   out8[7] = s.d.bucket_cap;
   return 0;
