@@ -348,6 +348,13 @@ int xpic_inject_particles(xpic_ctx* ctx, int ionized, int ejected, const xpic_in
  * denominator_tolerance, at the positions it writes: Bx at (x, y + 1/2, z + 1/2) d, By at (x + 1/2, y, z + 1/2) d,
  * Bz at (x + 1/2, y + 1/2, z) d.  A Bx or By node on the axis (r = 0) is 0 / 0 there as in the reference: NaN. */
 int xpic_set_coils_field(xpic_ctx* ctx, int field, int ncoils, const double* coils3);
+/* SetApproximateMirrorField::operator() (src/commands/set_magnetic_field.cpp:142-191) as written: field += the paraxial
+ * field of two coils of radius R and current I at z = -D / 2 and z = +D / 2, with B0(z, s) = I R^2 / 2 /
+ * (R^2 + (z + s D / 2)^2)^1.5 and B1(z, s) = (z + s D / 2) / (R^2 + (z + s D / 2)^2) for s = +1, -1.  The X component
+ * takes BOTH transverse terms, B0 B1 1.5 (x dx - geom_x / 2) and B0 B1 1.5 (y dy - geom_y / 2), at (z + 1/2) dz; the Y
+ * component takes nothing; the Z component takes B0 at z dz.  (The reference's JSON builder does not offer this setter,
+ * set_magnetic_field_builder.cpp:13-17; neither does the host executable.) */
+int xpic_set_mirror_field(xpic_ctx* ctx, int field, double D, double R, double I);
 /* ChargeConservation (charge_conservation.cpp:117-171): xpic_charge_collect() = initialize(); then once per step
  * xpic_charge_columns(): out = {N1dQ_0, N2dQ_0, ..., N1dQ_tot, N2dQ_tot} of (rho_new - rho_old)/dt + div(-) J.
  * Uses the scratch vectors XPIC_W0..W2. */
@@ -440,6 +447,41 @@ int xpic_full_orbit_push(xpic_ctx* ctx, int64_t n, const xpic_fo_params* params,
  * (XPIC_FO_CN: required; otherwise optional and zeroed): sum and maximum of the particle's iteration counts. */
 int xpic_full_orbit_trace(xpic_ctx* ctx, int64_t n, const xpic_fo_params* params, int64_t steps, int64_t sample_every,
   double* p_6, double* samples, int64_t* iterations_sum, int* iterations_max);
+
+/* ---- open-trap traces: the two traces above with RemoveParticles' region rule inside the step loop
+ * (RemoveParticles::execute, src/commands/remove_particles.cpp:22-38, applied to one particle).  At the top of every step
+ * the corner of the particle's cell, (floor(x / dx) dx, floor(y / dy) dy, floor(z / dz) dz) -- FLOOR_STEP as in
+ * Particles::add_particle (src/interfaces/particles.cpp:47-67) -- of its UNFOLDED position is tested with WithinBox /
+ * WithinCylinder (src/utils/geometries.cpp:3-19), the test of xpic_remove_particles.  A particle that fails is removed:
+ * exit_step[q] = step0 + the steps it has completed in this call, its state stays what it was, it takes no further step
+ * and adds nothing to the iteration counters.  Positions are not folded, so a particle that runs out of the box fails a
+ * box that lies inside the domain: the open end.  The state after the last step is not tested (the next call's first step
+ * tests it), so a call of s1 + s2 steps equals a call of s1 steps followed by one of s2 steps with step0 advanced by s1
+ * and the first call's exit_step, bit for bit.  A particle that stays runs the step functions of the closed trace: its
+ * result is the closed trace's, bit for bit.
+ * exit_step (required, in and out, one entry per particle): -1 alive; k >= 0 removed after completing k steps in total; a
+ * particle that enters with k >= 0 is returned untouched.  alive (or NULL; needs sample_every >= 1): alive[k] = particles
+ * still alive when sample k is taken, k < steps / sample_every.  *removed (required): particles removed by this call.  In
+ * samples, a removed particle's state is repeated in every later row.  Iteration counters as in the closed traces.
+ * compact: what happens to the list of live particles between the launches (each of at most XPIC_FO_LAUNCH_STEPS /
+ * XPIC_DK_LAUNCH_STEPS steps).  The results are bit-identical for all three values. */
+enum xpic_trace_compact {
+  XPIC_COMPACT_AUTO = 0,  /* rebuild the list, in order, when fewer than half of its entries are alive */
+  XPIC_COMPACT_NEVER = 1, /* every launch covers all n particles */
+  XPIC_COMPACT_ALWAYS = 2 /* rebuild the list after every launch that removed a particle */
+};
+typedef struct xpic_trace_region {
+  int32_t geometry; /* XPIC_GEOM_BOX, XPIC_GEOM_CYLINDER */
+  int32_t compact;  /* enum xpic_trace_compact */
+  double geom[7];   /* as xpic_remove_particles': {min xyz, max xyz} (box), {center xyz, radius, height} (cylinder) */
+  int64_t step0;    /* steps this batch has been traced already (>= 0) */
+} xpic_trace_region;
+int xpic_full_orbit_trace_open(xpic_ctx* ctx, int64_t n, const xpic_fo_params* params, int64_t steps, int64_t sample_every,
+  double* p_6, double* samples, int64_t* iterations_sum, int* iterations_max, const xpic_trace_region* region,
+  int64_t* exit_step, int64_t* alive, int64_t* removed);
+int xpic_drift_kinetic_trace_open(xpic_ctx* ctx, int64_t n, const xpic_dk_params* params, int gradB_field, int64_t steps,
+  int64_t sample_every, double* state_6, double* samples, int64_t* iterations_total, int* iterations_max,
+  const xpic_trace_region* region, int64_t* exit_step, int64_t* alive, int64_t* removed);
 
 /* ---- z-slab decomposition (DMDA da_processors_z = nranks; src/utils/world.cpp:36-38).  A context created with
  * nranks > 1 owns planes [rank*nz/nranks, (rank+1)*nz/nranks) and must be given a communicator before any

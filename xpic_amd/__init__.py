@@ -4,6 +4,7 @@ This package is a thin ctypes view of the C ABI in include/xpic_hip.h (xpic_amd/
 xpic_amd/csrc/*.hip by `make` / `__graft_entry__.build()`).  There is NO CPU fallback: if the shared library
 or a HIP device is missing, every entry point raises.
 """
+import collections
 import ctypes as C
 import os
 
@@ -29,9 +30,10 @@ SYMBOLS = [
     "xpic_ecsimcorr_first_push", "xpic_ecsimcorr_second_push", "xpic_ecsimcorr_final_update",
     "xpic_calculate_energy", "xpic_ecsimcorr_scalars", "xpic_solve", "xpic_set_tolerances", "xpic_set_preconditioner", "xpic_set_overlap", "xpic_comm_stats", "xpic_set_fill_kernel", "xpic_set_fused_rebin", "xpic_get_fill_variant", "xpic_debug_set", "xpic_step",
     "xpic_energy", "xpic_momentum", "xpic_charge_density", "xpic_moment_density", "xpic_moment", "xpic_velocity_distribution", "xpic_remove_particles", "xpic_fields_damping",
-    "xpic_inject_particles", "xpic_set_coils_field", "xpic_cell_traversal", "xpic_implicit_esirkepov_interpolate",
+    "xpic_inject_particles", "xpic_set_coils_field", "xpic_set_mirror_field", "xpic_cell_traversal", "xpic_implicit_esirkepov_interpolate",
     "xpic_implicit_esirkepov_decompose", "xpic_drift_kinetic_interpolate", "xpic_drift_kinetic_push",
-    "xpic_drift_kinetic_trace", "xpic_full_orbit_push", "xpic_full_orbit_trace", "xpic_charge_collect", "xpic_charge_columns", "xpic_comm_rccl_unique_id", "xpic_comm_init_rccl", "xpic_comm_init_callbacks", "xpic_comm_size", "xpic_comm_peer_export", "xpic_comm_peer_import",
+    "xpic_drift_kinetic_trace", "xpic_full_orbit_push", "xpic_full_orbit_trace", "xpic_full_orbit_trace_open",
+    "xpic_drift_kinetic_trace_open", "xpic_charge_collect", "xpic_charge_columns", "xpic_comm_rccl_unique_id", "xpic_comm_init_rccl", "xpic_comm_init_callbacks", "xpic_comm_size", "xpic_comm_peer_export", "xpic_comm_peer_import",
     "xpic_profile_enable", "xpic_profile_reset", "xpic_profile_get", "xpic_probe_copy_bandwidth",
 ]
 
@@ -127,6 +129,21 @@ FO_SCHEMES = {name: i for i, name in enumerate(
      "EB2B", "CN"])}
 FO_LAUNCH_STEPS = 64  # include/xpic_hip.h: XPIC_FO_LAUNCH_STEPS
 FO_MAXIT = 64         # include/xpic_hip.h: XPIC_FO_MAXIT
+
+
+class TraceRegion(C.Structure):  # include/xpic_hip.h: xpic_trace_region
+    _fields_ = [("geometry", C.c_int32), ("compact", C.c_int32), ("geom", C.c_double * 7), ("step0", C.c_int64)]
+
+
+COMPACT = {"auto": 0, "never": 1, "always": 2}  # include/xpic_hip.h: enum xpic_trace_compact
+
+
+class OpenTrace(collections.namedtuple("OpenTrace", "state samples exit_step alive removed iterations_sum iterations_max")):
+    """What Context.full_orbit_trace_open / drift_kinetic_trace_open return: the state [n][6]; samples
+    [steps // sample_every][n][6] and alive [steps // sample_every] (None without sample_every); exit_step [n] (-1: alive,
+    k: removed after completing k steps in total); removed, the particles this call removed; the iteration counters of the
+    closed traces."""
+    __slots__ = ()
 
 
 def guiding_centre(points6, B3, mp, qm, *, orbit_centre=False):
@@ -551,6 +568,11 @@ class Context:
         c3 = np.ascontiguousarray(np.asarray(coils, dtype=np.float64).reshape(-1, 3))
         self._ck(self.L.xpic_set_coils_field(self.h, field, int(c3.shape[0]), _dp(c3)))
 
+    def set_mirror_field(self, D, R, I, field=B0):
+        """SetApproximateMirrorField: field += the paraxial field of two coils of radius R and current I at z = -D / 2 and
+        z = +D / 2, as the reference writes it (both transverse terms into the X component)"""
+        self._ck(self.L.xpic_set_mirror_field(self.h, field, C.c_double(D), C.c_double(R), C.c_double(I)))
+
     def cell_traversal(self, end, start, max_pts=8):
         end, start = np.ascontiguousarray(end, dtype=np.float64), np.ascontiguousarray(start, dtype=np.float64)
         n = end.shape[0]
@@ -641,6 +663,50 @@ class Context:
                                               C.c_int64(int(sample_every)), _dp(state), _dp(samples) if sample_every else None,
                                               tot.ctypes.data_as(C.POINTER(C.c_int64)), mx.ctypes.data_as(C.POINTER(C.c_int))))
         return state, samples, tot, mx
+
+    # ---- open-trap traces (include/xpic_hip.h: xpic_trace_region): the traces above with RemoveParticles' corner rule at
+    # the top of every step.  region: a geometry dict as remove_particles'; exit_step: the array a previous call returned
+    # (None: everybody alive), step0: the steps that call and its predecessors made; compact: a key of COMPACT or its number
+    # ("never" by default: at 2^20 particles rebuilding the list gained 1.5 - 3.4 %, inside the +- 4 % box-to-box spread --
+    # DESIGN.md 5j, "Measured")
+    # keep_samples=False: alive only, no sample rows (samples is None)
+    def _open_args(self, state, steps, sample_every, region, exit_step, step0, compact, keep_samples):
+        state = np.array(state, dtype=np.float64).reshape(-1, 6)  # a copy: the call works in place
+        n = state.shape[0]
+        nsamp = max(int(steps), 0) // int(sample_every) if sample_every else 0
+        samples = np.zeros((nsamp, n, 6)) if sample_every and keep_samples else None
+        alive = np.zeros(nsamp, dtype=np.int64) if sample_every else None
+        ex = np.full(n, -1, dtype=np.int64) if exit_step is None else np.array(exit_step, dtype=np.int64).reshape(n)
+        kind, gp = _geom7(region)
+        reg = TraceRegion(kind, int(COMPACT.get(compact, compact)), (C.c_double * 7)(*gp[:7]), int(step0))
+        return state, samples, alive, ex, reg, np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int32)
+
+    def full_orbit_trace_open(self, state, steps, scheme, qm, dt, region, sample_every=0, exit_step=None, step0=0,
+                              compact="never", keep_samples=True, atol=1e-7, rtol=1e-7, maxit=30):
+        """full_orbit_trace in an open system -> OpenTrace"""
+        state, samples, alive, ex, reg, tot, mx = self._open_args(state, steps, sample_every, region, exit_step, step0, compact,
+                                                                      keep_samples)
+        P = self._fo_params(scheme, qm, dt, atol, rtol, maxit)
+        removed, i64 = C.c_int64(), C.POINTER(C.c_int64)
+        self._ck(self.L.xpic_full_orbit_trace_open(
+            self.h, C.c_int64(state.shape[0]), C.byref(P), C.c_int64(int(steps)), C.c_int64(int(sample_every)), _dp(state),
+            None if samples is None else _dp(samples), tot.ctypes.data_as(i64), mx.ctypes.data_as(C.POINTER(C.c_int)),
+            C.byref(reg), ex.ctypes.data_as(i64), alive.ctypes.data_as(i64) if sample_every else None, C.byref(removed)))
+        return OpenTrace(state, samples, ex, alive, removed.value, tot, mx)
+
+    def drift_kinetic_trace_open(self, state, steps, qm, mp, dt, region, gradB_field=None, sample_every=0, exit_step=None,
+                                 step0=0, compact="never", keep_samples=True, eps=1e-12, delta=1e-12, maxit=30):
+        """drift_kinetic_trace in an open system -> OpenTrace"""
+        state, samples, alive, ex, reg, tot, mx = self._open_args(state, steps, sample_every, region, exit_step, step0, compact,
+                                                                      keep_samples)
+        P = self._dk_params(qm, mp, dt, eps, delta, maxit)
+        removed, i64 = C.c_int64(), C.POINTER(C.c_int64)
+        self._ck(self.L.xpic_drift_kinetic_trace_open(
+            self.h, C.c_int64(state.shape[0]), C.byref(P), -1 if gradB_field is None else int(gradB_field),
+            C.c_int64(int(steps)), C.c_int64(int(sample_every)), _dp(state), None if samples is None else _dp(samples),
+            tot.ctypes.data_as(i64), mx.ctypes.data_as(C.POINTER(C.c_int)), C.byref(reg), ex.ctypes.data_as(i64),
+            alive.ctypes.data_as(i64) if sample_every else None, C.byref(removed)))
+        return OpenTrace(state, samples, ex, alive, removed.value, tot, mx)
 
     def charge_collect(self):
         self._ck(self.L.xpic_charge_collect(self.h))

@@ -938,6 +938,12 @@ int xpic_set_coils_field(xpic_ctx* ctx, int field, int ncoils, const double* coi
   return set_coils_field(ctx, ctx->field[field], ncoils, coils3);
 }
 
+int xpic_set_mirror_field(xpic_ctx* ctx, int field, double D, double R, double I)
+{ // SetApproximateMirrorField::operator(), set_magnetic_field.cpp:142-191
+  CTX_CHECK(ctx); FIELD_CHECK(field);
+  return set_mirror_field(ctx, ctx->field[field], D, R, I);
+}
+
 int xpic_charge_collect(xpic_ctx* ctx) // ChargeConservation::initialize, charge_conservation.cpp:117-123
 {
   CTX_CHECK(ctx);

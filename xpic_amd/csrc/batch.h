@@ -1,5 +1,7 @@
 // batch.h -- the host side that the batch particle calls share (eccapfim.hip, drift_kinetic.hip, full_orbit.hip): host
 // arrays of particles are staged on the device, a kernel runs one lane per particle, the results are copied back.
+// batch_trace_open is batch_trace for the open traces (trace_open.h, trace_open.hip): exit steps, alive counts, and the
+// list of live particles between launches.
 // DevScratch also owns every other device buffer that lives for one call (fields.hip, particles.hip, commands.hip,
 // api.hip).  Host code only: no kernel or device function is declared here.
 #pragma once
@@ -36,6 +38,29 @@ inline int64_t trace_sample_bytes(int64_t n, int64_t steps, int64_t sample_every
   const bool fits = !__builtin_mul_overflow((int64_t)(6 * sizeof(double)), n, &row_bytes) &&
     !__builtin_mul_overflow(row_bytes, *nsamp, &bytes) && bytes <= ((int64_t)1 << 46);
   return fits ? bytes : -1;
+}
+
+// An open trace (batch_trace_open): whether the list of `listed` entries, `live` of them alive, is rebuilt before the next
+// launch.  policy: enum xpic_trace_compact (0: when fewer than half are alive, 1: never, 2: whenever one is not).
+inline bool trace_compacts(int policy, int64_t live, int64_t listed)
+{
+  if (policy == 1 || live >= listed) return false;
+  return policy == 2 || 2 * live < listed;
+}
+
+// An open trace's sample rows [nsamp][n][6] on the host: row k is the state after step (k + 1) sample_every of the call.
+// The kernels write a particle's rows only while it steps; here a particle that is not alive at the end (exit_out >= 0)
+// gets its final state, which is the state it was removed with, in every row behind its last step: behind step
+// exit_out - step0 when this call removed it, in every row when it entered removed (exit_in >= 0).
+inline void fill_frozen_samples(int64_t n, int64_t nsamp, int64_t sample_every, int64_t step0, const int64_t* exit_in,
+  const int64_t* exit_out, const double* state_6, double* samples)
+{
+  for (int64_t q = 0; q < n; ++q) {
+    if (exit_out[q] < 0) continue;
+    const int64_t done = exit_in[q] >= 0 ? 0 : exit_out[q] - step0;
+    for (int64_t k = done > 0 ? done / sample_every : 0; k < nsamp; ++k)
+      for (int a = 0; a < 6; ++a) samples[((size_t)k * n + q) * 6 + a] = state_6[6 * q + a];
+  }
 }
 
 }  // namespace xpic
@@ -149,6 +174,97 @@ int batch_trace(xpic_ctx* c, const char* label, int launch_steps, int64_t n, int
   XPIC_HIP(hipStreamSynchronize(c->stream));
   to_aos(h.data(), n, state_6);
   for (int64_t k = 0; k < nsamp; ++k) to_aos(hs.data() + row * k, n, samples + row * k);
+  return 0;
+}
+
+// trace_open.hip: out[0 .. cap) = the entries of list[0 .. m) (null: 0 .. m - 1) whose exit_step is < 0, in their order;
+// blk and off: one element per workgroup of kLaneBlock entries.  Timed under `label`.
+int live_compact(xpic_ctx* c, const char* label, const int64_t* exit_step, const int64_t* list, int64_t m, int64_t cap,
+  int64_t* out, double* blk, int64_t* off);
+
+// batch_trace with the region rule of an open trace (include/xpic_hip.h: xpic_trace_region).  exit_step
+// [n] in and out, alive [nsamp] or null, *removed as the entry points document them; nsamp counts the rows of samples
+// and of alive, either of which may be null.  launch(s, list, m, first, nsteps, samples, it_sum, it_max, exit_step,
+// alive, removed) starts the kernel for steps first + 1 .. first + nsteps over the m entries of list (null: the particles
+// 0 .. m - 1); the kernel adds to alive[row] and to *removed (device, zeroed here).  After every launch the count removed
+// so far comes back (8 bytes), so the host knows how many entries are alive: when none is, the remaining launches are
+// skipped, and by `policy` (trace_compacts) the list is rebuilt for the next launch, timed under `compact_label`.
+// The sample rows behind a removed particle's last step are filled here, on the host, from the final state
+// (fill_frozen_samples): a launch no longer covers a particle that compaction has dropped.
+template <class Launch>
+int batch_trace_open(xpic_ctx* c, const char* label, const char* compact_label, int launch_steps, int64_t n, int64_t steps,
+  int64_t sample_every, int64_t nsamp, bool counters, int policy, int64_t step0, double* state_6, double* samples,
+  int64_t* it_sum, int* it_max, int64_t* exit_step, int64_t* alive, int64_t* removed, Launch launch)
+{
+  const size_t row = (size_t)6 * n; // doubles of one state
+  std::vector<double> h, hs;
+  to_soa(state_6, n, h);
+  const std::vector<int64_t> exit_in(exit_step, exit_step + n);
+  int64_t live = 0;
+  for (int64_t q = 0; q < n; ++q) live += exit_in[q] < 0;
+  DevScratch<double> s, sm, blk;
+  DevScratch<int64_t> tot, ex, al, rm, off, lst[2];
+  DevScratch<int> mx;
+  XPIC_CALL(s.alloc(row)); XPIC_CALL(ex.alloc(n)); XPIC_CALL(rm.alloc(1));
+  XPIC_CALL(zero(rm, 1, c->stream));
+  if (counters) {
+    XPIC_CALL(tot.alloc(n)); XPIC_CALL(mx.alloc(n));
+    XPIC_CALL(zero(tot, n, c->stream)); XPIC_CALL(zero(mx, n, c->stream));
+  }
+  if (samples && nsamp > 0) XPIC_CALL(sm.alloc(row * nsamp));
+  if (alive && nsamp > 0) {
+    XPIC_CALL(al.alloc(nsamp));
+    XPIC_CALL(zero(al, nsamp, c->stream));
+  }
+  XPIC_CALL(upload(s, h.data(), row, c->stream));
+  XPIC_CALL(upload(ex, exit_in.data(), n, c->stream));
+  const int64_t* list = nullptr; // the entries the next launch covers: null = every particle
+  int64_t listed = n, gone = 0;
+  int next = 0;                  // the buffer the next compaction writes
+  for (int64_t first = 0; first < steps && live > 0; first += launch_steps) {
+    const int ns = (int)std::min<int64_t>(launch_steps, steps - first);
+    {
+      Timed t(c, label);
+      launch(s.p, list, (long)listed, (long)first, ns, sm.p, (long long*)tot.p, mx.p, (long long*)ex.p,
+        (unsigned long long*)al.p, (unsigned long long*)rm.p);
+      XPIC_HIP(hipGetLastError());
+    }
+    int64_t g = 0;
+    XPIC_CALL(download(&g, rm, 1, c->stream));
+    XPIC_HIP(hipStreamSynchronize(c->stream));
+    live -= g - gone;
+    gone = g;
+    if (first + launch_steps < steps && live > 0 && trace_compacts(policy, live, listed)) {
+      if (!blk.p) { // (the list only shrinks: the first compaction's workgroup count bounds the later ones)
+        const size_t nb = lane_grid(listed).x;
+        XPIC_CALL(blk.alloc(nb)); XPIC_CALL(off.alloc(nb));
+      }
+      // (so do the live counts: buffer 0 is as long as the first list, buffer 1 as the second, and they alternate)
+      if (!lst[next].p) XPIC_CALL(lst[next].alloc(live));
+      XPIC_CALL(live_compact(c, compact_label, ex.p, list, listed, live, lst[next].p, blk.p, off.p));
+      list = lst[next].p;
+      listed = live;
+      next ^= 1;
+    }
+  }
+  XPIC_CALL(download(h.data(), s, row, c->stream));
+  XPIC_CALL(download(exit_step, ex, n, c->stream));
+  if (counters) {
+    XPIC_CALL(download(it_sum, tot, n, c->stream));
+    XPIC_CALL(download(it_max, mx, n, c->stream));
+  }
+  if (sm.p) {
+    hs.resize(row * nsamp);
+    XPIC_CALL(download(hs.data(), sm, row * nsamp, c->stream)); // the samples, once
+  }
+  if (al.p) XPIC_CALL(download(alive, al, nsamp, c->stream));
+  XPIC_HIP(hipStreamSynchronize(c->stream));
+  to_aos(h.data(), n, state_6);
+  if (sm.p) {
+    for (int64_t k = 0; k < nsamp; ++k) to_aos(hs.data() + row * k, n, samples + row * k);
+    fill_frozen_samples(n, nsamp, sample_every, step0, exit_in.data(), exit_step, state_6, samples);
+  }
+  *removed = gone;
   return 0;
 }
 

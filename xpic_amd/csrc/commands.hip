@@ -1,5 +1,6 @@
 // commands.hip -- the per-step commands of an open system on the device (the reference's src/commands/): RemoveParticles,
-// InjectParticles, FieldsDamping, and the SetCoilsField setter of SetMagneticField.
+// InjectParticles, FieldsDamping, and the SetCoilsField and SetApproximateMirrorField setters of SetMagneticField
+// (DESIGN.md 5g, 5j).
 //
 // Removal and injection change a sort's storage through ONE cell-wise rebuild: the new cell counts (the old ones, minus the
 // emptied cells, plus the binned new records) are scanned into a new cell_start, every surviving record is moved once to
@@ -332,6 +333,49 @@ __global__ void __launch_bounds__(kBlock) k_coils(GridDev g, double* F, const do
   F[2 * g.cstride + nd] += coils_Bz(cs, coils, nc, sz, r);
 }
 
+// ---- SetApproximateMirrorField ---------------------------------------------------------------------------------------
+// get_B0 / get_B1 (set_magnetic_field.cpp:183-191); sign is a PetscReal there
+__device__ inline double mirror_B0(double z, double sign, double D, double R, double I)
+{
+  const double zc = z + 0.5 * sign * D;
+  return 0.5 * I * (R * R) / pow(R * R + zc * zc, 1.5);
+}
+__device__ inline double mirror_B1(double z, double sign, double D, double R)
+{
+  const double zc = z + 0.5 * sign * D;
+  return zc / (R * R + zc * zc);
+}
+
+// SetApproximateMirrorField::operator() (:142-181) as written, one thread per owned node: both transverse terms go to
+// the X component, at (z + 1/2) dz; Bz at z dz; the Y component is left alone
+__global__ void __launch_bounds__(kBlock) k_mirror(GridDev g, double* F, double D, double R, double I)
+{
+  const long i = (long)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= g.nown) return;
+  int x, y, zl;
+  cell_xyz(g, i, &x, &y, &zl);
+  const int z = g.z0 + zl;
+  const long nd = g.node(x, y, g.wz(zl));
+  double sz, sm;
+  double fx = F[nd], fz = F[2 * g.cstride + nd];
+
+  sz = (z + 0.5) * g.dz;
+  sm = 1.5 * (x * g.dx - 0.5 * g.Lx);
+  fx += mirror_B0(sz, +1.0, D, R, I) * sm * mirror_B1(sz, +1.0, D, R);
+  fx += mirror_B0(sz, -1.0, D, R, I) * sm * mirror_B1(sz, -1.0, D, R);
+
+  sz = (z + 0.5) * g.dz;
+  sm = 1.5 * (y * g.dy - 0.5 * g.Ly);
+  fx += mirror_B0(sz, +1.0, D, R, I) * sm * mirror_B1(sz, +1.0, D, R);
+  fx += mirror_B0(sz, -1.0, D, R, I) * sm * mirror_B1(sz, -1.0, D, R);
+
+  sz = z * g.dz;
+  fz += mirror_B0(sz, +1.0, D, R, I);
+  fz += mirror_B0(sz, -1.0, D, R, I);
+  F[nd] = fx;
+  F[2 * g.cstride + nd] = fz;
+}
+
 int cmd_geom(int geometry, const double* geom, CmdGeom* G)
 {
   XPIC_CHECK(geom, "null geometry");
@@ -520,6 +564,15 @@ int set_coils_field(xpic_ctx* c, double* F, int ncoils, const double* coils3)
     hipLaunchKernelGGL(k_coils, dim3(cgrid(i1 - i0)), dim3(kBlock), 0, c->stream, c->g, F, d.p, d.p + kCoilN, ncoils, i0, i1);
     XPIC_HIP(hipGetLastError());
   }
+  XPIC_HIP(hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+int set_mirror_field(xpic_ctx* c, double* F, double D, double R, double I)
+{
+  Timed t(c, "cmd_mirror");
+  hipLaunchKernelGGL(k_mirror, dim3(cgrid(c->g.nown)), dim3(kBlock), 0, c->stream, c->g, F, D, R, I);
+  XPIC_HIP(hipGetLastError());
   XPIC_HIP(hipStreamSynchronize(c->stream));
   return 0;
 }

@@ -377,6 +377,7 @@ int fields_damping(xpic_ctx* c, double* E, double* B, const double* B0, int geom
 int inject_particles(xpic_ctx* c, Sort& si, Sort& se, const xpic_inject_params& p, int64_t pairs, int64_t step,
   int64_t* added, double* energy2);
 int set_coils_field(xpic_ctx* c, double* F, int ncoils, const double* coils3);
+int set_mirror_field(xpic_ctx* c, double* F, double D, double R, double I);
 
 // ecsim.hip
 int ecsim_fill_sort(xpic_ctx* c, Sort& s, const double* B, double* currI_sort, double* matL, bool first_sort, bool post_ghost_rows);

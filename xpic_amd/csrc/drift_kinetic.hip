@@ -12,6 +12,7 @@
 #include "common.h"
 #include "device_common.h"
 #include "ie_shape.h"
+#include "trace_open.h"
 
 // The pusher's own expressions are contracted per source expression only (not across statements), so k_dk_push and
 // k_dk_trace, which inline the same dk_process, round identically whatever surrounds the call.  (The segment shape in
@@ -277,6 +278,47 @@ __global__ void __launch_bounds__(kBlock) k_dk_trace(GridDev g, const double* __
   it_max[q] = most;
 }
 
+// k_dk_trace with the region rule of an open trace (trace_open.h) over the m entries of `list` (null: the
+// particles 0 .. m - 1): as k_fo_trace_open, the step being dk_process as in k_dk_push and k_dk_trace.
+static_assert(XPIC_DK_LAUNCH_STEPS <= kOpenRows, "open_tally holds one row per step of a launch");
+template <bool GRAD>
+__global__ void __launch_bounds__(kBlock) k_dk_trace_open(GridDev g, const double* __restrict__ E,
+  const double* __restrict__ B, const double* __restrict__ gB, xpic_dk_params P, OpenRegion R, long n, double* __restrict__ s,
+  const long long* __restrict__ list, long m, long first, int nsteps, long sample_every, long nsamp,
+  double* __restrict__ samples, long long* __restrict__ it_total, int* __restrict__ it_max, long long* __restrict__ exit_step,
+  unsigned long long* alive, unsigned long long* removed)
+{
+  const long j = (long)blockIdx.x * kBlock + threadIdx.x;
+  const long q = j < m ? (list ? (long)list[j] : j) : -1;
+  const bool live = q >= 0 && q < n && exit_step[q] < 0;
+  const int ns = nsteps < XPIC_DK_LAUNCH_STEPS ? nsteps : XPIC_DK_LAUNCH_STEPS;
+  int done = 0;
+  bool gone = false;
+  if (live) {
+    DKPoint p0, pn;
+    dk_load(s, n, q, pn);
+    long long total = it_total[q];
+    int most = it_max[q];
+    for (; done < ns; ++done) {
+      if (!open_keep(g, R, pn.r)) { gone = true; break; }
+      p0 = pn;
+      const int it = dk_process<GRAD>(g, E, B, gB, P, p0, pn);
+      total += it;
+      most = it > most ? it : most;
+      const long step = first + done + 1;
+      if (samples && step % sample_every == 0) {
+        const long row = step / sample_every - 1;
+        if (row < nsamp) dk_store(samples + row * 6 * n, n, q, pn);
+      }
+    }
+    dk_store(s, n, q, pn);
+    it_total[q] = total;
+    it_max[q] = most;
+    if (gone) exit_step[q] = R.step0 + first + done;
+  }
+  open_tally<kBlock>(live, gone, first + done, first, ns, sample_every, nsamp, alive, removed);
+}
+
 // the checks the three calls share; *gradB: the vector of gradB_field, null for -1 (grad B = 0)
 int dk_check(xpic_ctx* ctx, int64_t n, int gradB_field, const double** gradB)
 {
@@ -370,6 +412,38 @@ int xpic_drift_kinetic_trace(xpic_ctx* ctx, int64_t n, const xpic_dk_params* par
     iterations_max, [&](double* s, long first, int ns, double* sm, long long* it_sum, int* it_max) {
       hipLaunchKernelGGL(gradB ? k_dk_trace<true> : k_dk_trace<false>, lane_grid(n), dim3(kBlock), 0, ctx->stream, ctx->g,
         ctx->field[XPIC_E], ctx->field[XPIC_B], gradB, *params, (long)n, s, first, ns, (long)sample_every, sm, it_sum, it_max);
+    });
+}
+
+int xpic_drift_kinetic_trace_open(xpic_ctx* ctx, int64_t n, const xpic_dk_params* params, int gradB_field, int64_t steps,
+  int64_t sample_every, double* state_6, double* samples, int64_t* iterations_total, int* iterations_max,
+  const xpic_trace_region* region, int64_t* exit_step, int64_t* alive, int64_t* removed)
+{ // xpic_drift_kinetic_trace with RemoveParticles::execute (remove_particles.cpp:22-38) at the top of every step
+  const double* gradB;
+  XPIC_CALL(dk_check(ctx, n, gradB_field, &gradB));
+  XPIC_CALL(dk_check_params(params));
+  OpenRegion R;
+  XPIC_CALL(open_region("drift_kinetic_trace_open", region, &R));
+  XPIC_CHECK(steps >= 0, "drift_kinetic_trace_open: steps is negative");
+  XPIC_CHECK((!samples && !alive) || sample_every >= 1,
+    "drift_kinetic_trace_open: sample_every must be >= 1 when samples or alive are asked for");
+  XPIC_CHECK(state_6, "drift_kinetic_trace_open: state_6 is null");
+  XPIC_CHECK(exit_step, "drift_kinetic_trace_open: exit_step is null");
+  XPIC_CHECK(removed, "drift_kinetic_trace_open: removed is null");
+  XPIC_CHECK(iterations_total, "drift_kinetic_trace_open: iterations_total is null");
+  XPIC_CHECK(iterations_max, "drift_kinetic_trace_open: iterations_max is null");
+  int64_t nsamp;
+  XPIC_CHECK(trace_sample_bytes(samples ? n : 0, steps, sample_every, samples || alive, &nsamp) >= 0,
+    "drift_kinetic_trace_open: the sample buffer (48 n steps / sample_every bytes) is too large");
+  *removed = 0;
+  if (n == 0 || steps == 0) return 0;
+  return batch_trace_open(ctx, "dk_trace_open", "dk_trace_open_compact", XPIC_DK_LAUNCH_STEPS, n, steps, sample_every, nsamp,
+    true, region->compact, region->step0, state_6, samples, iterations_total, iterations_max, exit_step, alive, removed,
+    [&](double* s, const int64_t* list, long m, long first, int ns, double* sm, long long* it_sum, int* it_max, long long* ex,
+      unsigned long long* al, unsigned long long* rm) {
+      hipLaunchKernelGGL(gradB ? k_dk_trace_open<true> : k_dk_trace_open<false>, lane_grid(m), dim3(kBlock), 0, ctx->stream,
+        ctx->g, ctx->field[XPIC_E], ctx->field[XPIC_B], gradB, *params, R, (long)n, s, (const long long*)list, m, first, ns,
+        (long)sample_every, (long)nsamp, sm, it_sum, it_max, ex, al, rm);
     });
 }
 

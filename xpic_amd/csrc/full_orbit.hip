@@ -18,6 +18,7 @@
 #include "common.h"
 #include "device_common.h"
 #include "ie_shape.h"
+#include "trace_open.h"
 
 // contracted per source expression only (not across statements), so k_fo_push and k_fo_trace, which inline the same
 // fo_step / fo_cn_process, round identically whatever surrounds the call
@@ -99,6 +100,47 @@ __global__ void __launch_bounds__(kBlock) k_fo_trace(GridDev g, const double* __
   if (CN) { it_sum[q] = total; it_max[q] = most; }
 }
 
+// k_fo_trace with the region rule of an open trace (trace_open.h) over the m entries of `list` (null:
+// the particles 0 .. m - 1).  A lane whose particle is alive tests the corner of its cell at the top of every step and
+// leaves the loop when the test fails: exit_step = step0 + the steps completed, the state as it was.  The step itself is
+// fo_one, as in k_fo_push and k_fo_trace.  Every thread reaches open_tally.
+static_assert(kLaunchSteps <= kOpenRows, "open_tally holds one row per step of a launch");
+template <bool CN>
+__global__ void __launch_bounds__(kBlock) k_fo_trace_open(GridDev g, const double* __restrict__ E,
+  const double* __restrict__ B, xpic_fo_params P, OpenRegion R, long n, double* __restrict__ s,
+  const long long* __restrict__ list, long m, long first, int nsteps, long sample_every, long nsamp,
+  double* __restrict__ samples, long long* __restrict__ it_sum, int* __restrict__ it_max, long long* __restrict__ exit_step,
+  unsigned long long* alive, unsigned long long* removed)
+{
+  const long j = (long)blockIdx.x * kBlock + threadIdx.x;
+  const long q = j < m ? (list ? (long)list[j] : j) : -1;
+  const bool live = q >= 0 && q < n && exit_step[q] < 0;
+  const int ns = nsteps < kLaunchSteps ? nsteps : kLaunchSteps;
+  int done = 0;
+  bool gone = false;
+  if (live) {
+    FOPoint pn;
+    fo_load(s, n, q, pn);
+    long long total = CN ? it_sum[q] : 0;
+    int most = CN ? it_max[q] : 0;
+    for (; done < ns; ++done) {
+      if (!open_keep(g, R, pn.r)) { gone = true; break; }
+      const int it = fo_one<CN>(g, E, B, P, pn);
+      total += it;
+      most = it > most ? it : most;
+      const long step = first + done + 1;
+      if (samples && step % sample_every == 0) {
+        const long row = step / sample_every - 1;
+        if (row < nsamp) fo_store(samples + row * 6 * n, n, q, pn);
+      }
+    }
+    fo_store(s, n, q, pn);
+    if (CN) { it_sum[q] = total; it_max[q] = most; }
+    if (gone) exit_step[q] = R.step0 + first + done;
+  }
+  open_tally<kBlock>(live, gone, first + done, first, ns, sample_every, nsamp, alive, removed);
+}
+
 // the checks the two calls share
 int fo_check(xpic_ctx* ctx, int64_t n, const xpic_fo_params* P)
 {
@@ -160,6 +202,42 @@ int xpic_full_orbit_trace(xpic_ctx* ctx, int64_t n, const xpic_fo_params* params
       hipLaunchKernelGGL(cn ? k_fo_trace<true> : k_fo_trace<false>, lane_grid(n), dim3(kBlock), 0, ctx->stream, ctx->g,
         ctx->field[XPIC_E], ctx->field[XPIC_B], *params, (long)n, s, first, ns, (long)sample_every, (long)nsamp, sm, it_sum,
         it_max);
+    }));
+  if (!cn) {
+    if (iterations_sum) std::fill(iterations_sum, iterations_sum + n, (int64_t)0);
+    if (iterations_max) std::fill(iterations_max, iterations_max + n, 0);
+  }
+  return 0;
+}
+
+int xpic_full_orbit_trace_open(xpic_ctx* ctx, int64_t n, const xpic_fo_params* params, int64_t steps, int64_t sample_every,
+  double* p_6, double* samples, int64_t* iterations_sum, int* iterations_max, const xpic_trace_region* region,
+  int64_t* exit_step, int64_t* alive, int64_t* removed)
+{ // xpic_full_orbit_trace with RemoveParticles::execute (remove_particles.cpp:22-38) at the top of every step
+  XPIC_CALL(fo_check(ctx, n, params));
+  const bool cn = params->scheme == XPIC_FO_CN;
+  OpenRegion R;
+  XPIC_CALL(open_region("full_orbit_trace_open", region, &R));
+  XPIC_CHECK(steps >= 0, "full_orbit_trace_open: steps is negative");
+  XPIC_CHECK((!samples && !alive) || sample_every >= 1,
+    "full_orbit_trace_open: sample_every must be >= 1 when samples or alive are asked for");
+  XPIC_CHECK(p_6, "full_orbit_trace_open: p_6 is null");
+  XPIC_CHECK(exit_step, "full_orbit_trace_open: exit_step is null");
+  XPIC_CHECK(removed, "full_orbit_trace_open: removed is null");
+  XPIC_CHECK(iterations_sum || !cn, "full_orbit_trace_open: iterations_sum is null");
+  XPIC_CHECK(iterations_max || !cn, "full_orbit_trace_open: iterations_max is null");
+  int64_t nsamp;
+  XPIC_CHECK(trace_sample_bytes(samples ? n : 0, steps, sample_every, samples || alive, &nsamp) >= 0,
+    "full_orbit_trace_open: the sample buffer (48 n steps / sample_every bytes) is too large");
+  *removed = 0;
+  if (n == 0 || steps == 0) return 0;
+  XPIC_CALL(batch_trace_open(ctx, "fo_trace_open", "fo_trace_open_compact", kLaunchSteps, n, steps, sample_every, nsamp, cn,
+    region->compact, region->step0, p_6, samples, iterations_sum, iterations_max, exit_step, alive, removed,
+    [&](double* s, const int64_t* list, long m, long first, int ns, double* sm, long long* it_sum, int* it_max, long long* ex,
+      unsigned long long* al, unsigned long long* rm) {
+      hipLaunchKernelGGL(cn ? k_fo_trace_open<true> : k_fo_trace_open<false>, lane_grid(m), dim3(kBlock), 0, ctx->stream,
+        ctx->g, ctx->field[XPIC_E], ctx->field[XPIC_B], *params, R, (long)n, s, (const long long*)list, m, first, ns,
+        (long)sample_every, (long)nsamp, sm, it_sum, it_max, ex, al, rm);
     }));
   if (!cn) {
     if (iterations_sum) std::fill(iterations_sum, iterations_sum + n, (int64_t)0);
