@@ -483,6 +483,42 @@ int xpic_drift_kinetic_trace_open(xpic_ctx* ctx, int64_t n, const xpic_dk_params
   int64_t sample_every, double* state_6, double* samples, int64_t* iterations_total, int* iterations_max,
   const xpic_trace_region* region, int64_t* exit_step, int64_t* alive, int64_t* removed);
 
+/* ---- paired trace: a guiding centre beside the full orbit of the same particle, advanced in lock-step on the device, and
+ * the reference's comparison of the two reduced there -- the time loop of the grid tests
+ * tests/drift_kinetic_push/drift_kinetic_grid_boris_ex1..4.cpp (ex1.cpp:79-98: process, boris_step, interpolate,
+ * update_comparison_stats) for n pairs.  Pair q is the Point record p_6[6 q ..] (fo: its scheme and tolerances) and the
+ * PointByField record state_6[6 q ..] (dk, gradB_field as in xpic_drift_kinetic_trace); both are read and overwritten.
+ * After every step the grid / Boris half of update_comparison_stats (tests/drift_kinetic_push/drift_kinetic_push.h:293-329;
+ * there is no analytical member here) is formed statement by statement, with Bg = the B_p of
+ * DriftKineticEsirkepov::interpolate(rn = the guiding centre after the step, r0 = before it) (ex1.cpp:92-93), which is
+ * xpic_drift_kinetic_interpolate's Bp3 for that segment, and Vector3::parallel_to / transverse_to / length
+ * (src/utils/vector3.h:160-205):
+ *   err_z      = |gc.z - fo.z|                                                       (:311)
+ *   err_par    = |gc.p_parallel - |fo.p.parallel_to(Bg)||     (a length: the sign is lost, as in the reference)  (:316-317)
+ *   err_mu     = |gc.mu_p - 0.5 mp |fo.p.transverse_to(Bg)|^2 / |Bg||               (:320-322)
+ *   err_energy = |0.5 (gc.p_perp^2 + gc.p_parallel^2) - 0.5 fo.p^2|                  (:270-278, :325-327)
+ * Every maximum is m = (m < e) ? e : m, the reference's std::max(m, e): an error that is not a number leaves the maximum
+ * alone, an infinite one is kept; |Bg| = 0 gets no special case.
+ * stats_4 [n][4] (required, in and out): the running maxima {z, p_parallel, mu, energy} of each pair over the steps; the
+ * entries are read as the maxima so far (zeros to start; a negative entry or a NaN is not checked, the rule above says what
+ * becomes of it).  curve_4 [steps / sample_every][4] (or NULL; needs sample_every >= 1): curve_4[k][j] = the maximum over
+ * the pairs of error j at step (k + 1) sample_every of this call, 0 where no pair has an error > 0; written, not
+ * accumulated.  dk_iterations_total / dk_iterations_max (required) and fo_iterations_sum / fo_iterations_max (XPIC_FO_CN:
+ * required; otherwise optional and zeroed) are the counters of the two closed traces.
+ * Checks: those of xpic_full_orbit_trace and xpic_drift_kinetic_trace, dk->maxit <= XPIC_PAIR_DK_MAXIT, and
+ * fo->dt == dk->dt, fo->qm == dk->qm.  n == 0 succeeds and touches nothing; steps == 0 returns the inputs.  Single z-slab
+ * contexts only.  Launches of at most XPIC_PAIR_LAUNCH_STEPS steps.  The region rule of the open traces is not part of
+ * this call: a pair is never removed.
+ * Guarantees: (a) p_6, state_6 and the four counters are bit for bit those of xpic_full_orbit_trace and
+ * xpic_drift_kinetic_trace over the same steps; (b) a call of s1 + s2 steps equals a call of s1 steps followed by one of
+ * s2 steps fed the first call's p_6, state_6 and stats_4, bit for bit in the states and stats_4; (c) curve_4[k][j] is, bit
+ * for bit, the maximum over q of the error a run of pair q alone has at that step. */
+#define XPIC_PAIR_LAUNCH_STEPS 64
+#define XPIC_PAIR_DK_MAXIT 1024
+int xpic_paired_trace(xpic_ctx* ctx, int64_t n, const xpic_fo_params* fo, const xpic_dk_params* dk, int gradB_field,
+  int64_t steps, int64_t sample_every, double* p_6, double* state_6, double* stats_4, double* curve_4,
+  int64_t* fo_iterations_sum, int* fo_iterations_max, int64_t* dk_iterations_total, int* dk_iterations_max);
+
 /* ---- z-slab decomposition (DMDA da_processors_z = nranks; src/utils/world.cpp:36-38).  A context created with
  * nranks > 1 owns planes [rank*nz/nranks, (rank+1)*nz/nranks) and must be given a communicator before any
  * call that moves data between slabs (steps, solves, operator applies, re-binning, energy): those calls are

@@ -1,0 +1,77 @@
+"""Plain numpy restatement of the reference's comparison of a guiding centre with the full orbit of the same particle,
+the model the kernel of xpic_amd/csrc/paired_trace.hip is tested against:
+
+  compare_step(...)   update_comparison_stats, the grid / Boris half   tests/drift_kinetic_push/drift_kinetic_push.h:293-329
+  operands(...)       the two numbers each of its four errors is the difference of
+  accumulate(...)     its std::max(m, e): m = (m < e) ? e : m
+  paired_trace(...)   the time loop of tests/drift_kinetic_push/drift_kinetic_grid_boris_ex1.cpp:79-98, with the steps of
+                      drift_kinetic_ref.push and full_orbit_ref.step / cn_step and the B of drift_kinetic_ref.interpolate
+
+Fields are arrays [nz][ny][nx][3]; a guiding centre is {x, y, z, p_parallel, p_perp, mu_p}, an orbit {x, y, z, px, py, pz}.
+Everything is vectorised over the pairs."""
+import numpy as np
+
+import drift_kinetic_ref as DK
+import full_orbit_ref as FO
+
+STATS = ("z", "p_parallel", "mu", "energy")
+
+
+def operands(gc, fo, Bg, mp):
+    """-> (a, b), each [n][4]: the two operands whose difference update_comparison_stats takes for err_z, err_parallel,
+    err_mu and err_energy (drift_kinetic_push.h:311-328), a from the guiding centre and b from the orbit; Bg is the B_p of
+    DriftKineticEsirkepov::interpolate(rn = the guiding centre after the step, r0 = before it)"""
+    gc, fo, Bg = (np.asarray(v, dtype=np.float64) for v in (gc, fo, Bg))
+    p = fo[:, 3:]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        par = ((p * Bg).sum(axis=1)[:, None] * Bg) / (Bg * Bg).sum(axis=1)[:, None]  # Vector3::parallel_to
+        tr = p - par                                                                  # Vector3::transverse_to
+        v_par = DK._len(par)
+        p_perp = DK._len(tr)
+        mu = 0.5 * mp * (p_perp * p_perp) / DK._len(Bg)
+    e_drift = 0.5 * (gc[:, 4] * gc[:, 4] + gc[:, 3] * gc[:, 3])  # get_kinetic_energy(PointByField) :270-273
+    e_boris = 0.5 * (p * p).sum(axis=1)                           # get_kinetic_energy(Point) :275-278
+    return (np.column_stack([gc[:, 2], gc[:, 3], gc[:, 5], e_drift]), np.column_stack([fo[:, 2], v_par, mu, e_boris]))
+
+
+def compare_step(gc, fo, Bg, mp):
+    """-> [n][4]: err_z, err_parallel, err_mu, err_energy of every pair"""
+    a, b = operands(gc, fo, Bg, mp)
+    return np.abs(a - b)
+
+
+def accumulate(m, e):
+    """std::max(m, e) as <algorithm> defines it, (m < e) ? e : m: a NaN in e leaves m alone (and a NaN in m stays), an
+    infinite e is kept"""
+    with np.errstate(invalid="ignore"):
+        return np.where(m < e, e, m)
+
+
+def paired_trace(E, B, gradB, d, fo, gc, steps, scheme, qm, mp, dt, sample_every=0, stats=None, eps=1e-12, delta=1e-12,
+                 dk_maxit=30, atol=FO.CN_ATOL, rtol=FO.CN_RTOL, maxit=FO.CN_MAXIT):
+    """-> (fo, gc, stats [n][4], curve [steps // sample_every][4] or None, errors [steps][n][4]).  stats enters as the
+    running maxima (None: zeros); curve[k] is the maximum over the pairs of the errors at step (k + 1) sample_every,
+    accumulated from 0 by the same rule"""
+    fo = np.array(fo, dtype=np.float64).reshape(-1, 6)
+    gc = np.array(gc, dtype=np.float64).reshape(-1, 6)
+    n = fo.shape[0]
+    stats = np.zeros((n, 4)) if stats is None else np.array(stats, dtype=np.float64).reshape(n, 4)
+    curve = np.zeros((steps // sample_every, 4)) if sample_every else None
+    errors = np.zeros((steps, n, 4))
+    for k in range(1, steps + 1):
+        old = gc
+        gc, _ = DK.push(E, B, gradB, d, old, qm, mp, dt, eps=eps, delta=delta, maxit=dk_maxit)
+        if scheme == "CN":
+            fo, _ = FO.cn_step(E, B, d, fo, qm, dt, atol=atol, rtol=rtol, maxit=maxit)
+        else:
+            fo = FO.step(scheme, E, B, d, fo, qm, dt)
+        _, Bg, _ = DK.interpolate(E, B, gradB, d, gc[:, :3], old[:, :3])
+        e = compare_step(gc, fo, Bg, mp)
+        errors[k - 1] = e
+        stats = accumulate(stats, e)
+        if sample_every and k % sample_every == 0:
+            row = np.zeros(4)
+            for q in range(n):
+                row = accumulate(row, e[q])
+            curve[k // sample_every - 1] = row
+    return fo, gc, stats, curve, errors

@@ -33,7 +33,7 @@ SYMBOLS = [
     "xpic_inject_particles", "xpic_set_coils_field", "xpic_set_mirror_field", "xpic_cell_traversal", "xpic_implicit_esirkepov_interpolate",
     "xpic_implicit_esirkepov_decompose", "xpic_drift_kinetic_interpolate", "xpic_drift_kinetic_push",
     "xpic_drift_kinetic_trace", "xpic_full_orbit_push", "xpic_full_orbit_trace", "xpic_full_orbit_trace_open",
-    "xpic_drift_kinetic_trace_open", "xpic_charge_collect", "xpic_charge_columns", "xpic_comm_rccl_unique_id", "xpic_comm_init_rccl", "xpic_comm_init_callbacks", "xpic_comm_size", "xpic_comm_peer_export", "xpic_comm_peer_import",
+    "xpic_drift_kinetic_trace_open", "xpic_paired_trace", "xpic_charge_collect", "xpic_charge_columns", "xpic_comm_rccl_unique_id", "xpic_comm_init_rccl", "xpic_comm_init_callbacks", "xpic_comm_size", "xpic_comm_peer_export", "xpic_comm_peer_import",
     "xpic_profile_enable", "xpic_profile_reset", "xpic_profile_get", "xpic_probe_copy_bandwidth",
 ]
 
@@ -136,6 +136,18 @@ class TraceRegion(C.Structure):  # include/xpic_hip.h: xpic_trace_region
 
 
 COMPACT = {"auto": 0, "never": 1, "always": 2}  # include/xpic_hip.h: enum xpic_trace_compact
+PAIR_LAUNCH_STEPS = 64  # include/xpic_hip.h: XPIC_PAIR_LAUNCH_STEPS
+PAIR_DK_MAXIT = 1024    # include/xpic_hip.h: XPIC_PAIR_DK_MAXIT
+PAIR_STATS = ("z", "p_parallel", "mu", "energy")  # the columns of stats_4 and curve_4 (xpic_paired_trace)
+
+
+class PairedTrace(collections.namedtuple(
+        "PairedTrace", "p state stats curve fo_iterations_sum fo_iterations_max dk_iterations_total dk_iterations_max")):
+    """What Context.paired_trace returns: the full orbits p [n][6] and the guiding centres state [n][6] after the steps;
+    stats [n][4], each pair's largest errors over the steps, and curve [steps // sample_every][4] (None without
+    sample_every), the largest error over the pairs at every sample_every-th step, both with the columns PAIR_STATS; the
+    iteration counters of the two closed traces."""
+    __slots__ = ()
 
 
 class OpenTrace(collections.namedtuple("OpenTrace", "state samples exit_step alive removed iterations_sum iterations_max")):
@@ -707,6 +719,33 @@ class Context:
             tot.ctypes.data_as(i64), mx.ctypes.data_as(C.POINTER(C.c_int)), C.byref(reg), ex.ctypes.data_as(i64),
             alive.ctypes.data_as(i64) if sample_every else None, C.byref(removed)))
         return OpenTrace(state, samples, ex, alive, removed.value, tot, mx)
+
+    # ---- paired trace (include/xpic_hip.h: xpic_paired_trace): full_orbit_trace of p and drift_kinetic_trace of state
+    # (guiding_centre(p, ..., orbit_centre=True) lays the two side by side) in lock-step, with the reference's comparison
+    # of the pair (ComparisonStats, tests/drift_kinetic_push/drift_kinetic_push.h:253-329) kept on the device
+    def paired_trace(self, p, state, steps, scheme, qm, mp, dt, gradB_field=None, sample_every=0, stats=None, atol=1e-7,
+                     rtol=1e-7, maxit=30, eps=1e-12, delta=1e-12, dk_maxit=30):
+        """-> PairedTrace.  stats: the running maxima a previous call returned (None: zeros), so that calls compose;
+        sample_every: the curve's stride (0: no curve); maxit is the full orbit's (CN), dk_maxit the guiding centre's"""
+        p = np.array(p, dtype=np.float64).reshape(-1, 6)  # copies: the call works in place
+        state = np.array(state, dtype=np.float64).reshape(-1, 6)
+        n = p.shape[0]
+        if state.shape[0] != n:
+            raise XpicError("paired_trace: p and state hold different numbers of particles")
+        stats = np.zeros((n, 4)) if stats is None else np.array(stats, dtype=np.float64).reshape(n, 4)
+        nsamp = max(int(steps), 0) // int(sample_every) if sample_every else 0
+        curve = np.zeros((nsamp, 4)) if sample_every else None
+        fsum, fmax = np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int32)
+        dtot, dmax = np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int32)
+        F = self._fo_params(scheme, qm, dt, atol, rtol, maxit)
+        D = self._dk_params(qm, mp, dt, eps, delta, dk_maxit)
+        i64, i32 = C.POINTER(C.c_int64), C.POINTER(C.c_int)
+        self._ck(self.L.xpic_paired_trace(
+            self.h, C.c_int64(n), C.byref(F), C.byref(D), -1 if gradB_field is None else int(gradB_field),
+            C.c_int64(int(steps)), C.c_int64(int(sample_every)), _dp(p), _dp(state), _dp(stats),
+            _dp(curve) if sample_every else None, fsum.ctypes.data_as(i64), fmax.ctypes.data_as(i32),
+            dtot.ctypes.data_as(i64), dmax.ctypes.data_as(i32)))
+        return PairedTrace(p, state, stats, curve, fsum, fmax, dtot, dmax)
 
     def charge_collect(self):
         self._ck(self.L.xpic_charge_collect(self.h))

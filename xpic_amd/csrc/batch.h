@@ -1,5 +1,6 @@
-// batch.h -- the host side that the batch particle calls share (eccapfim.hip, drift_kinetic.hip, full_orbit.hip): host
-// arrays of particles are staged on the device, a kernel runs one lane per particle, the results are copied back.
+// batch.h -- the host side that the batch particle calls share (eccapfim.hip, drift_kinetic.hip, full_orbit.hip,
+// paired_trace.hip): host arrays of particles are staged on the device, a kernel runs one lane per particle, the results
+// are copied back.  batch_pair_trace is batch_trace for two batches advanced side by side (paired_trace.hip).
 // batch_trace_open is batch_trace for the open traces (trace_open.h, trace_open.hip): exit steps, alive counts, and the
 // list of live particles between launches.
 // DevScratch also owns every other device buffer that lives for one call (fields.hip, particles.hip, commands.hip,
@@ -15,17 +16,17 @@ namespace xpic {
 
 // ---- This part uses nothing from HIP: a plain host compiler compiles it (and a sanitizer build runs it) ----------------
 
-// [n][6] host records -> [6][n], and back
-inline void to_soa(const double* aos, int64_t n, std::vector<double>& soa)
+// [n][w] host records -> [w][n], and back; w = 6: a particle, w = 4: the statistics of a pair
+inline void to_soa(const double* aos, int64_t n, std::vector<double>& soa, int w = 6)
 {
-  soa.resize((size_t)6 * n);
+  soa.resize((size_t)w * n);
   for (int64_t q = 0; q < n; ++q)
-    for (int k = 0; k < 6; ++k) soa[(size_t)k * n + q] = aos[6 * q + k];
+    for (int k = 0; k < w; ++k) soa[(size_t)k * n + q] = aos[w * q + k];
 }
-inline void to_aos(const double* soa, int64_t n, double* aos)
+inline void to_aos(const double* soa, int64_t n, double* aos, int w = 6)
 {
   for (int64_t q = 0; q < n; ++q)
-    for (int k = 0; k < 6; ++k) aos[6 * q + k] = soa[(size_t)k * n + q];
+    for (int k = 0; k < w; ++k) aos[w * q + k] = soa[(size_t)k * n + q];
 }
 
 // The sample buffer of a trace of n >= 0 particles over steps >= 0 steps: a sample after every sample_every-th step
@@ -174,6 +175,62 @@ int batch_trace(xpic_ctx* c, const char* label, int launch_steps, int64_t n, int
   XPIC_HIP(hipStreamSynchronize(c->stream));
   to_aos(h.data(), n, state_6);
   for (int64_t k = 0; k < nsamp; ++k) to_aos(hs.data() + row * k, n, samples + row * k);
+  return 0;
+}
+
+// batch_trace for a full orbit and a guiding centre per lane (paired_trace.hip): `steps` steps of n > 0
+// pairs in place in p_6 and state_6, the running maxima stats_4 [n][4] staged as [4][n] (in and out), curve_4 [nsamp][4]
+// (null with nsamp == 0) zeroed on the device and written by the kernel's atomic maxima, the dk counters always and the fo
+// counters with `fo_counters`, all zeroed here.  launch(fo_s, dk_s, stats, first, nsteps, curve, fo_sum, fo_max, dk_sum,
+// dk_max) starts the kernel for steps first + 1 .. first + nsteps (curve: null without one; fo_sum, fo_max: null without
+// fo counters); each launch is timed under `label`.  Everything comes back once, after the last launch.
+template <class Launch>
+int batch_pair_trace(xpic_ctx* c, const char* label, int launch_steps, int64_t n, int64_t steps, int64_t nsamp,
+  bool fo_counters, double* p_6, double* state_6, double* stats_4, double* curve_4, int64_t* fo_sum, int* fo_max,
+  int64_t* dk_sum, int* dk_max, Launch launch)
+{
+  const size_t row = (size_t)6 * n; // doubles of one state
+  std::vector<double> hf, hd, hst;
+  to_soa(p_6, n, hf);
+  to_soa(state_6, n, hd);
+  to_soa(stats_4, n, hst, 4);
+  DevScratch<double> fs, ds, st, cv;
+  DevScratch<int64_t> ftot, dtot;
+  DevScratch<int> fmx, dmx;
+  XPIC_CALL(fs.alloc(row)); XPIC_CALL(ds.alloc(row)); XPIC_CALL(st.alloc(4 * n));
+  XPIC_CALL(dtot.alloc(n)); XPIC_CALL(dmx.alloc(n));
+  XPIC_CALL(zero(dtot, n, c->stream)); XPIC_CALL(zero(dmx, n, c->stream));
+  if (fo_counters) {
+    XPIC_CALL(ftot.alloc(n)); XPIC_CALL(fmx.alloc(n));
+    XPIC_CALL(zero(ftot, n, c->stream)); XPIC_CALL(zero(fmx, n, c->stream));
+  }
+  if (nsamp > 0) {
+    XPIC_CALL(cv.alloc(4 * nsamp));
+    XPIC_CALL(zero(cv, 4 * nsamp, c->stream));
+  }
+  XPIC_CALL(upload(fs, hf.data(), row, c->stream));
+  XPIC_CALL(upload(ds, hd.data(), row, c->stream));
+  XPIC_CALL(upload(st, hst.data(), 4 * n, c->stream));
+  for (int64_t first = 0; first < steps; first += launch_steps) {
+    const int ns = (int)std::min<int64_t>(launch_steps, steps - first);
+    Timed t(c, label);
+    launch(fs.p, ds.p, st.p, (long)first, ns, (unsigned long long*)cv.p, (long long*)ftot.p, fmx.p, (long long*)dtot.p, dmx.p);
+    XPIC_HIP(hipGetLastError());
+  }
+  XPIC_CALL(download(hf.data(), fs, row, c->stream));
+  XPIC_CALL(download(hd.data(), ds, row, c->stream));
+  XPIC_CALL(download(hst.data(), st, 4 * n, c->stream));
+  XPIC_CALL(download(dk_sum, dtot, n, c->stream));
+  XPIC_CALL(download(dk_max, dmx, n, c->stream));
+  if (fo_counters) {
+    XPIC_CALL(download(fo_sum, ftot, n, c->stream));
+    XPIC_CALL(download(fo_max, fmx, n, c->stream));
+  }
+  if (nsamp > 0) XPIC_CALL(download(curve_4, cv, 4 * nsamp, c->stream));
+  XPIC_HIP(hipStreamSynchronize(c->stream));
+  to_aos(hf.data(), n, p_6);
+  to_aos(hd.data(), n, state_6);
+  to_aos(hst.data(), n, stats_4, 4);
   return 0;
 }
 
