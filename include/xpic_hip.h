@@ -519,6 +519,66 @@ int xpic_paired_trace(xpic_ctx* ctx, int64_t n, const xpic_fo_params* fo, const 
   int64_t steps, int64_t sample_every, double* p_6, double* state_6, double* stats_4, double* curve_4,
   int64_t* fo_iterations_sum, int* fo_iterations_max, int64_t* dk_iterations_total, int* dk_iterations_max);
 
+/* ---- analytic field models: a second field source for the tracers, evaluated on the device at the position the
+ * reference's set_fields_callback is given, instead of gathered from the context's grid.  A closed set of kinds, each the
+ * restatement of one family of the reference's callbacks (xpic_amd/csrc/field_model.h):
+ *   XPIC_MODEL_UNIFORM           E = E0, B = B0, grad |B| = 0 (tests/drift_kinetic_push/drift_kinetic_push_ex1.cpp:9-13,
+ *                                ex2.cpp:11-16, tests/crank_nicolson_push/crank_nicolson_push_ex1.cpp, ex2.cpp)
+ *   XPIC_MODEL_LINEAR            E = E0, B = B0 + ((r - r0) . g) g / |g|, grad |B| = g (drift_kinetic_push_ex3.cpp:12-17)
+ *   XPIC_MODEL_QUADRATIC_MIRROR  quadratic_magnetic_mirror::get_fields (tests/drift_kinetic_push/drift_kinetic_push.h:24-70)
+ *                                with B_min, B_max, W, D; axis at (W / 2, W / 2), midplane z = D / 2.  E_phi and phi: the
+ *                                E of drift_kinetic_push_ex4.cpp:12-22, {E_phi (y - W / 2), -E_phi (x - W / 2),
+ *                                phi pi / D sin(pi (z - D / 2) / D)}; both 0: E = 0
+ *   XPIC_MODEL_GAUSSIAN_MIRROR   gaussian_magnetic_mirror::get_fields (drift_kinetic_push.h:72-157) with B_min, B_max, L,
+ *                                W; axis at (L, L), throats at z = 0 and z = 2 L; E = 0
+ * Members a kind does not name are ignored.  W (and the quadratic mirror's D) must not be 0. */
+enum xpic_model_kind {
+  XPIC_MODEL_UNIFORM = 0, XPIC_MODEL_LINEAR = 1, XPIC_MODEL_QUADRATIC_MIRROR = 2, XPIC_MODEL_GAUSSIAN_MIRROR = 3,
+  XPIC_MODEL_NKINDS = 4
+};
+typedef struct xpic_field_model {
+  int32_t kind; /* enum xpic_model_kind */
+  int32_t reserved;
+  double E0[3];
+  double B0[3];
+  double r0[3];
+  double g[3];
+  double B_min;
+  double B_max;
+  double W;
+  double D;
+  double L;
+  double E_phi;
+  double phi;
+} xpic_field_model;
+/* The model at n positions r3[3 q ..] (host arrays) -> E3, B3, gradB3 (3 doubles per position each). */
+int xpic_model_fields(xpic_ctx* ctx, const xpic_field_model* model, int64_t n, const double* r3, double* E3, double* B3,
+  double* gradB3);
+/* Fills grid vectors from a model as the reference's FieldContext::initialize does (drift_kinetic_push.h:176-209 with the
+ * fill functions of drift_kinetic_grid_boris_ex1..4.cpp): all three components of node (i, j, k) are the model at
+ * (i dx, j dy, k dz).  A field id < 0 is skipped.  Any context; on z-slabs every rank fills its owned planes (ghost planes
+ * are the next exchange's). */
+int xpic_set_model_field(xpic_ctx* ctx, const xpic_field_model* model, int E_field, int B_field, int gradB_field);
+/* xpic_full_orbit_trace_open and xpic_drift_kinetic_trace_open with the model in the grid's place.  The model is evaluated
+ * where the reference's callback is: at rn for the drift-kinetic pusher (E_p too: no segment shape), at the particle's r in
+ * the kick of a Chin scheme, at the midpoint (r1 + r0) / 2 for Crank-Nicolson (drift_kinetic_push_ex9.cpp:75-78).  The
+ * step arithmetic is the grid traces' own text (full_orbit_step.h, drift_kinetic_step.h).  steps == 1 is the one-step push.
+ * region: as in the open traces, with two differences.  geometry may be XPIC_GEOM_NONE: no particle is ever tested or
+ * removed, the call is the closed trace, and exit_step, alive and removed may be NULL.  `compact` is not read: every launch
+ * covers all n particles (XPIC_COMPACT_NEVER).  dx, dy, dz of the region rule are the context's.  Calls compose through
+ * step0 and exit_step as the open traces do, bit for bit.  No grid vector is read, so any context is accepted, z-slabs
+ * included.  n == 0 succeeds and touches nothing.  Launches of at most XPIC_MODEL_LAUNCH_STEPS steps; the drift-kinetic
+ * maxit is within 1 .. XPIC_MODEL_DK_MAXIT, the Crank-Nicolson one within 1 .. XPIC_FO_MAXIT. */
+#define XPIC_GEOM_NONE (-1)
+#define XPIC_MODEL_LAUNCH_STEPS 64
+#define XPIC_MODEL_DK_MAXIT 1024
+int xpic_model_full_orbit_trace(xpic_ctx* ctx, int64_t n, const xpic_fo_params* params, const xpic_field_model* model,
+  int64_t steps, int64_t sample_every, double* p_6, double* samples, int64_t* iterations_sum, int* iterations_max,
+  const xpic_trace_region* region, int64_t* exit_step, int64_t* alive, int64_t* removed);
+int xpic_model_drift_kinetic_trace(xpic_ctx* ctx, int64_t n, const xpic_dk_params* params, const xpic_field_model* model,
+  int64_t steps, int64_t sample_every, double* state_6, double* samples, int64_t* iterations_total, int* iterations_max,
+  const xpic_trace_region* region, int64_t* exit_step, int64_t* alive, int64_t* removed);
+
 /* ---- z-slab decomposition (DMDA da_processors_z = nranks; src/utils/world.cpp:36-38).  A context created with
  * nranks > 1 owns planes [rank*nz/nranks, (rank+1)*nz/nranks) and must be given a communicator before any
  * call that moves data between slabs (steps, solves, operator applies, re-binning, energy): those calls are

@@ -33,7 +33,8 @@ SYMBOLS = [
     "xpic_inject_particles", "xpic_set_coils_field", "xpic_set_mirror_field", "xpic_cell_traversal", "xpic_implicit_esirkepov_interpolate",
     "xpic_implicit_esirkepov_decompose", "xpic_drift_kinetic_interpolate", "xpic_drift_kinetic_push",
     "xpic_drift_kinetic_trace", "xpic_full_orbit_push", "xpic_full_orbit_trace", "xpic_full_orbit_trace_open",
-    "xpic_drift_kinetic_trace_open", "xpic_paired_trace", "xpic_charge_collect", "xpic_charge_columns", "xpic_comm_rccl_unique_id", "xpic_comm_init_rccl", "xpic_comm_init_callbacks", "xpic_comm_size", "xpic_comm_peer_export", "xpic_comm_peer_import",
+    "xpic_drift_kinetic_trace_open", "xpic_paired_trace", "xpic_model_fields", "xpic_set_model_field",
+    "xpic_model_full_orbit_trace", "xpic_model_drift_kinetic_trace", "xpic_charge_collect", "xpic_charge_columns", "xpic_comm_rccl_unique_id", "xpic_comm_init_rccl", "xpic_comm_init_callbacks", "xpic_comm_size", "xpic_comm_peer_export", "xpic_comm_peer_import",
     "xpic_profile_enable", "xpic_profile_reset", "xpic_profile_get", "xpic_probe_copy_bandwidth",
 ]
 
@@ -139,6 +140,35 @@ COMPACT = {"auto": 0, "never": 1, "always": 2}  # include/xpic_hip.h: enum xpic_
 PAIR_LAUNCH_STEPS = 64  # include/xpic_hip.h: XPIC_PAIR_LAUNCH_STEPS
 PAIR_DK_MAXIT = 1024    # include/xpic_hip.h: XPIC_PAIR_DK_MAXIT
 PAIR_STATS = ("z", "p_parallel", "mu", "energy")  # the columns of stats_4 and curve_4 (xpic_paired_trace)
+
+
+class FieldModel(C.Structure):  # include/xpic_hip.h: xpic_field_model
+    _fields_ = [("kind", C.c_int32), ("reserved", C.c_int32), ("E0", C.c_double * 3), ("B0", C.c_double * 3),
+                ("r0", C.c_double * 3), ("g", C.c_double * 3), ("B_min", C.c_double), ("B_max", C.c_double), ("W", C.c_double),
+                ("D", C.c_double), ("L", C.c_double), ("E_phi", C.c_double), ("phi", C.c_double)]
+
+
+MODEL_KINDS = {"uniform": 0, "linear": 1, "quadratic_mirror": 2, "gaussian_mirror": 3}  # include/xpic_hip.h: enum xpic_model_kind
+GEOM_NONE = -1             # include/xpic_hip.h: XPIC_GEOM_NONE
+MODEL_LAUNCH_STEPS = 64    # include/xpic_hip.h: XPIC_MODEL_LAUNCH_STEPS
+MODEL_DK_MAXIT = 1024      # include/xpic_hip.h: XPIC_MODEL_DK_MAXIT
+
+
+def field_model(kind, **params):
+    """An analytic field model (include/xpic_hip.h: xpic_field_model).  kind: a key of MODEL_KINDS or its number; params:
+    the members the kind reads -- uniform: E0, B0; linear: E0, B0, r0, g; quadratic_mirror: B_min, B_max, W, D (and E_phi,
+    phi); gaussian_mirror: B_min, B_max, L, W.  A member that is not given is 0."""
+    m = FieldModel()
+    m.kind = int(MODEL_KINDS.get(kind, kind))
+    names = {f[0] for f in FieldModel._fields_} - {"kind", "reserved"}
+    for k, v in params.items():
+        if k not in names:
+            raise XpicError("field_model: no parameter %r" % (k,))
+        if k in ("E0", "B0", "r0", "g"):
+            setattr(m, k, (C.c_double * 3)(*[float(x) for x in v]))
+        else:
+            setattr(m, k, float(v))
+    return m
 
 
 class PairedTrace(collections.namedtuple(
@@ -746,6 +776,63 @@ class Context:
             _dp(curve) if sample_every else None, fsum.ctypes.data_as(i64), fmax.ctypes.data_as(i32),
             dtot.ctypes.data_as(i64), dmax.ctypes.data_as(i32)))
         return PairedTrace(p, state, stats, curve, fsum, fmax, dtot, dmax)
+
+    # ---- analytic field models (include/xpic_hip.h: xpic_field_model): the tracers with a closed-form field evaluated
+    # on the device in the grid's place.  model: what field_model(...) returns.  region: a geometry dict as in the open
+    # traces, or None for no region (the closed trace: exit_step stays -1, alive is the batch size, removed 0)
+    def model_fields(self, model, r):
+        """-> (E, B, gradB) of the model at the positions r [n][3]"""
+        r = np.ascontiguousarray(r, dtype=np.float64).reshape(-1, 3)
+        E, B, gB = np.zeros_like(r), np.zeros_like(r), np.zeros_like(r)
+        self._ck(self.L.xpic_model_fields(self.h, None if model is None else C.byref(model), C.c_int64(r.shape[0]), _dp(r),
+                                          _dp(E), _dp(B), _dp(gB)))
+        return E, B, gB
+
+    def set_model_field(self, model, E_field=E, B_field=B, gradB_field=None):
+        """fills the grid vectors from the model, every component of node (i, j, k) at (i dx, j dy, k dz); None: skipped"""
+        ids = [-1 if f is None else int(f) for f in (E_field, B_field, gradB_field)]
+        self._ck(self.L.xpic_set_model_field(self.h, None if model is None else C.byref(model), *ids))
+
+    def _model_args(self, state, steps, sample_every, region, exit_step, step0, keep_samples):
+        if region is None:
+            state, samples, alive, ex, reg, tot, mx = self._open_args(
+                state, steps, sample_every, {"name": "box", "min": (0, 0, 0), "max": (0, 0, 0)}, exit_step, step0, "never",
+                keep_samples)
+            reg.geometry = GEOM_NONE
+        else:
+            state, samples, alive, ex, reg, tot, mx = self._open_args(state, steps, sample_every, region, exit_step, step0,
+                                                                          "never", keep_samples)
+        return state, samples, alive, ex, reg, tot, mx
+
+    def model_full_orbit_trace(self, state, steps, scheme, qm, dt, model, region=None, sample_every=0, exit_step=None,
+                               step0=0, keep_samples=True, atol=1e-7, rtol=1e-7, maxit=30):
+        """full_orbit_trace_open on an analytic model -> OpenTrace; steps = 1 is the one-step push"""
+        state, samples, alive, ex, reg, tot, mx = self._model_args(state, steps, sample_every, region, exit_step, step0,
+                                                                       keep_samples)
+        P = self._fo_params(scheme, qm, dt, atol, rtol, maxit)
+        removed, i64 = C.c_int64(), C.POINTER(C.c_int64)
+        bare = region is None and exit_step is None  # the closed trace: the library gets no exit_step and no removed
+        self._ck(self.L.xpic_model_full_orbit_trace(
+            self.h, C.c_int64(state.shape[0]), C.byref(P), None if model is None else C.byref(model), C.c_int64(int(steps)),
+            C.c_int64(int(sample_every)), _dp(state), None if samples is None else _dp(samples), tot.ctypes.data_as(i64),
+            mx.ctypes.data_as(C.POINTER(C.c_int)), C.byref(reg), None if bare else ex.ctypes.data_as(i64),
+            alive.ctypes.data_as(i64) if sample_every else None, None if bare else C.byref(removed)))
+        return OpenTrace(state, samples, ex, alive, removed.value, tot, mx)
+
+    def model_drift_kinetic_trace(self, state, steps, qm, mp, dt, model, region=None, sample_every=0, exit_step=None,
+                                  step0=0, keep_samples=True, eps=1e-12, delta=1e-12, maxit=30):
+        """drift_kinetic_trace_open on an analytic model -> OpenTrace; steps = 1 is the one-step push"""
+        state, samples, alive, ex, reg, tot, mx = self._model_args(state, steps, sample_every, region, exit_step, step0,
+                                                                       keep_samples)
+        P = self._dk_params(qm, mp, dt, eps, delta, maxit)
+        removed, i64 = C.c_int64(), C.POINTER(C.c_int64)
+        bare = region is None and exit_step is None  # the closed trace: the library gets no exit_step and no removed
+        self._ck(self.L.xpic_model_drift_kinetic_trace(
+            self.h, C.c_int64(state.shape[0]), C.byref(P), None if model is None else C.byref(model), C.c_int64(int(steps)),
+            C.c_int64(int(sample_every)), _dp(state), None if samples is None else _dp(samples), tot.ctypes.data_as(i64),
+            mx.ctypes.data_as(C.POINTER(C.c_int)), C.byref(reg), None if bare else ex.ctypes.data_as(i64),
+            alive.ctypes.data_as(i64) if sample_every else None, None if bare else C.byref(removed)))
+        return OpenTrace(state, samples, ex, alive, removed.value, tot, mx)
 
     def charge_collect(self):
         self._ck(self.L.xpic_charge_collect(self.h))

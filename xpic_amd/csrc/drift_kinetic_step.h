@@ -149,15 +149,29 @@ __device__ inline void dk_v_terms(const xpic_dk_params& P, const DKPoint& p0, do
   *drive = P.dt * P.qm * (dot3(Eh, h) + term);
 }
 
+// The field source of dk_process: what the reference's set_fields_callback is to DriftKineticPush.  A source has
+//   void dk(const double* rn, const double* r0, double* Ep, double* Bp, double* gBp) const
+// DKGrid is the grid of the context (dk_fields); model_trace.hip has the analytic one.
+template <bool GRAD>
+struct DKGrid {
+  const GridDev& g;
+  const double* __restrict__ E;
+  const double* __restrict__ B;
+  const double* __restrict__ gB;
+  __device__ inline void dk(const double* rn, const double* r0, double* Ep, double* Bp, double* gBp) const
+  {
+    dk_fields<GRAD>(g, E, B, gB, rn, r0, Ep, Bp, gBp);
+  }
+};
+
 // DriftKineticPush::process(dt, pn, p0) (:48-108), statement by statement; pn enters as the initial guess.  Returns the
 // reference's `it`: the number of updates made, maxit for a lane that did not meet the tolerances (the reference's
 // trailing PetscCheckAbort is the caller's to make).
-template <bool GRAD>
-__device__ inline int dk_process(const GridDev& g, const double* __restrict__ E, const double* __restrict__ B,
-  const double* __restrict__ gB, const xpic_dk_params& P, const DKPoint& p0, DKPoint& pn)
+template <class SRC>
+__device__ inline int dk_process(const SRC& src, const xpic_dk_params& P, const DKPoint& p0, DKPoint& pn)
 {
   double Eh[3], Bp[3], gradBp[3];
-  dk_fields<GRAD>(g, E, B, gB, pn.r, p0.r, Eh, Bp, gradBp); // set_fields(p0.r, pn.r, Eh, Bp, gradBp)
+  src.dk(pn.r, p0.r, Eh, Bp, gradBp); // set_fields(p0.r, pn.r, Eh, Bp, gradBp)
   double Vd[3], Vhh[3], B0[3], Bh[3], gradB0[3], gradBh[3], b0[3], bp[3], h[3];
   double Vh = 0.0, R1 = 0.0, R2 = 0.0;
 #pragma unroll
@@ -183,7 +197,7 @@ __device__ inline int dk_process(const GridDev& g, const double* __restrict__ E,
     if ((R1 < P.eps) && (R2 < P.delta) && it) break;
 #pragma unroll
     for (int c = 0; c < 3; ++c) pn.r[c] = p0.r[c] + P.dt * (Vhh[c] + Vd[c]); // update_r :121-125
-    dk_fields<GRAD>(g, E, B, gB, pn.r, p0.r, Eh, Bp, gradBp);
+    src.dk(pn.r, p0.r, Eh, Bp, gradBp);
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
       Bh[c] = 0.5 * (Bp[c] + B0[c]);
@@ -198,6 +212,14 @@ __device__ inline int dk_process(const GridDev& g, const double* __restrict__ E,
     pn.ppar = p0.ppar + drive - mu_term;                                    // update_v_parallel :133-142
   }
   return it;
+}
+
+// dk_process on the context's grid
+template <bool GRAD>
+__device__ inline int dk_process(const GridDev& g, const double* __restrict__ E, const double* __restrict__ B,
+  const double* __restrict__ gB, const xpic_dk_params& P, const DKPoint& p0, DKPoint& pn)
+{
+  return dk_process(DKGrid<GRAD>{g, E, B, gB}, P, p0, pn);
 }
 
 __device__ inline void dk_load(const double* __restrict__ s, long n, long q, DKPoint& p)

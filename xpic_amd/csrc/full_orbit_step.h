@@ -199,12 +199,28 @@ __device__ inline void fo_update_vEB(double dt, double qm, const double* Ep, con
   for (int c = 0; c < 3; ++c) v[c] += a[c] + (bw[c] + 0.5 * bbw[c]) / den;
 }
 
+// The field source of fo_step and fo_cn_process: what `interpolate` is to process_<id> and the set_fields_callback to
+// CrankNicolsonPush.  A source has
+//   void at(const double* r, double* Ep, double* Bp) const                            the fields of a kick at r
+//   void segment(const double* rn, const double* r0, double* Ep, double* Bp) const    those of a step r0 -> rn
+// FOGrid is the grid of the context (fo_gather, fo_gather_segment); model_trace.hip has the analytic one.
+struct FOGrid {
+  const GridDev& g;
+  const double* __restrict__ E;
+  const double* __restrict__ B;
+  __device__ inline void at(const double* r, double* Ep, double* Bp) const { fo_gather<true>(g, E, B, r, Ep, Bp); }
+  __device__ inline void segment(const double* rn, const double* r0, double* Ep, double* Bp) const
+  {
+    fo_gather_segment(g, E, B, rn, r0, Ep, Bp);
+  }
+};
+
 // interpolate(point.r, E_p, B_p); push.set_fields(E_p, B_p); push.update_v<kind>(h, point)
-__device__ inline void fo_kick(const GridDev& g, const double* __restrict__ E, const double* __restrict__ B, int kind,
-  double h, double qm, FOPoint& pt)
+template <class SRC>
+__device__ inline void fo_kick(const SRC& src, int kind, double h, double qm, FOPoint& pt)
 {
   double Ep[3], Bp[3];
-  fo_gather<true>(g, E, B, pt.r, Ep, Bp);
+  src.at(pt.r, Ep, Bp);
   if (kind == FO_VEB) fo_update_vEB(h, qm, Ep, Bp, pt.p);
   else fo_update_v_magnetic(kind, h, qm, Bp, pt.p);
 }
@@ -212,8 +228,8 @@ __device__ inline void fo_kick(const GridDev& g, const double* __restrict__ E, c
 // process_<id>(push, point, interpolate) for the 17 Chin ids (boris_push.h:20-198).  The one switch names, for every id,
 // the velocity update it uses and which of the four orders of statements it is; the statements below are those of the
 // process_ functions, in their order and with their dt / 2 arguments.  `scheme` is uniform over a launch.
-__device__ inline void fo_step(int scheme, const GridDev& g, const double* __restrict__ E, const double* __restrict__ B,
-  double qm, double dt, FOPoint& pt)
+template <class SRC>
+__device__ inline void fo_step(int scheme, const SRC& src, double qm, double dt, FOPoint& pt)
 {
   enum { O_1A, O_1B, O_2A, O_2B };
   int kind = FO_VM, order = O_1A;
@@ -235,10 +251,16 @@ __device__ inline void fo_step(int scheme, const GridDev& g, const double* __res
   }
   if (order == O_1B) fo_update_r(dt, pt);                  // 1B: r first
   if (order == O_2B) fo_update_r(dt / 2.0, pt);            // 2B: r_0 + (dt / 2) v_0 -> r_{1/2}
-  fo_kick(g, E, B, kind, order == O_2A ? dt / 2.0 : dt, qm, pt);
+  fo_kick(src, kind, order == O_2A ? dt / 2.0 : dt, qm, pt);
   if (order == O_1A || order == O_2A) fo_update_r(dt, pt); // 1A: r last; 2A: r_0 + dt v_{1/2} -> r_1
   if (order == O_2B) fo_update_r(dt / 2.0, pt);            // 2B: r_{1/2} + (dt / 2) v_1 -> r_1
-  if (order == O_2A) fo_kick(g, E, B, kind, dt / 2.0, qm, pt); // 2A: v_B(r_1, v_{1/2}, dt / 2) -> v_1
+  if (order == O_2A) fo_kick(src, kind, dt / 2.0, qm, pt); // 2A: v_B(r_1, v_{1/2}, dt / 2) -> v_1
+}
+// fo_step on the context's grid
+__device__ inline void fo_step(int scheme, const GridDev& g, const double* __restrict__ E, const double* __restrict__ B,
+  double qm, double dt, FOPoint& pt)
+{
+  fo_step(scheme, FOGrid{g, E, B}, qm, dt, pt);
 }
 
 // calc_residue of CrankNicolsonPush::process (:41-43)
@@ -255,8 +277,9 @@ __device__ inline double fo_cn_residue(double dt, double qm, const FOPoint& pn, 
 // CrankNicolsonPush::process(dt, pn, p0) (:31-71), statement by statement; pn enters as the initial guess.  Returns the
 // reference's `it`: the index of the iteration whose residual met the tolerances, maxit for a lane that ran out of
 // iterations (the reference's trailing PetscCheckAbort is the caller's to make).  maxit <= XPIC_FO_MAXIT on the host.
-__device__ inline int fo_cn_process(const GridDev& g, const double* __restrict__ E, const double* __restrict__ B, double qm,
-  double dt, double atol, double rtol, int maxit, FOPoint& pn, const FOPoint& p0)
+template <class SRC>
+__device__ inline int fo_cn_process(const SRC& src, double qm, double dt, double atol, double rtol, int maxit, FOPoint& pn,
+  const FOPoint& p0)
 {
   double vh[3], Ep[3], Bp[3];
 #pragma unroll
@@ -264,7 +287,7 @@ __device__ inline int fo_cn_process(const GridDev& g, const double* __restrict__
     vh[c] = 0.5 * (pn.p[c] + p0.p[c]);
     pn.r[c] = p0.r[c] + dt * vh[c];
   }
-  fo_gather_segment(g, E, B, pn.r, p0.r, Ep, Bp); // set_fields(pn.r, p0.r, E_p, B_p)
+  src.segment(pn.r, p0.r, Ep, Bp); // set_fields(pn.r, p0.r, E_p, B_p)
   const double r0 = fo_cn_residue(dt, qm, pn, p0, vh, Ep, Bp);
   double rn = 0;
   const double alpha = 0.5 * dt * qm;
@@ -286,9 +309,15 @@ __device__ inline int fo_cn_process(const GridDev& g, const double* __restrict__
     }
     rn = fo_cn_residue(dt, qm, pn, p0, vh, Ep, Bp);
     if (rn < atol + rtol * r0) return it;
-    fo_gather_segment(g, E, B, pn.r, p0.r, Ep, Bp);
+    src.segment(pn.r, p0.r, Ep, Bp);
   }
   return maxit;
+}
+// fo_cn_process on the context's grid
+__device__ inline int fo_cn_process(const GridDev& g, const double* __restrict__ E, const double* __restrict__ B, double qm,
+  double dt, double atol, double rtol, int maxit, FOPoint& pn, const FOPoint& p0)
+{
+  return fo_cn_process(FOGrid{g, E, B}, qm, dt, atol, rtol, maxit, pn, p0);
 }
 
 }  // namespace xpic

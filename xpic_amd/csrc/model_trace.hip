@@ -1,0 +1,338 @@
+// model_trace.hip -- the tracers on an analytic field model instead of the context's grid: the
+// reference's examples that feed their pusher through set_fields_callback with a closed-form field,
+//   tests/drift_kinetic_push/drift_kinetic_push_ex1 .. ex5, ex9.cpp     DriftKineticPush (callback at rn)
+//   tests/boris_push/boris_push_ex*.cpp, drift_kinetic_push_ex9.cpp     process_<id> (fields at the particle's r)
+//   tests/crank_nicolson_push/crank_nicolson_push_ex1, ex2.cpp, ex9     CrankNicolsonPush (ex9.cpp:75-78: at (r1 + r0) / 2)
+// for a batch.  The models are field_model.h's; the step arithmetic is full_orbit_step.h's and drift_kinetic_step.h's own
+// text, instantiated with a field source that evaluates the model in registers where the grid source gathers.  One lane
+// per particle, fp64, no cross-lane operation but open_tally's.  One kernel per pusher serves the closed trace, the open
+// trace and the one-step push: the region rule (trace_open.h) is skipped for XPIC_GEOM_NONE, which the host passes as
+// R.kind < 0.  No grid vector is read, so no index is formed from a position and any context will do.
+// Every loop is bounded by a constant or by an argument the entry points have range-checked: fo maxit <= XPIC_FO_MAXIT,
+// 1 <= dk maxit <= XPIC_MODEL_DK_MAXIT, at most XPIC_MODEL_LAUNCH_STEPS steps per launch.  Every global index is formed
+// under q < n, row < nsamp or i < nown.  The staging is batch.h's batch_trace_open with the "never" policy.
+#include <algorithm>
+#include <cmath>
+#include <vector>
+
+#include "batch.h"
+#include "common.h"
+#include "device_common.h"
+#include "field_model.h"
+#include "ie_shape.h"
+#include "trace_open.h"
+
+// as in full_orbit.hip and drift_kinetic.hip: contracted per source expression only
+#pragma clang fp contract(on)
+
+#include "full_orbit_step.h"
+#include "drift_kinetic_step.h"
+
+namespace xpic {
+
+namespace {
+
+constexpr int kBlock = kLaneBlock; // batch.h: lane_grid launches workgroups of this size
+constexpr int kLaunchSteps = XPIC_MODEL_LAUNCH_STEPS;
+static_assert(kLaunchSteps <= kOpenRows, "open_tally holds one row per step of a launch");
+
+// the analytic field source of the step functions (full_orbit_step.h: FOGrid, drift_kinetic_step.h: DKGrid)
+struct ModelSource {
+  const xpic_field_model& m;
+  __device__ inline void dk(const double* rn, const double*, double* Ep, double* Bp, double* gBp) const
+  {
+    model_fields(m, rn, Ep, Bp, gBp);
+  }
+  __device__ inline void at(const double* r, double* Ep, double* Bp) const
+  {
+    double gBp[3];
+    model_fields(m, r, Ep, Bp, gBp);
+  }
+  __device__ inline void segment(const double* rn, const double* r0, double* Ep, double* Bp) const
+  {
+    const double rm[3] = {(r0[0] + rn[0]) / 2, (r0[1] + rn[1]) / 2, (r0[2] + rn[2]) / 2};
+    double gBp[3];
+    model_fields(m, rm, Ep, Bp, gBp);
+  }
+};
+
+__device__ inline void fo_load(const double* __restrict__ s, long n, long q, FOPoint& p)
+{
+  p.r[0] = s[q]; p.r[1] = s[n + q]; p.r[2] = s[2 * n + q];
+  p.p[0] = s[3 * n + q]; p.p[1] = s[4 * n + q]; p.p[2] = s[5 * n + q];
+}
+__device__ inline void fo_store(double* __restrict__ s, long n, long q, const FOPoint& p)
+{
+  s[q] = p.r[0]; s[n + q] = p.r[1]; s[2 * n + q] = p.r[2];
+  s[3 * n + q] = p.p[0]; s[4 * n + q] = p.p[1]; s[5 * n + q] = p.p[2];
+}
+
+__global__ void __launch_bounds__(kBlock) k_model_fields(xpic_field_model M, long n, const double* __restrict__ r3,
+  double* __restrict__ out)
+{
+  const long q = (long)blockIdx.x * kBlock + threadIdx.x;
+  if (q >= n) return;
+  const double r[3] = {r3[3 * q], r3[3 * q + 1], r3[3 * q + 2]};
+  double E[3], B[3], gB[3];
+  model_fields(M, r, E, B, gB);
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    out[3 * q + c] = E[c];
+    out[3 * n + 3 * q + c] = B[c];
+    out[6 * n + 3 * q + c] = gB[c];
+  }
+}
+
+// FieldContext::initialize (drift_kinetic_push.h:191-199), one thread per owned node as k_mirror (commands.hip): all
+// three components of node (x, y, z) are the model at (x dx, y dy, z dz); a null vector is skipped
+__global__ void __launch_bounds__(kBlock) k_set_model_field(GridDev g, xpic_field_model M, double* E, double* B, double* gB)
+{
+  const long i = (long)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= g.nown) return;
+  const int x = (int)(i % g.nx), y = (int)((i / g.nx) % g.ny), zl = (int)(i / g.plane);
+  const int z = g.z0 + zl;
+  const long nd = g.node(x, y, g.wz(zl));
+  const double r[3] = {x * g.dx, y * g.dy, z * g.dz};
+  double Ep[3], Bp[3], gBp[3];
+  model_fields(M, r, Ep, Bp, gBp);
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    if (E) E[c * g.cstride + nd] = Ep[c];
+    if (B) B[c * g.cstride + nd] = Bp[c];
+    if (gB) gB[c * g.cstride + nd] = gBp[c];
+  }
+}
+
+// k_fo_trace_open (full_orbit.hip) on the model; R.kind < 0: no region rule
+template <bool CN>
+__global__ void __launch_bounds__(kBlock) k_model_fo_trace(GridDev g, xpic_field_model M, xpic_fo_params P, OpenRegion R,
+  long n, double* __restrict__ s, long first, int nsteps, long sample_every, long nsamp, double* __restrict__ samples,
+  long long* __restrict__ it_sum, int* __restrict__ it_max, long long* __restrict__ exit_step, unsigned long long* alive,
+  unsigned long long* removed)
+{
+  const long q = (long)blockIdx.x * kBlock + threadIdx.x;
+  const bool live = q < n && exit_step[q] < 0;
+  const int ns = nsteps < kLaunchSteps ? nsteps : kLaunchSteps;
+  const ModelSource src{M};
+  int done = 0;
+  bool gone = false;
+  if (live) {
+    FOPoint pn;
+    fo_load(s, n, q, pn);
+    long long total = CN ? it_sum[q] : 0;
+    int most = CN ? it_max[q] : 0;
+    for (; done < ns; ++done) {
+      if (R.kind >= 0 && !open_keep(g, R, pn.r)) { gone = true; break; }
+      int it = 0;
+      if (CN) {
+        const FOPoint p0 = pn;
+        it = fo_cn_process(src, P.qm, P.dt, P.atol, P.rtol, P.maxit, pn, p0);
+      }
+      else fo_step(P.scheme, src, P.qm, P.dt, pn);
+      total += it;
+      most = it > most ? it : most;
+      const long step = first + done + 1;
+      if (samples && step % sample_every == 0) {
+        const long row = step / sample_every - 1;
+        if (row < nsamp) fo_store(samples + row * 6 * n, n, q, pn);
+      }
+    }
+    fo_store(s, n, q, pn);
+    if (CN) { it_sum[q] = total; it_max[q] = most; }
+    if (gone) exit_step[q] = R.step0 + first + done;
+  }
+  open_tally<kBlock>(live, gone, first + done, first, ns, sample_every, nsamp, alive, removed);
+}
+
+// k_dk_trace_open (drift_kinetic.hip) on the model
+__global__ void __launch_bounds__(kBlock) k_model_dk_trace(GridDev g, xpic_field_model M, xpic_dk_params P, OpenRegion R,
+  long n, double* __restrict__ s, long first, int nsteps, long sample_every, long nsamp, double* __restrict__ samples,
+  long long* __restrict__ it_total, int* __restrict__ it_max, long long* __restrict__ exit_step, unsigned long long* alive,
+  unsigned long long* removed)
+{
+  const long q = (long)blockIdx.x * kBlock + threadIdx.x;
+  const bool live = q < n && exit_step[q] < 0;
+  const int ns = nsteps < kLaunchSteps ? nsteps : kLaunchSteps;
+  const ModelSource src{M};
+  int done = 0;
+  bool gone = false;
+  if (live) {
+    DKPoint p0, pn;
+    dk_load(s, n, q, pn);
+    long long total = it_total[q];
+    int most = it_max[q];
+    for (; done < ns; ++done) {
+      if (R.kind >= 0 && !open_keep(g, R, pn.r)) { gone = true; break; }
+      p0 = pn;
+      const int it = dk_process(src, P, p0, pn);
+      total += it;
+      most = it > most ? it : most;
+      const long step = first + done + 1;
+      if (samples && step % sample_every == 0) {
+        const long row = step / sample_every - 1;
+        if (row < nsamp) dk_store(samples + row * 6 * n, n, q, pn);
+      }
+    }
+    dk_store(s, n, q, pn);
+    it_total[q] = total;
+    it_max[q] = most;
+    if (gone) exit_step[q] = R.step0 + first + done;
+  }
+  open_tally<kBlock>(live, gone, first + done, first, ns, sample_every, nsamp, alive, removed);
+}
+
+int model_ok(const char* who, const xpic_field_model* model)
+{
+  const char* bad = model_check(model);
+  XPIC_CHECK(!bad, std::string(who) + ": " + (bad ? bad : ""));
+  return 0;
+}
+
+// open_region (trace_open.h) with XPIC_GEOM_NONE allowed and `compact` not read
+int model_region(const char* who, const xpic_trace_region* in, OpenRegion* R)
+{
+  XPIC_CHECK(in, std::string(who) + ": region is null");
+  XPIC_CHECK(in->geometry == XPIC_GEOM_NONE || in->geometry == XPIC_GEOM_BOX || in->geometry == XPIC_GEOM_CYLINDER,
+    std::string(who) + ": unknown geometry kind");
+  XPIC_CHECK(in->step0 >= 0, std::string(who) + ": step0 is negative");
+  R->kind = in->geometry;
+  for (int i = 0; i < 7; ++i) R->a[i] = in->geom[i];
+  R->step0 = in->step0;
+  return 0;
+}
+
+// The checks and the driver the two traces share, after their own checks of params.  Under XPIC_GEOM_NONE the optional
+// outputs that are null get stand-ins here, so the kernel and batch_trace_open see one shape of call.
+template <class Launch>
+int model_trace(xpic_ctx* ctx, const std::string& who, const char* label, int64_t n, bool counters, int64_t steps,
+  int64_t sample_every, double* state_6, double* samples, int64_t* it_sum, int* it_max, const OpenRegion& R,
+  int64_t* exit_step, int64_t* alive, int64_t* removed, Launch launch)
+{
+  const bool open = R.kind >= 0;
+  XPIC_CHECK(n <= ((int64_t)1 << 36), who + ": n is larger than 2^36");
+  XPIC_CHECK(steps >= 0, who + ": steps is negative");
+  XPIC_CHECK((!samples && !alive) || sample_every >= 1, who + ": sample_every must be >= 1 when samples or alive are asked for");
+  XPIC_CHECK(state_6, who + ": the particle array is null");
+  XPIC_CHECK(exit_step || !open, who + ": exit_step is null");
+  XPIC_CHECK(removed || !open, who + ": removed is null");
+  XPIC_CHECK((it_sum && it_max) || !counters, who + ": an iteration counter is null");
+  int64_t nsamp;
+  XPIC_CHECK(trace_sample_bytes(samples ? n : 0, steps, sample_every, samples || alive, &nsamp) >= 0,
+    who + ": the sample buffer (48 n steps / sample_every bytes) is too large");
+  if (removed) *removed = 0;
+  if (n == 0 || steps == 0) return 0;
+  std::vector<int64_t> ex_own;
+  if (!exit_step) {
+    ex_own.assign((size_t)n, -1);
+    exit_step = ex_own.data();
+  }
+  int64_t rm_own = 0;
+  XPIC_CALL(batch_trace_open(ctx, label, label, kLaunchSteps, n, steps, sample_every, nsamp, counters, XPIC_COMPACT_NEVER,
+    R.step0, state_6, samples, it_sum, it_max, exit_step, alive, removed ? removed : &rm_own,
+    [&](double* s, const int64_t*, long, long first, int ns, double* sm, long long* sum, int* mx, long long* ex,
+      unsigned long long* al, unsigned long long* rm) { launch(s, first, ns, (long)nsamp, sm, sum, mx, ex, al, rm); }));
+  if (!counters) {
+    if (it_sum) std::fill(it_sum, it_sum + n, (int64_t)0);
+    if (it_max) std::fill(it_max, it_max + n, 0);
+  }
+  return 0;
+}
+
+}  // namespace
+
+}  // namespace xpic
+
+using namespace xpic;
+
+extern "C" {
+
+int xpic_model_fields(xpic_ctx* ctx, const xpic_field_model* model, int64_t n, const double* r3, double* E3, double* B3,
+  double* gradB3)
+{
+  XPIC_CHECK(ctx != nullptr, "null context");
+  XPIC_CALL(model_ok("model_fields", model));
+  XPIC_CHECK(n >= 0, "model_fields: n is negative");
+  XPIC_CHECK(n <= ((int64_t)1 << 36), "model_fields: n is larger than 2^36");
+  XPIC_CHECK(r3 && E3 && B3 && gradB3, "model_fields: a null array");
+  if (n == 0) return 0;
+  DevScratch<double> a, o;
+  XPIC_CALL(a.alloc(3 * n)); XPIC_CALL(o.alloc(9 * n));
+  XPIC_CALL(upload(a, r3, 3 * n, ctx->stream));
+  {
+    Timed t(ctx, "model_fields");
+    hipLaunchKernelGGL(k_model_fields, lane_grid(n), dim3(kBlock), 0, ctx->stream, *model, (long)n, (const double*)a.p, o.p);
+    XPIC_HIP(hipGetLastError());
+  }
+  XPIC_CALL(download(E3, o, 3 * n, ctx->stream));
+  XPIC_CALL(download(B3, o, 3 * n, ctx->stream, 3 * n));
+  XPIC_CALL(download(gradB3, o, 3 * n, ctx->stream, 6 * n));
+  XPIC_HIP(hipStreamSynchronize(ctx->stream));
+  return 0;
+}
+
+int xpic_set_model_field(xpic_ctx* ctx, const xpic_field_model* model, int E_field, int B_field, int gradB_field)
+{ // FieldContext::initialize, tests/drift_kinetic_push/drift_kinetic_push.h:176-209
+  XPIC_CHECK(ctx != nullptr, "null context");
+  XPIC_CALL(model_ok("set_model_field", model));
+  double* v[3];
+  const int id[3] = {E_field, B_field, gradB_field};
+  for (int k = 0; k < 3; ++k) {
+    XPIC_CHECK(id[k] < 0 || (id[k] < XPIC_NFIELDS && ctx->field[id[k]]), "set_model_field: not an allocated field id");
+    v[k] = id[k] < 0 ? nullptr : ctx->field[id[k]];
+  }
+  XPIC_CHECK(!(v[0] && v[0] == v[1]) && !(v[0] && v[0] == v[2]) && !(v[1] && v[1] == v[2]),
+    "set_model_field: the same field id twice");
+  Timed t(ctx, "set_model_field");
+  hipLaunchKernelGGL(k_set_model_field, lane_grid(std::max<int64_t>(ctx->g.nown, 1)), dim3(kBlock), 0, ctx->stream, ctx->g,
+    *model, v[0], v[1], v[2]);
+  XPIC_HIP(hipGetLastError());
+  XPIC_HIP(hipStreamSynchronize(ctx->stream));
+  return 0;
+}
+
+int xpic_model_full_orbit_trace(xpic_ctx* ctx, int64_t n, const xpic_fo_params* params, const xpic_field_model* model,
+  int64_t steps, int64_t sample_every, double* p_6, double* samples, int64_t* iterations_sum, int* iterations_max,
+  const xpic_trace_region* region, int64_t* exit_step, int64_t* alive, int64_t* removed)
+{
+  const std::string who = "model_full_orbit_trace";
+  XPIC_CHECK(ctx != nullptr, "null context");
+  XPIC_CHECK(n >= 0, who + ": n is negative");
+  XPIC_CHECK(params, who + ": params is null");
+  XPIC_CHECK(params->scheme >= 0 && params->scheme < XPIC_FO_NSCHEMES, who + ": unknown scheme id");
+  const bool cn = params->scheme == XPIC_FO_CN;
+  if (cn) XPIC_CHECK(params->maxit >= 1 && params->maxit <= XPIC_FO_MAXIT, who + ": maxit must be within 1 .. 64");
+  XPIC_CALL(model_ok(who.c_str(), model));
+  OpenRegion R;
+  XPIC_CALL(model_region(who.c_str(), region, &R));
+  return model_trace(ctx, who, "model_fo_trace", n, cn, steps, sample_every, p_6, samples, iterations_sum, iterations_max, R,
+    exit_step, alive, removed,
+    [&](double* s, long first, int ns, long nsamp, double* sm, long long* sum, int* mx, long long* ex, unsigned long long* al,
+      unsigned long long* rm) {
+      hipLaunchKernelGGL(cn ? k_model_fo_trace<true> : k_model_fo_trace<false>, lane_grid(n), dim3(kBlock), 0, ctx->stream,
+        ctx->g, *model, *params, R, (long)n, s, first, ns, (long)sample_every, nsamp, sm, sum, mx, ex, al, rm);
+    });
+}
+
+int xpic_model_drift_kinetic_trace(xpic_ctx* ctx, int64_t n, const xpic_dk_params* params, const xpic_field_model* model,
+  int64_t steps, int64_t sample_every, double* state_6, double* samples, int64_t* iterations_total, int* iterations_max,
+  const xpic_trace_region* region, int64_t* exit_step, int64_t* alive, int64_t* removed)
+{
+  const std::string who = "model_drift_kinetic_trace";
+  XPIC_CHECK(ctx != nullptr, "null context");
+  XPIC_CHECK(n >= 0, who + ": n is negative");
+  XPIC_CHECK(params, who + ": params is null");
+  XPIC_CHECK(params->maxit >= 1 && params->maxit <= XPIC_MODEL_DK_MAXIT, who + ": maxit must be within 1 .. 1024");
+  XPIC_CHECK(params->mp != 0.0, who + ": mp must not be 0");
+  XPIC_CALL(model_ok(who.c_str(), model));
+  OpenRegion R;
+  XPIC_CALL(model_region(who.c_str(), region, &R));
+  return model_trace(ctx, who, "model_dk_trace", n, true, steps, sample_every, state_6, samples, iterations_total,
+    iterations_max, R, exit_step, alive, removed,
+    [&](double* s, long first, int ns, long nsamp, double* sm, long long* sum, int* mx, long long* ex, unsigned long long* al,
+      unsigned long long* rm) {
+      hipLaunchKernelGGL(k_model_dk_trace, lane_grid(n), dim3(kBlock), 0, ctx->stream, ctx->g, *model, *params, R, (long)n, s,
+        first, ns, (long)sample_every, nsamp, sm, sum, mx, ex, al, rm);
+    });
+}
+
+}  // extern "C"
