@@ -579,6 +579,57 @@ int xpic_model_drift_kinetic_trace(xpic_ctx* ctx, int64_t n, const xpic_dk_param
   int64_t steps, int64_t sample_every, double* state_6, double* samples, int64_t* iterations_total, int* iterations_max,
   const xpic_trace_region* region, int64_t* exit_step, int64_t* alive, int64_t* removed);
 
+/* ---- triplet trace: the whole time loop of the reference's grid tests
+ * (tests/drift_kinetic_push/drift_kinetic_grid_boris_ex1..4.cpp, ex1.cpp:79-98) for n triplets, with all seven maxima of
+ * ComparisonStats (tests/drift_kinetic_push/drift_kinetic_push.h:253-329) reduced on the device.  Triplet q is three
+ * records, all read and overwritten: the Point p_6[6 q ..] (a full orbit on the model, fo: its scheme and tolerances), the
+ * PointByField state_model_6[6 q ..] (a guiding centre on the model) and the PointByField state_grid_6[6 q ..] (a guiding
+ * centre on the context's XPIC_E / XPIC_B, gradB_field as in xpic_drift_kinetic_trace -- the grid xpic_set_model_field
+ * fills, though nothing here requires that).  dk serves both guiding centres.  One step, in the reference's order:
+ *   1. DriftKineticPush::process of the analytic centre, the model at rn                 (push_analytical, ex1.cpp:85)
+ *   2. DriftKineticPush::process of the grid centre, DriftKineticEsirkepov::interpolate  (push_grid, :86)
+ *   3. the orbit's step on the model with fo->scheme: boris_step (drift_kinetic_push.h:280-291) is XPIC_FO_EB2B; all 18
+ *      ids are accepted, XPIC_FO_CN with the model at the midpoint as in xpic_model_full_orbit_trace           (:87)
+ *   4. Ba, gBa = the model at the analytic centre's new position                                                (:89-90)
+ *   5. Bg, gBg = DriftKineticEsirkepov::interpolate(rn = the grid centre after the step, r0 = before it); gBg = 0 with
+ *      gradB_field == -1                                                                                        (:92-93)
+ *   6. update_comparison_stats (drift_kinetic_push.h:293-329), statement by statement:
+ *        err_B      = |Ba - Bg|                 err_gradB = |gBa - gBg|            err_pos = |model.r - grid.r|
+ *        err_z      = |grid.z - fo.z|
+ *        err_par    = |grid.p_parallel - |fo.p.parallel_to(Ba)||
+ *        err_mu     = |grid.mu_p - 0.5 mp |fo.p.transverse_to(Ba)|^2 / |Ba||
+ *        err_energy = |0.5 (grid.p_perp^2 + grid.p_parallel^2) - 0.5 fo.p^2|
+ * The last four are xpic_paired_trace's with one difference: the orbit's momentum is projected on B_analytical, as the
+ * reference does (:314), where xpic_paired_trace, which has no analytical member, projects on B_grid.  Every maximum is
+ * m = (m < e) ? e : m: an error that is not a number leaves it alone, an infinite one is kept; |B| = 0 gets no special case.
+ * stats_7 [n][XPIC_TRIPLET_NSTATS] (required, in and out): each triplet's running maxima {B, gradB, pos, z, p_parallel, mu,
+ * energy}, ComparisonStats' order, read as the maxima so far.  curve_7 [steps / sample_every][7] (or NULL; needs
+ * sample_every >= 1): curve_7[k][j] = the maximum over the triplets of error j at step (k + 1) sample_every of this call,
+ * 0 where no triplet has an error > 0; written, not accumulated.  dkm_* (required), dkg_* (required with the grid) and
+ * fo_* (XPIC_FO_CN: required; otherwise optional and zeroed) are the counters of the three closed traces.
+ * with_grid == 0 is the grid-less pair, the analytic centre beside the orbit (drift_kinetic_push_ex9.cpp): there is no
+ * grid member; state_grid_6, dkg_* and gradB_field are not read (NULL / -1 will do); statistics 0 .. 2 are neither read
+ * nor written, in stats_7 and (left 0) in curve_7; statistics 3 .. 6 have the analytic centre in the grid centre's
+ * place; no grid vector is read, so any context is accepted, z-slabs included.  With with_grid != 0: single z-slab contexts
+ * only, as for xpic_paired_trace.
+ * Checks: those of xpic_paired_trace (dk->maxit within 1 .. XPIC_TRIPLET_DK_MAXIT, fo->dt == dk->dt, fo->qm == dk->qm) and
+ * those of the model traces on `model`.  n == 0 succeeds and touches nothing; steps == 0 returns the inputs.  Launches of
+ * at most XPIC_TRIPLET_LAUNCH_STEPS steps.  A triplet is never removed: the region rule is not part of this call.
+ * Guarantees, all bit for bit: (a) each member is its closed trace over the same steps -- state_model_6 and dkm_* those of
+ * xpic_model_drift_kinetic_trace with XPIC_GEOM_NONE, state_grid_6 and dkg_* those of xpic_drift_kinetic_trace, p_6 and
+ * fo_* those of xpic_model_full_orbit_trace with XPIC_GEOM_NONE; (b) a call of s1 + s2 steps equals a call of s1 steps
+ * followed by one of s2 steps fed the first call's states and stats_7, in all states and in stats_7; (c) curve_7[k][j] is
+ * the maximum over q of the error that triplet q alone has at that step; (d) with with_grid == 0, columns 0 .. 2 of stats_7
+ * come back exactly as they went in. */
+#define XPIC_TRIPLET_NSTATS 7 /* {B, gradB, pos, z, p_parallel, mu, energy}: ComparisonStats' order */
+#define XPIC_TRIPLET_LAUNCH_STEPS 64
+#define XPIC_TRIPLET_DK_MAXIT 1024
+int xpic_triplet_trace(xpic_ctx* ctx, int64_t n, const xpic_fo_params* fo, const xpic_dk_params* dk,
+  const xpic_field_model* model, int with_grid, int gradB_field, int64_t steps, int64_t sample_every, double* p_6,
+  double* state_model_6, double* state_grid_6, double* stats_7, double* curve_7, int64_t* fo_iterations_sum,
+  int* fo_iterations_max, int64_t* dkm_iterations_total, int* dkm_iterations_max, int64_t* dkg_iterations_total,
+  int* dkg_iterations_max);
+
 /* ---- z-slab decomposition (DMDA da_processors_z = nranks; src/utils/world.cpp:36-38).  A context created with
  * nranks > 1 owns planes [rank*nz/nranks, (rank+1)*nz/nranks) and must be given a communicator before any
  * call that moves data between slabs (steps, solves, operator applies, re-binning, energy): those calls are

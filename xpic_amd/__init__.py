@@ -34,7 +34,7 @@ SYMBOLS = [
     "xpic_implicit_esirkepov_decompose", "xpic_drift_kinetic_interpolate", "xpic_drift_kinetic_push",
     "xpic_drift_kinetic_trace", "xpic_full_orbit_push", "xpic_full_orbit_trace", "xpic_full_orbit_trace_open",
     "xpic_drift_kinetic_trace_open", "xpic_paired_trace", "xpic_model_fields", "xpic_set_model_field",
-    "xpic_model_full_orbit_trace", "xpic_model_drift_kinetic_trace", "xpic_charge_collect", "xpic_charge_columns", "xpic_comm_rccl_unique_id", "xpic_comm_init_rccl", "xpic_comm_init_callbacks", "xpic_comm_size", "xpic_comm_peer_export", "xpic_comm_peer_import",
+    "xpic_model_full_orbit_trace", "xpic_model_drift_kinetic_trace", "xpic_triplet_trace", "xpic_charge_collect", "xpic_charge_columns", "xpic_comm_rccl_unique_id", "xpic_comm_init_rccl", "xpic_comm_init_callbacks", "xpic_comm_size", "xpic_comm_peer_export", "xpic_comm_peer_import",
     "xpic_profile_enable", "xpic_profile_reset", "xpic_profile_get", "xpic_probe_copy_bandwidth",
 ]
 
@@ -152,6 +152,10 @@ MODEL_KINDS = {"uniform": 0, "linear": 1, "quadratic_mirror": 2, "gaussian_mirro
 GEOM_NONE = -1             # include/xpic_hip.h: XPIC_GEOM_NONE
 MODEL_LAUNCH_STEPS = 64    # include/xpic_hip.h: XPIC_MODEL_LAUNCH_STEPS
 MODEL_DK_MAXIT = 1024      # include/xpic_hip.h: XPIC_MODEL_DK_MAXIT
+TRIPLET_LAUNCH_STEPS = 64  # include/xpic_hip.h: XPIC_TRIPLET_LAUNCH_STEPS
+TRIPLET_DK_MAXIT = 1024    # include/xpic_hip.h: XPIC_TRIPLET_DK_MAXIT
+# the columns of stats_7 and curve_7 (xpic_triplet_trace), XPIC_TRIPLET_NSTATS of them: ComparisonStats' order
+TRIPLET_STATS = ("B", "gradB", "pos", "z", "p_parallel", "mu", "energy")
 
 
 def field_model(kind, **params):
@@ -177,6 +181,17 @@ class PairedTrace(collections.namedtuple(
     stats [n][4], each pair's largest errors over the steps, and curve [steps // sample_every][4] (None without
     sample_every), the largest error over the pairs at every sample_every-th step, both with the columns PAIR_STATS; the
     iteration counters of the two closed traces."""
+    __slots__ = ()
+
+
+class TripletTrace(collections.namedtuple(
+        "TripletTrace", "p state_model state_grid stats curve fo_iterations_sum fo_iterations_max dkm_iterations_total "
+        "dkm_iterations_max dkg_iterations_total dkg_iterations_max")):
+    """What Context.triplet_trace returns, PairedTrace extended: the full orbits p, the guiding centres on the model
+    state_model and on the grid state_grid, [n][6] each, after the steps; stats [n][7], each triplet's largest errors over
+    the steps, and curve [steps // sample_every][7] (None without sample_every), both with the columns TRIPLET_STATS; the
+    iteration counters of the three closed traces.  For the grid-less pair state_grid and the dkg counters are None, and
+    columns 0 .. 2 of stats and curve are what went in and 0."""
     __slots__ = ()
 
 
@@ -833,6 +848,38 @@ class Context:
             mx.ctypes.data_as(C.POINTER(C.c_int)), C.byref(reg), None if bare else ex.ctypes.data_as(i64),
             alive.ctypes.data_as(i64) if sample_every else None, None if bare else C.byref(removed)))
         return OpenTrace(state, samples, ex, alive, removed.value, tot, mx)
+
+    # ---- triplet trace (include/xpic_hip.h: xpic_triplet_trace): model_drift_kinetic_trace of state_model,
+    # drift_kinetic_trace of state_grid and model_full_orbit_trace of p in lock-step, with all seven maxima of the
+    # reference's ComparisonStats kept on the device; the grid is the context's (set_model_field fills it from the model)
+    def triplet_trace(self, p, state_model, state_grid, steps, scheme, qm, mp, dt, model, gradB_field=None, sample_every=0,
+                      stats=None, atol=1e-7, rtol=1e-7, maxit=30, eps=1e-12, delta=1e-12, dk_maxit=30):
+        """-> TripletTrace.  state_grid=None selects the grid-less pair (state_model beside p; gradB_field is not read).
+        stats: the running maxima a previous call returned (None: zeros), so that calls compose; sample_every: the curve's
+        stride (0: no curve); maxit is the full orbit's (CN), dk_maxit the guiding centres'"""
+        p = np.array(p, dtype=np.float64).reshape(-1, 6)  # copies: the call works in place
+        sm = np.array(state_model, dtype=np.float64).reshape(-1, 6)
+        grid = state_grid is not None
+        sg = np.array(state_grid, dtype=np.float64).reshape(-1, 6) if grid else None
+        n = p.shape[0]
+        if sm.shape[0] != n or (grid and sg.shape[0] != n):
+            raise XpicError("triplet_trace: p, state_model and state_grid hold different numbers of particles")
+        stats = np.zeros((n, 7)) if stats is None else np.array(stats, dtype=np.float64).reshape(n, 7)
+        nsamp = max(int(steps), 0) // int(sample_every) if sample_every else 0
+        curve = np.zeros((nsamp, 7)) if sample_every else None
+        fsum, fmax = np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int32)
+        mtot, mmax = np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int32)
+        gtot, gmax = (np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int32)) if grid else (None, None)
+        F = self._fo_params(scheme, qm, dt, atol, rtol, maxit)
+        D = self._dk_params(qm, mp, dt, eps, delta, dk_maxit)
+        i64, i32 = C.POINTER(C.c_int64), C.POINTER(C.c_int)
+        self._ck(self.L.xpic_triplet_trace(
+            self.h, C.c_int64(n), C.byref(F), C.byref(D), None if model is None else C.byref(model), int(grid),
+            -1 if gradB_field is None or not grid else int(gradB_field), C.c_int64(int(steps)), C.c_int64(int(sample_every)),
+            _dp(p), _dp(sm), _dp(sg) if grid else None, _dp(stats), _dp(curve) if sample_every else None,
+            fsum.ctypes.data_as(i64), fmax.ctypes.data_as(i32), mtot.ctypes.data_as(i64), mmax.ctypes.data_as(i32),
+            gtot.ctypes.data_as(i64) if grid else None, gmax.ctypes.data_as(i32) if grid else None))
+        return TripletTrace(p, sm, sg, stats, curve, fsum, fmax, mtot, mmax, gtot, gmax)
 
     def charge_collect(self):
         self._ck(self.L.xpic_charge_collect(self.h))

@@ -1,6 +1,7 @@
 // batch.h -- the host side that the batch particle calls share (eccapfim.hip, drift_kinetic.hip, full_orbit.hip,
 // paired_trace.hip): host arrays of particles are staged on the device, a kernel runs one lane per particle, the results
-// are copied back.  batch_pair_trace is batch_trace for two batches advanced side by side (paired_trace.hip).
+// are copied back.  batch_pair_trace is batch_trace for two batches advanced side by side (paired_trace.hip),
+// batch_triplet_trace for three (triplet_trace.hip).
 // batch_trace_open is batch_trace for the open traces (trace_open.h, trace_open.hip): exit steps, alive counts, and the
 // list of live particles between launches.
 // DevScratch also owns every other device buffer that lives for one call (fields.hip, particles.hip, commands.hip,
@@ -231,6 +232,81 @@ int batch_pair_trace(xpic_ctx* c, const char* label, int launch_steps, int64_t n
   to_aos(hf.data(), n, p_6);
   to_aos(hd.data(), n, state_6);
   to_aos(hst.data(), n, stats_4, 4);
+  return 0;
+}
+
+// batch_pair_trace for three members per lane (triplet_trace.hip): a full orbit p_6, a guiding centre on the
+// analytic model state_model_6 and, with `with_grid`, one on the grid state_grid_6, `steps` steps of n > 0 triplets in
+// place.  The running maxima stats_7 [n][7] are in and out: with the grid all seven columns are staged as [7][n]; without
+// it only columns 3 .. 6 are, as [4][n], and columns 0 .. 2 of the caller's array are neither read nor written.  curve_7
+// [nsamp][7] (null with nsamp == 0) is zeroed on the device and written by the kernel's atomic maxima.  The model
+// centre's counters always, the grid centre's with `with_grid`, the orbit's with `fo_counters`, all zeroed here.
+// launch(fo_s, dm_s, dg_s, stats, first, nsteps, curve, fo_sum, fo_max, dm_sum, dm_max, dg_sum, dg_max) starts the kernel
+// for steps first + 1 .. first + nsteps (null: dg_s, dg_sum, dg_max without the grid; curve without one; fo_sum, fo_max
+// without fo counters); each launch is timed under `label`.  Everything comes back once, after the last launch.
+template <class Launch>
+int batch_triplet_trace(xpic_ctx* c, const char* label, int launch_steps, int64_t n, int64_t steps, int64_t nsamp,
+  bool fo_counters, bool with_grid, double* p_6, double* state_model_6, double* state_grid_6, double* stats_7,
+  double* curve_7, int64_t* fo_sum, int* fo_max, int64_t* dm_sum, int* dm_max, int64_t* dg_sum, int* dg_max, Launch launch)
+{
+  const size_t row = (size_t)6 * n;                  // doubles of one state
+  const int j0 = with_grid ? 0 : 3, w = 7 - j0;      // the columns of stats_7 that travel
+  std::vector<double> hf, hm, hg, hst((size_t)w * n);
+  to_soa(p_6, n, hf);
+  to_soa(state_model_6, n, hm);
+  if (with_grid) to_soa(state_grid_6, n, hg);
+  for (int64_t q = 0; q < n; ++q)
+    for (int k = 0; k < w; ++k) hst[(size_t)k * n + q] = stats_7[7 * q + j0 + k];
+  DevScratch<double> fs, ms, gs, st, cv;
+  DevScratch<int64_t> ftot, mtot, gtot;
+  DevScratch<int> fmx, mmx, gmx;
+  XPIC_CALL(fs.alloc(row)); XPIC_CALL(ms.alloc(row)); XPIC_CALL(st.alloc((size_t)w * n));
+  XPIC_CALL(mtot.alloc(n)); XPIC_CALL(mmx.alloc(n));
+  XPIC_CALL(zero(mtot, n, c->stream)); XPIC_CALL(zero(mmx, n, c->stream));
+  if (with_grid) {
+    XPIC_CALL(gs.alloc(row)); XPIC_CALL(gtot.alloc(n)); XPIC_CALL(gmx.alloc(n));
+    XPIC_CALL(zero(gtot, n, c->stream)); XPIC_CALL(zero(gmx, n, c->stream));
+  }
+  if (fo_counters) {
+    XPIC_CALL(ftot.alloc(n)); XPIC_CALL(fmx.alloc(n));
+    XPIC_CALL(zero(ftot, n, c->stream)); XPIC_CALL(zero(fmx, n, c->stream));
+  }
+  if (nsamp > 0) {
+    XPIC_CALL(cv.alloc(7 * nsamp));
+    XPIC_CALL(zero(cv, 7 * nsamp, c->stream));
+  }
+  XPIC_CALL(upload(fs, hf.data(), row, c->stream));
+  XPIC_CALL(upload(ms, hm.data(), row, c->stream));
+  if (with_grid) XPIC_CALL(upload(gs, hg.data(), row, c->stream));
+  XPIC_CALL(upload(st, hst.data(), (size_t)w * n, c->stream));
+  for (int64_t first = 0; first < steps; first += launch_steps) {
+    const int ns = (int)std::min<int64_t>(launch_steps, steps - first);
+    Timed t(c, label);
+    launch(fs.p, ms.p, gs.p, st.p, (long)first, ns, (unsigned long long*)cv.p, (long long*)ftot.p, fmx.p, (long long*)mtot.p,
+      mmx.p, (long long*)gtot.p, gmx.p);
+    XPIC_HIP(hipGetLastError());
+  }
+  XPIC_CALL(download(hf.data(), fs, row, c->stream));
+  XPIC_CALL(download(hm.data(), ms, row, c->stream));
+  if (with_grid) XPIC_CALL(download(hg.data(), gs, row, c->stream));
+  XPIC_CALL(download(hst.data(), st, (size_t)w * n, c->stream));
+  XPIC_CALL(download(dm_sum, mtot, n, c->stream));
+  XPIC_CALL(download(dm_max, mmx, n, c->stream));
+  if (with_grid) {
+    XPIC_CALL(download(dg_sum, gtot, n, c->stream));
+    XPIC_CALL(download(dg_max, gmx, n, c->stream));
+  }
+  if (fo_counters) {
+    XPIC_CALL(download(fo_sum, ftot, n, c->stream));
+    XPIC_CALL(download(fo_max, fmx, n, c->stream));
+  }
+  if (nsamp > 0) XPIC_CALL(download(curve_7, cv, 7 * nsamp, c->stream));
+  XPIC_HIP(hipStreamSynchronize(c->stream));
+  to_aos(hf.data(), n, p_6);
+  to_aos(hm.data(), n, state_model_6);
+  if (with_grid) to_aos(hg.data(), n, state_grid_6);
+  for (int64_t q = 0; q < n; ++q)
+    for (int k = 0; k < w; ++k) stats_7[7 * q + j0 + k] = hst[(size_t)k * n + q];
   return 0;
 }
 

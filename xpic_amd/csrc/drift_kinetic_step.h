@@ -151,7 +151,7 @@ __device__ inline void dk_v_terms(const xpic_dk_params& P, const DKPoint& p0, do
 
 // The field source of dk_process: what the reference's set_fields_callback is to DriftKineticPush.  A source has
 //   void dk(const double* rn, const double* r0, double* Ep, double* Bp, double* gBp) const
-// DKGrid is the grid of the context (dk_fields); model_trace.hip has the analytic one.
+// DKGrid is the grid of the context (dk_fields); model_source.h has the analytic one.
 template <bool GRAD>
 struct DKGrid {
   const GridDev& g;

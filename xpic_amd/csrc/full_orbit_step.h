@@ -203,7 +203,7 @@ __device__ inline void fo_update_vEB(double dt, double qm, const double* Ep, con
 // CrankNicolsonPush.  A source has
 //   void at(const double* r, double* Ep, double* Bp) const                            the fields of a kick at r
 //   void segment(const double* rn, const double* r0, double* Ep, double* Bp) const    those of a step r0 -> rn
-// FOGrid is the grid of the context (fo_gather, fo_gather_segment); model_trace.hip has the analytic one.
+// FOGrid is the grid of the context (fo_gather, fo_gather_segment); model_source.h has the analytic one.
 struct FOGrid {
   const GridDev& g;
   const double* __restrict__ E;

@@ -27,6 +27,7 @@
 
 #include "full_orbit_step.h"
 #include "drift_kinetic_step.h"
+#include "model_source.h"
 
 namespace xpic {
 
@@ -36,25 +37,7 @@ constexpr int kBlock = kLaneBlock; // batch.h: lane_grid launches workgroups of 
 constexpr int kLaunchSteps = XPIC_MODEL_LAUNCH_STEPS;
 static_assert(kLaunchSteps <= kOpenRows, "open_tally holds one row per step of a launch");
 
-// the analytic field source of the step functions (full_orbit_step.h: FOGrid, drift_kinetic_step.h: DKGrid)
-struct ModelSource {
-  const xpic_field_model& m;
-  __device__ inline void dk(const double* rn, const double*, double* Ep, double* Bp, double* gBp) const
-  {
-    model_fields(m, rn, Ep, Bp, gBp);
-  }
-  __device__ inline void at(const double* r, double* Ep, double* Bp) const
-  {
-    double gBp[3];
-    model_fields(m, r, Ep, Bp, gBp);
-  }
-  __device__ inline void segment(const double* rn, const double* r0, double* Ep, double* Bp) const
-  {
-    const double rm[3] = {(r0[0] + rn[0]) / 2, (r0[1] + rn[1]) / 2, (r0[2] + rn[2]) / 2};
-    double gBp[3];
-    model_fields(m, rm, Ep, Bp, gBp);
-  }
-};
+// (ModelSource, the analytic field source of the step functions, is model_source.h's)
 
 __device__ inline void fo_load(const double* __restrict__ s, long n, long q, FOPoint& p)
 {
