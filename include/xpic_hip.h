@@ -579,6 +579,53 @@ int xpic_model_drift_kinetic_trace(xpic_ctx* ctx, int64_t n, const xpic_dk_param
   int64_t steps, int64_t sample_every, double* state_6, double* samples, int64_t* iterations_total, int* iterations_max,
   const xpic_trace_region* region, int64_t* exit_step, int64_t* alive, int64_t* removed);
 
+/* ---- time-dependent analytic fields: the model traces with a time envelope on the model's E, the callback of
+ * tests/crank_nicolson_push/crank_nicolson_push_ex3.cpp:39-58 that captures the loop index, `E_p = E0 * (t * dt)`,
+ * `B_p = B0`.  A closed set of kinds again:
+ *   XPIC_ENV_CONSTANT   no factor is applied at all: the call is the model trace, bit for bit (a NULL envelope too)
+ *   XPIC_ENV_RAMP       f = a + b * t        ex3 is a = 0, b = 1; then f is exactly t, contracted or not
+ *   XPIC_ENV_HARMONIC   f = cos(omega * t + phase)     AN EXTENSION: the reference has no such callback
+ * Time: t = (double)(region->step0 + k) * dt, one product, k = the steps this call has completed before the step in
+ * question -- the reference's `t * dt` with its integer loop index; dt is params->dt.  One factor per step: every field
+ * evaluation inside the step (all kicks of a Chin scheme, every Picard / Crank-Nicolson iteration, the drift-kinetic
+ * callback) sees the same f, as a callback that captures t does.  E of the step is E_model(r) * f, component by component
+ * (Vector3R * scalar); B and grad |B| are untouched.  a + b * t and omega * t + phase are formed without contraction, one
+ * rounding per operation.  The parameters the kind reads (a, b for the ramp, omega, phase for the harmonic) must be finite;
+ * the others are ignored. */
+enum xpic_envelope_kind { XPIC_ENV_CONSTANT = 0, XPIC_ENV_RAMP = 1, XPIC_ENV_HARMONIC = 2, XPIC_ENV_NKINDS = 3 };
+typedef struct xpic_field_envelope {
+  int32_t kind; /* enum xpic_envelope_kind */
+  int32_t reserved;
+  double a;
+  double b;
+  double omega;
+  double phase;
+} xpic_field_envelope;
+/* xpic_model_full_orbit_trace and xpic_model_drift_kinetic_trace with an envelope: everything else is theirs -- region
+ * semantics with XPIC_GEOM_NONE, samples, counters, checks, launches of at most XPIC_MODEL_LAUNCH_STEPS steps, any context,
+ * z-slabs included.  step0, which the model traces read even under XPIC_GEOM_NONE, also fixes the clock here: a call of
+ * s1 + s2 steps equals a call of s1 steps followed by one of s2 steps with step0 advanced by s1 (and the first call's
+ * exit_step and sums_4), bit for bit, for every envelope.
+ * sums_4 [n][4] (or NULL; the full-orbit trace only; read and written, so calls compose through it): the running sums of
+ * ex3's two checks (ex3.cpp:51-57), kept on the device so that a long run needs no samples.  After each completed step
+ * p0 -> pn of a live particle, with vh = 0.5 (pn.p + p0.p) and (E_s, B_s) = the model at (r0 + rn) / 2 with the step's factor:
+ *   sums_4[q][0]    += 0.5 (|pn.p|^2 - |p0.p|^2) - qm dt (vh . E_s)    (qm = -1, uniform E0: ex3's term before its / geom_nt)
+ *   sums_4[q][1..3] += vh.transverse_to(B_s)                            (Vector3::transverse_to, src/utils/vector3.h:195-205)
+ * The sums are not divided: the caller divides by its step count.  A removed particle adds nothing after its exit.  With
+ * sums_4 the step costs one more model evaluation; without it, nothing. */
+int xpic_model_full_orbit_trace_timed(xpic_ctx* ctx, int64_t n, const xpic_fo_params* params, const xpic_field_model* model,
+  const xpic_field_envelope* envelope, int64_t steps, int64_t sample_every, double* p_6, double* samples,
+  int64_t* iterations_sum, int* iterations_max, const xpic_trace_region* region, int64_t* exit_step, int64_t* alive,
+  int64_t* removed, double* sums_4);
+int xpic_model_drift_kinetic_trace_timed(xpic_ctx* ctx, int64_t n, const xpic_dk_params* params,
+  const xpic_field_model* model, const xpic_field_envelope* envelope, int64_t steps, int64_t sample_every, double* state_6,
+  double* samples, int64_t* iterations_total, int* iterations_max, const xpic_trace_region* region, int64_t* exit_step,
+  int64_t* alive, int64_t* removed);
+/* out[i] = the factor of step step0 + i for i < nsteps (0 <= nsteps <= 2^31, step0 >= 0; a host array), evaluated on the
+ * device by the device function the two traces call: what a test holds against a host cos. */
+int xpic_envelope_factors(xpic_ctx* ctx, const xpic_field_envelope* envelope, double dt, int64_t step0, int64_t nsteps,
+  double* out);
+
 /* ---- triplet trace: the whole time loop of the reference's grid tests
  * (tests/drift_kinetic_push/drift_kinetic_grid_boris_ex1..4.cpp, ex1.cpp:79-98) for n triplets, with all seven maxima of
  * ComparisonStats (tests/drift_kinetic_push/drift_kinetic_push.h:253-329) reduced on the device.  Triplet q is three

@@ -1,0 +1,91 @@
+"""CPU checks of tests/timed_trace_ref.py, the model the GPU kernels of xpic_amd/csrc/timed_trace.hip are tested against:
+the reference's recorded tables of crank_nicolson_push_ex3 (tests/golden/crank_nicolson_push_ex3) and its two PetscChecks
+from the restated sums, the identities of the constant envelope, and composition through step0."""
+import os
+
+import numpy as np
+import pytest
+
+import analytic_trace_ref as A
+import full_orbit_ref as FO
+import timed_trace_ref as T
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GOLD = os.path.join(ROOT, "tests", "golden", "crank_nicolson_push_ex3")
+TABLE_FLOOR = 1e-11  # the floor of the ex1 / ex2 table tests (tests/test_analytic_trace_ref.py)
+
+
+@pytest.mark.parametrize("omega_dt,steps,rows", [(1000.0, 188, 189), (100.0, 1885, 126), (10.0, 18850, 124)])
+def test_crank_nicolson_ex3_tables_and_checks(omega_dt, steps, rows):
+    """crank_nicolson_push_ex3.cpp: the whole table, and the energy balance and the mean drift velocity at the reference's
+    own bounds, from one run of geom_nt + 1 steps with the sums"""
+    dt, nt, every = T.ex3_run(omega_dt)
+    assert nt == steps
+    gold = np.loadtxt(os.path.join(GOLD, "omega_dt_%.1f.txt" % omega_dt), skiprows=1)
+    assert gold.shape == (rows, 7)
+    out = T.trace("CN", A.model("uniform", **T.EX3_MODEL), T.EX3_ENVELOPE, [T.EX3_START], nt + 1, T.EX3_QM, 1.0, dt, None,
+                  (1.0, 1.0, 1.0), sample_every=every, sums=True)
+    assert out.iterations_max.max() < FO.CN_MAXIT
+    mine = T.ex3_rows(T.EX3_START, out.samples, dt, every, rows)
+    assert mine.shape == gold.shape
+    err = np.abs(mine - gold)
+    bound = FO.table_bound(gold, TABLE_FLOOR)
+    energy, drift = T.ex3_checks(out.sums[0], dt, nt)
+    print("omega_dt", omega_dt, "steps", nt, "largest error / bound", (err / bound).max(), "energy", energy, "drift", drift)
+    assert (err <= bound).all()
+    assert energy <= T.EX3_ENERGY_BOUND
+    assert drift < T.EX3_DRIFT_BOUND
+
+
+def same(a, b, fields=("state", "samples", "exit_step", "alive", "removed", "iterations_sum", "iterations_max")):
+    for f in fields:
+        x, y = np.asarray(getattr(a, f)), np.asarray(getattr(b, f))
+        assert x.shape == y.shape and x.tobytes() == y.astype(x.dtype).tobytes(), f
+
+
+def run(kind, name, env, p, steps, **kw):
+    return T.trace(kind, A.model(name, **T.MODELS[name]), env, p, steps, T.QM, T.MP, T.DT, T.region(name), T.D,
+                   **T.PIN.get(kind, {}), **kw)
+
+
+@pytest.mark.parametrize("kind", ["EB2B", "CN", "dk"])
+def test_constant_envelope_is_the_analytic_trace(kind):
+    """bit for bit: no envelope, the constant one, the ramp a = 1, b = 0 and the harmonic omega = 0, phase = 0"""
+    name = "quadratic_mirror"
+    p = T.particles(name, kind, 40)
+    push = A.pusher(kind, A.model(name, **T.MODELS[name]), T.QM, T.MP, T.DT, **T.PIN.get(kind, {}))
+    ref = A.trace(push, p, 80, T.region(name), T.D, sample_every=T.EVERY)
+    assert (ref.exit_step >= 0).any() and (ref.exit_step < 0).any()
+    for env in (None, {"kind": "constant"}, {"kind": "ramp", "a": 1.0, "b": 0.0},
+                {"kind": "harmonic", "omega": 0.0, "phase": 0.0}):
+        same(run(kind, name, env, p, 80, sample_every=T.EVERY), ref)
+
+
+@pytest.mark.parametrize("ename", list(T.ENVELOPES))
+@pytest.mark.parametrize("kind", ["EB2B", "CN", "dk"])
+def test_composition_through_step0(kind, ename):
+    name, env = "quadratic_mirror", T.ENVELOPES[ename]
+    p = T.particles(name, kind, 40)
+    sums = None if kind == "dk" else True
+    full = run(kind, name, env, p, 80, sample_every=T.EVERY, sums=sums)
+    a = run(kind, name, env, p, 35, sample_every=T.EVERY, sums=sums)
+    b = run(kind, name, env, a.state, 45, sample_every=T.EVERY, exit_step=a.exit_step, step0=35, sums=a.sums)
+    assert full.state.tobytes() == b.state.tobytes() and np.array_equal(full.exit_step, b.exit_step)
+    assert np.array_equal(full.samples, np.concatenate([a.samples, b.samples]))
+    assert np.array_equal(full.alive, np.concatenate([a.alive, b.alive]))
+    assert full.removed == a.removed + b.removed
+    assert np.array_equal(full.iterations_sum, a.iterations_sum + b.iterations_sum)
+    if sums:
+        assert full.sums.tobytes() == b.sums.tobytes()
+    # the clock matters: the same second call with step0 left at 0 is another trace
+    c = run(kind, name, env, a.state, 45, exit_step=a.exit_step, step0=0)
+    assert c.state.tobytes() != b.state.tobytes()
+
+
+def test_factor():
+    """the ramp a = 0, b = 1 is exactly float(step) * dt; the sums of a step at rest in no field are 0"""
+    steps = np.array([0, 1, 7, 188496, 1999999])
+    for dt in (0.05, 1e-3, 10.0):
+        assert np.array_equal(T.factor(T.EX3_ENVELOPE, steps, dt), steps.astype(np.float64) * dt)
+    assert T.factor(None, 5, 0.1) == 1.0 and T.factor({"kind": "constant"}, 5, 0.1) == 1.0
+    assert T.factor({"kind": "harmonic", "omega": 2.0, "phase": 0.5}, 3, 0.25) == np.cos(2.0 * 0.75 + 0.5)

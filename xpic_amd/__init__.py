@@ -34,7 +34,8 @@ SYMBOLS = [
     "xpic_implicit_esirkepov_decompose", "xpic_drift_kinetic_interpolate", "xpic_drift_kinetic_push",
     "xpic_drift_kinetic_trace", "xpic_full_orbit_push", "xpic_full_orbit_trace", "xpic_full_orbit_trace_open",
     "xpic_drift_kinetic_trace_open", "xpic_paired_trace", "xpic_model_fields", "xpic_set_model_field",
-    "xpic_model_full_orbit_trace", "xpic_model_drift_kinetic_trace", "xpic_triplet_trace", "xpic_charge_collect", "xpic_charge_columns", "xpic_comm_rccl_unique_id", "xpic_comm_init_rccl", "xpic_comm_init_callbacks", "xpic_comm_size", "xpic_comm_peer_export", "xpic_comm_peer_import",
+    "xpic_model_full_orbit_trace", "xpic_model_drift_kinetic_trace", "xpic_model_full_orbit_trace_timed",
+    "xpic_model_drift_kinetic_trace_timed", "xpic_envelope_factors", "xpic_triplet_trace", "xpic_charge_collect", "xpic_charge_columns", "xpic_comm_rccl_unique_id", "xpic_comm_init_rccl", "xpic_comm_init_callbacks", "xpic_comm_size", "xpic_comm_peer_export", "xpic_comm_peer_import",
     "xpic_profile_enable", "xpic_profile_reset", "xpic_profile_get", "xpic_probe_copy_bandwidth",
 ]
 
@@ -158,6 +159,28 @@ TRIPLET_DK_MAXIT = 1024    # include/xpic_hip.h: XPIC_TRIPLET_DK_MAXIT
 TRIPLET_STATS = ("B", "gradB", "pos", "z", "p_parallel", "mu", "energy")
 
 
+class FieldEnvelope(C.Structure):  # include/xpic_hip.h: xpic_field_envelope
+    _fields_ = [("kind", C.c_int32), ("reserved", C.c_int32), ("a", C.c_double), ("b", C.c_double), ("omega", C.c_double),
+                ("phase", C.c_double)]
+
+
+# include/xpic_hip.h: enum xpic_envelope_kind; "harmonic" is an extension, the reference has no such callback
+ENVELOPE_KINDS = {"constant": 0, "ramp": 1, "harmonic": 2}
+
+
+def field_envelope(kind, **params):
+    """A time envelope of a model's E (include/xpic_hip.h: xpic_field_envelope).  kind: a key of ENVELOPE_KINDS or its
+    number; params: the members the kind reads -- ramp: a, b (f = a + b t); harmonic: omega, phase
+    (f = cos(omega t + phase)); constant: none.  A member that is not given is 0."""
+    e = FieldEnvelope()
+    e.kind = int(ENVELOPE_KINDS.get(kind, kind))
+    for k, v in params.items():
+        if k not in ("a", "b", "omega", "phase"):
+            raise XpicError("field_envelope: no parameter %r" % (k,))
+        setattr(e, k, float(v))
+    return e
+
+
 def field_model(kind, **params):
     """An analytic field model (include/xpic_hip.h: xpic_field_model).  kind: a key of MODEL_KINDS or its number; params:
     the members the kind reads -- uniform: E0, B0; linear: E0, B0, r0, g; quadratic_mirror: B_min, B_max, W, D (and E_phi,
@@ -200,6 +223,14 @@ class OpenTrace(collections.namedtuple("OpenTrace", "state samples exit_step ali
     [steps // sample_every][n][6] and alive [steps // sample_every] (None without sample_every); exit_step [n] (-1: alive,
     k: removed after completing k steps in total); removed, the particles this call removed; the iteration counters of the
     closed traces."""
+    __slots__ = ()
+
+
+class TimedTrace(collections.namedtuple(
+        "TimedTrace", "state samples exit_step alive removed iterations_sum iterations_max sums")):
+    """What Context.model_full_orbit_trace_timed returns: OpenTrace's fields and sums [n][4] (None when not asked for), the
+    running sums of crank_nicolson_push_ex3's two checks: the energy balance and the three components of the mean
+    transverse velocity, neither divided by the step count."""
     __slots__ = ()
 
 
@@ -848,6 +879,52 @@ class Context:
             mx.ctypes.data_as(C.POINTER(C.c_int)), C.byref(reg), None if bare else ex.ctypes.data_as(i64),
             alive.ctypes.data_as(i64) if sample_every else None, None if bare else C.byref(removed)))
         return OpenTrace(state, samples, ex, alive, removed.value, tot, mx)
+
+    # ---- time-dependent analytic fields (include/xpic_hip.h: xpic_field_envelope): the two model traces with a time
+    # envelope on the model's E.  envelope: what field_envelope(...) returns, or None (constant: the model trace itself);
+    # step0 also fixes the clock, t = (step0 + k) dt
+    def model_full_orbit_trace_timed(self, state, steps, scheme, qm, dt, model, envelope, region=None, sample_every=0,
+                                     exit_step=None, step0=0, keep_samples=True, atol=1e-7, rtol=1e-7, maxit=30, sums=None):
+        """model_full_orbit_trace with an envelope -> TimedTrace.  sums: True for sums that start at 0, or the [n][4] array a
+        previous call returned, so that calls compose; None: no sums"""
+        state, samples, alive, ex, reg, tot, mx = self._model_args(state, steps, sample_every, region, exit_step, step0,
+                                                                       keep_samples)
+        n = state.shape[0]
+        if sums is not None:
+            sums = np.zeros((n, 4)) if sums is True else np.array(sums, dtype=np.float64).reshape(n, 4)
+        P = self._fo_params(scheme, qm, dt, atol, rtol, maxit)
+        removed, i64 = C.c_int64(), C.POINTER(C.c_int64)
+        bare = region is None and exit_step is None  # the closed trace: the library gets no exit_step and no removed
+        self._ck(self.L.xpic_model_full_orbit_trace_timed(
+            self.h, C.c_int64(n), C.byref(P), None if model is None else C.byref(model),
+            None if envelope is None else C.byref(envelope), C.c_int64(int(steps)), C.c_int64(int(sample_every)), _dp(state),
+            None if samples is None else _dp(samples), tot.ctypes.data_as(i64), mx.ctypes.data_as(C.POINTER(C.c_int)),
+            C.byref(reg), None if bare else ex.ctypes.data_as(i64), alive.ctypes.data_as(i64) if sample_every else None,
+            None if bare else C.byref(removed), None if sums is None else _dp(sums)))
+        return TimedTrace(state, samples, ex, alive, removed.value, tot, mx, sums)
+
+    def model_drift_kinetic_trace_timed(self, state, steps, qm, mp, dt, model, envelope, region=None, sample_every=0,
+                                        exit_step=None, step0=0, keep_samples=True, eps=1e-12, delta=1e-12, maxit=30):
+        """model_drift_kinetic_trace with an envelope -> OpenTrace"""
+        state, samples, alive, ex, reg, tot, mx = self._model_args(state, steps, sample_every, region, exit_step, step0,
+                                                                       keep_samples)
+        P = self._dk_params(qm, mp, dt, eps, delta, maxit)
+        removed, i64 = C.c_int64(), C.POINTER(C.c_int64)
+        bare = region is None and exit_step is None
+        self._ck(self.L.xpic_model_drift_kinetic_trace_timed(
+            self.h, C.c_int64(state.shape[0]), C.byref(P), None if model is None else C.byref(model),
+            None if envelope is None else C.byref(envelope), C.c_int64(int(steps)), C.c_int64(int(sample_every)), _dp(state),
+            None if samples is None else _dp(samples), tot.ctypes.data_as(i64), mx.ctypes.data_as(C.POINTER(C.c_int)),
+            C.byref(reg), None if bare else ex.ctypes.data_as(i64), alive.ctypes.data_as(i64) if sample_every else None,
+            None if bare else C.byref(removed)))
+        return OpenTrace(state, samples, ex, alive, removed.value, tot, mx)
+
+    def envelope_factors(self, envelope, dt, step0, nsteps):
+        """-> the factors of steps step0 .. step0 + nsteps - 1, evaluated on the device as the traces evaluate them"""
+        out = np.zeros(max(int(nsteps), 0))
+        self._ck(self.L.xpic_envelope_factors(self.h, None if envelope is None else C.byref(envelope), C.c_double(float(dt)),
+                                              C.c_int64(int(step0)), C.c_int64(int(nsteps)), _dp(out)))
+        return out
 
     # ---- triplet trace (include/xpic_hip.h: xpic_triplet_trace): model_drift_kinetic_trace of state_model,
     # drift_kinetic_trace of state_grid and model_full_orbit_trace of p in lock-step, with all seven maxima of the

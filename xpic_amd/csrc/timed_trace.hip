@@ -1,0 +1,322 @@
+// timed_trace.hip -- the model traces (model_trace.hip) with a time envelope on the model's E (DESIGN.md
+// 5n): the reference's one pusher example whose callback captures the step index,
+//   tests/crank_nicolson_push/crank_nicolson_push_ex3.cpp:39-58     E_p = E0 * (t * dt); B_p = B0;
+// and the running sums of its two checks (:51-57) kept on the device.  The kernels are k_model_fo_trace<CN> and
+// k_model_dk_trace with the field source formed at the top of every step: TimedModelSource (timed_source.h) carries the
+// factor of step R.step0 + first + done, so every field evaluation inside a step sees the same one.  The step arithmetic
+// is full_orbit_step.h's and drift_kinetic_step.h's own text.  One lane per particle, fp64, no cross-lane operation but
+// open_tally's.  Every loop is bounded by a constant or by an argument the entry points have range-checked: fo maxit <=
+// XPIC_FO_MAXIT, 1 <= dk maxit <= XPIC_MODEL_DK_MAXIT, at most XPIC_MODEL_LAUNCH_STEPS steps per launch.  Every global
+// index is formed under q < n, row < nsamp or i < nsteps.  The staging is batch.h's batch_trace_open with the "never"
+// policy; sums_4 travels as [4][n] in a DevScratch of this file.
+#include <algorithm>
+#include <cmath>
+#include <vector>
+
+#include "batch.h"
+#include "common.h"
+#include "device_common.h"
+#include "field_model.h"
+#include "ie_shape.h"
+#include "trace_open.h"
+
+// as in model_trace.hip: contracted per source expression only
+#pragma clang fp contract(on)
+
+#include "full_orbit_step.h"
+#include "drift_kinetic_step.h"
+#include "timed_source.h"
+
+namespace xpic {
+
+namespace {
+
+constexpr int kBlock = kLaneBlock; // batch.h: lane_grid launches workgroups of this size
+constexpr int kLaunchSteps = XPIC_MODEL_LAUNCH_STEPS;
+static_assert(kLaunchSteps <= kOpenRows, "open_tally holds one row per step of a launch");
+
+__device__ inline void fo_load(const double* __restrict__ s, long n, long q, FOPoint& p)
+{
+  p.r[0] = s[q]; p.r[1] = s[n + q]; p.r[2] = s[2 * n + q];
+  p.p[0] = s[3 * n + q]; p.p[1] = s[4 * n + q]; p.p[2] = s[5 * n + q];
+}
+__device__ inline void fo_store(double* __restrict__ s, long n, long q, const FOPoint& p)
+{
+  s[q] = p.r[0]; s[n + q] = p.r[1]; s[2 * n + q] = p.r[2];
+  s[3 * n + q] = p.p[0]; s[4 * n + q] = p.p[1]; s[5 * n + q] = p.p[2];
+}
+
+// the terms of ex3's two checks for the step p0 -> pn (ex3.cpp:51-57), added to the lane's sums: the energy balance
+// with the work of the step's E at the midpoint, and vh.transverse_to(B_s) (Vector3::parallel_to / transverse_to,
+// src/utils/vector3.h:195-205, statement by statement)
+__device__ inline void ex3_sums(const TimedModelSource& src, double qm, double dt, const FOPoint& pn, const FOPoint& p0,
+  double* sum)
+{
+  double vh[3], Es[3], Bs[3];
+#pragma unroll
+  for (int c = 0; c < 3; ++c) vh[c] = 0.5 * (pn.p[c] + p0.p[c]);
+  src.segment(pn.r, p0.r, Es, Bs);
+  sum[0] += 0.5 * (fo_dot3(pn.p, pn.p) - fo_dot3(p0.p, p0.p)) - qm * dt * fo_dot3(vh, Es);
+  const double vb = fo_dot3(vh, Bs), bb = fo_dot3(Bs, Bs);
+#pragma unroll
+  for (int c = 0; c < 3; ++c) sum[1 + c] += vh[c] - (vb * Bs[c]) / bb;
+}
+
+// k_model_fo_trace<CN> (model_trace.hip) with the step's factor; SUMS: sums [4][n], read and written
+template <bool CN, bool SUMS>
+__global__ void __launch_bounds__(kBlock) k_timed_fo_trace(GridDev g, xpic_field_model M, xpic_field_envelope V,
+  xpic_fo_params P, OpenRegion R, long n, double* __restrict__ s, long first, int nsteps, long sample_every, long nsamp,
+  double* __restrict__ samples, long long* __restrict__ it_sum, int* __restrict__ it_max, long long* __restrict__ exit_step,
+  unsigned long long* alive, unsigned long long* removed, double* __restrict__ sums)
+{
+  const long q = (long)blockIdx.x * kBlock + threadIdx.x;
+  const bool live = q < n && exit_step[q] < 0;
+  const int ns = nsteps < kLaunchSteps ? nsteps : kLaunchSteps;
+  const bool on = V.kind != XPIC_ENV_CONSTANT;
+  int done = 0;
+  bool gone = false;
+  if (live) {
+    FOPoint pn;
+    fo_load(s, n, q, pn);
+    long long total = CN ? it_sum[q] : 0;
+    int most = CN ? it_max[q] : 0;
+    double sum[4] = {0.0, 0.0, 0.0, 0.0};
+    if (SUMS) {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) sum[k] = sums[k * n + q];
+    }
+    for (; done < ns; ++done) {
+      if (R.kind >= 0 && !open_keep(g, R, pn.r)) { gone = true; break; }
+      const TimedModelSource src{M, on, envelope_factor(V, R.step0 + first + done, P.dt)};
+      const FOPoint p0 = pn;
+      int it = 0;
+      if (CN) it = fo_cn_process(src, P.qm, P.dt, P.atol, P.rtol, P.maxit, pn, p0);
+      else fo_step(P.scheme, src, P.qm, P.dt, pn);
+      if (SUMS) ex3_sums(src, P.qm, P.dt, pn, p0, sum);
+      total += it;
+      most = it > most ? it : most;
+      const long step = first + done + 1;
+      if (samples && step % sample_every == 0) {
+        const long row = step / sample_every - 1;
+        if (row < nsamp) fo_store(samples + row * 6 * n, n, q, pn);
+      }
+    }
+    fo_store(s, n, q, pn);
+    if (CN) { it_sum[q] = total; it_max[q] = most; }
+    if (SUMS) {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) sums[k * n + q] = sum[k];
+    }
+    if (gone) exit_step[q] = R.step0 + first + done;
+  }
+  open_tally<kBlock>(live, gone, first + done, first, ns, sample_every, nsamp, alive, removed);
+}
+
+// k_model_dk_trace (model_trace.hip) with the step's factor
+__global__ void __launch_bounds__(kBlock) k_timed_dk_trace(GridDev g, xpic_field_model M, xpic_field_envelope V,
+  xpic_dk_params P, OpenRegion R, long n, double* __restrict__ s, long first, int nsteps, long sample_every, long nsamp,
+  double* __restrict__ samples, long long* __restrict__ it_total, int* __restrict__ it_max,
+  long long* __restrict__ exit_step, unsigned long long* alive, unsigned long long* removed)
+{
+  const long q = (long)blockIdx.x * kBlock + threadIdx.x;
+  const bool live = q < n && exit_step[q] < 0;
+  const int ns = nsteps < kLaunchSteps ? nsteps : kLaunchSteps;
+  const bool on = V.kind != XPIC_ENV_CONSTANT;
+  int done = 0;
+  bool gone = false;
+  if (live) {
+    DKPoint p0, pn;
+    dk_load(s, n, q, pn);
+    long long total = it_total[q];
+    int most = it_max[q];
+    for (; done < ns; ++done) {
+      if (R.kind >= 0 && !open_keep(g, R, pn.r)) { gone = true; break; }
+      const TimedModelSource src{M, on, envelope_factor(V, R.step0 + first + done, P.dt)};
+      p0 = pn;
+      const int it = dk_process(src, P, p0, pn);
+      total += it;
+      most = it > most ? it : most;
+      const long step = first + done + 1;
+      if (samples && step % sample_every == 0) {
+        const long row = step / sample_every - 1;
+        if (row < nsamp) dk_store(samples + row * 6 * n, n, q, pn);
+      }
+    }
+    dk_store(s, n, q, pn);
+    it_total[q] = total;
+    it_max[q] = most;
+    if (gone) exit_step[q] = R.step0 + first + done;
+  }
+  open_tally<kBlock>(live, gone, first + done, first, ns, sample_every, nsamp, alive, removed);
+}
+
+// the factors of steps step0 .. step0 + nsteps - 1 by the device function the traces call
+__global__ void __launch_bounds__(kBlock) k_envelope_factors(xpic_field_envelope V, double dt, long long step0, long nsteps,
+  double* __restrict__ out)
+{
+  const long i = (long)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= nsteps) return;
+  out[i] = envelope_factor(V, step0 + i, dt);
+}
+
+// the envelope a call runs with: a null one is the constant one
+int timed_envelope(const std::string& who, const xpic_field_envelope* in, xpic_field_envelope* V)
+{
+  const char* bad = envelope_check(in);
+  XPIC_CHECK(!bad, who + ": " + (bad ? bad : ""));
+  *V = xpic_field_envelope{};
+  if (in) *V = *in;
+  return 0;
+}
+
+// model_trace.hip's model_region: open_region (trace_open.h) with XPIC_GEOM_NONE allowed and `compact` not read
+int timed_region(const std::string& who, const xpic_trace_region* in, OpenRegion* R)
+{
+  XPIC_CHECK(in, who + ": region is null");
+  XPIC_CHECK(in->geometry == XPIC_GEOM_NONE || in->geometry == XPIC_GEOM_BOX || in->geometry == XPIC_GEOM_CYLINDER,
+    who + ": unknown geometry kind");
+  XPIC_CHECK(in->step0 >= 0, who + ": step0 is negative");
+  R->kind = in->geometry;
+  for (int i = 0; i < 7; ++i) R->a[i] = in->geom[i];
+  R->step0 = in->step0;
+  return 0;
+}
+
+// The checks and the driver the two traces share, after their own checks of params: model_trace.hip's, with sums_4
+// (null: none) staged as [4][n] around the launches.  launch(..., sums): the device's [4][n], null without sums_4.
+template <class Launch>
+int timed_trace(xpic_ctx* ctx, const std::string& who, const char* label, int64_t n, bool counters, int64_t steps,
+  int64_t sample_every, double* state_6, double* samples, int64_t* it_sum, int* it_max, const OpenRegion& R,
+  int64_t* exit_step, int64_t* alive, int64_t* removed, double* sums_4, Launch launch)
+{
+  const bool open = R.kind >= 0;
+  XPIC_CHECK(n <= ((int64_t)1 << 36), who + ": n is larger than 2^36");
+  XPIC_CHECK(steps >= 0, who + ": steps is negative");
+  XPIC_CHECK((!samples && !alive) || sample_every >= 1, who + ": sample_every must be >= 1 when samples or alive are asked for");
+  XPIC_CHECK(state_6, who + ": the particle array is null");
+  XPIC_CHECK(exit_step || !open, who + ": exit_step is null");
+  XPIC_CHECK(removed || !open, who + ": removed is null");
+  XPIC_CHECK((it_sum && it_max) || !counters, who + ": an iteration counter is null");
+  int64_t nsamp;
+  XPIC_CHECK(trace_sample_bytes(samples ? n : 0, steps, sample_every, samples || alive, &nsamp) >= 0,
+    who + ": the sample buffer (48 n steps / sample_every bytes) is too large");
+  if (removed) *removed = 0;
+  if (n == 0 || steps == 0) return 0;
+  std::vector<int64_t> ex_own;
+  if (!exit_step) {
+    ex_own.assign((size_t)n, -1);
+    exit_step = ex_own.data();
+  }
+  int64_t rm_own = 0;
+  std::vector<double> hsum;
+  DevScratch<double> dsum;
+  if (sums_4) {
+    to_soa(sums_4, n, hsum, 4);
+    XPIC_CALL(dsum.alloc(4 * n));
+    XPIC_CALL(upload(dsum, hsum.data(), 4 * n, ctx->stream));
+  }
+  XPIC_CALL(batch_trace_open(ctx, label, label, kLaunchSteps, n, steps, sample_every, nsamp, counters, XPIC_COMPACT_NEVER,
+    R.step0, state_6, samples, it_sum, it_max, exit_step, alive, removed ? removed : &rm_own,
+    [&](double* s, const int64_t*, long, long first, int ns, double* sm, long long* sum, int* mx, long long* ex,
+      unsigned long long* al, unsigned long long* rm) { launch(s, first, ns, (long)nsamp, sm, sum, mx, ex, al, rm, dsum.p); }));
+  if (sums_4) {
+    XPIC_CALL(download(hsum.data(), dsum, 4 * n, ctx->stream));
+    XPIC_HIP(hipStreamSynchronize(ctx->stream));
+    to_aos(hsum.data(), n, sums_4, 4);
+  }
+  if (!counters) {
+    if (it_sum) std::fill(it_sum, it_sum + n, (int64_t)0);
+    if (it_max) std::fill(it_max, it_max + n, 0);
+  }
+  return 0;
+}
+
+}  // namespace
+
+}  // namespace xpic
+
+using namespace xpic;
+
+extern "C" {
+
+int xpic_model_full_orbit_trace_timed(xpic_ctx* ctx, int64_t n, const xpic_fo_params* params, const xpic_field_model* model,
+  const xpic_field_envelope* envelope, int64_t steps, int64_t sample_every, double* p_6, double* samples,
+  int64_t* iterations_sum, int* iterations_max, const xpic_trace_region* region, int64_t* exit_step, int64_t* alive,
+  int64_t* removed, double* sums_4)
+{
+  const std::string who = "model_full_orbit_trace_timed";
+  XPIC_CHECK(ctx != nullptr, "null context");
+  XPIC_CHECK(n >= 0, who + ": n is negative");
+  XPIC_CHECK(params, who + ": params is null");
+  XPIC_CHECK(params->scheme >= 0 && params->scheme < XPIC_FO_NSCHEMES, who + ": unknown scheme id");
+  const bool cn = params->scheme == XPIC_FO_CN;
+  if (cn) XPIC_CHECK(params->maxit >= 1 && params->maxit <= XPIC_FO_MAXIT, who + ": maxit must be within 1 .. 64");
+  const char* bad = model_check(model);
+  XPIC_CHECK(!bad, who + ": " + (bad ? bad : ""));
+  xpic_field_envelope V;
+  XPIC_CALL(timed_envelope(who, envelope, &V));
+  OpenRegion R;
+  XPIC_CALL(timed_region(who, region, &R));
+  const bool sums = sums_4 != nullptr;
+  auto kernel = cn ? (sums ? k_timed_fo_trace<true, true> : k_timed_fo_trace<true, false>)
+                   : (sums ? k_timed_fo_trace<false, true> : k_timed_fo_trace<false, false>);
+  return timed_trace(ctx, who, "timed_fo_trace", n, cn, steps, sample_every, p_6, samples, iterations_sum, iterations_max, R,
+    exit_step, alive, removed, sums_4,
+    [&](double* s, long first, int ns, long nsamp, double* sm, long long* sum, int* mx, long long* ex, unsigned long long* al,
+      unsigned long long* rm, double* sd) {
+      hipLaunchKernelGGL(kernel, lane_grid(n), dim3(kBlock), 0, ctx->stream, ctx->g, *model, V, *params, R, (long)n, s, first,
+        ns, (long)sample_every, nsamp, sm, sum, mx, ex, al, rm, sd);
+    });
+}
+
+int xpic_model_drift_kinetic_trace_timed(xpic_ctx* ctx, int64_t n, const xpic_dk_params* params,
+  const xpic_field_model* model, const xpic_field_envelope* envelope, int64_t steps, int64_t sample_every, double* state_6,
+  double* samples, int64_t* iterations_total, int* iterations_max, const xpic_trace_region* region, int64_t* exit_step,
+  int64_t* alive, int64_t* removed)
+{
+  const std::string who = "model_drift_kinetic_trace_timed";
+  XPIC_CHECK(ctx != nullptr, "null context");
+  XPIC_CHECK(n >= 0, who + ": n is negative");
+  XPIC_CHECK(params, who + ": params is null");
+  XPIC_CHECK(params->maxit >= 1 && params->maxit <= XPIC_MODEL_DK_MAXIT, who + ": maxit must be within 1 .. 1024");
+  XPIC_CHECK(params->mp != 0.0, who + ": mp must not be 0");
+  const char* bad = model_check(model);
+  XPIC_CHECK(!bad, who + ": " + (bad ? bad : ""));
+  xpic_field_envelope V;
+  XPIC_CALL(timed_envelope(who, envelope, &V));
+  OpenRegion R;
+  XPIC_CALL(timed_region(who, region, &R));
+  return timed_trace(ctx, who, "timed_dk_trace", n, true, steps, sample_every, state_6, samples, iterations_total,
+    iterations_max, R, exit_step, alive, removed, nullptr,
+    [&](double* s, long first, int ns, long nsamp, double* sm, long long* sum, int* mx, long long* ex, unsigned long long* al,
+      unsigned long long* rm, double*) {
+      hipLaunchKernelGGL(k_timed_dk_trace, lane_grid(n), dim3(kBlock), 0, ctx->stream, ctx->g, *model, V, *params, R, (long)n,
+        s, first, ns, (long)sample_every, nsamp, sm, sum, mx, ex, al, rm);
+    });
+}
+
+int xpic_envelope_factors(xpic_ctx* ctx, const xpic_field_envelope* envelope, double dt, int64_t step0, int64_t nsteps,
+  double* out)
+{
+  const std::string who = "envelope_factors";
+  XPIC_CHECK(ctx != nullptr, "null context");
+  xpic_field_envelope V;
+  XPIC_CALL(timed_envelope(who, envelope, &V));
+  XPIC_CHECK(step0 >= 0, who + ": step0 is negative");
+  XPIC_CHECK(nsteps >= 0 && nsteps <= ((int64_t)1 << 31), who + ": nsteps must be within 0 .. 2^31");
+  XPIC_CHECK(out || nsteps == 0, who + ": out is null");
+  if (nsteps == 0) return 0;
+  DevScratch<double> o;
+  XPIC_CALL(o.alloc(nsteps));
+  {
+    Timed t(ctx, "envelope_factors");
+    hipLaunchKernelGGL(k_envelope_factors, lane_grid(nsteps), dim3(kBlock), 0, ctx->stream, V, dt, (long long)step0,
+      (long)nsteps, o.p);
+    XPIC_HIP(hipGetLastError());
+  }
+  XPIC_CALL(download(out, o, nsteps, ctx->stream));
+  XPIC_HIP(hipStreamSynchronize(ctx->stream));
+  return 0;
+}
+
+}  // extern "C"
