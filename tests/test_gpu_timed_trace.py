@@ -1,4 +1,4 @@
-"""The model traces with a time envelope on the device (xpic_amd/csrc/timed_trace.hip; include/xpic_hip.h:
+"""The model traces with a time envelope on the device (xpic_amd/csrc/model_trace.hip; include/xpic_hip.h:
 xpic_field_envelope, xpic_model_full_orbit_trace_timed, xpic_model_drift_kinetic_trace_timed, xpic_envelope_factors)
 against the reference's tables of crank_nicolson_push_ex3, against the untimed model traces, and against the numpy
 restatement tests/timed_trace_ref.py (pinned without a GPU by tests/test_timed_trace_ref.py).  Shapes as in

@@ -1,4 +1,4 @@
-"""CPU checks of tests/timed_trace_ref.py, the model the GPU kernels of xpic_amd/csrc/timed_trace.hip are tested against:
+"""CPU checks of tests/timed_trace_ref.py, the model the GPU kernels of xpic_amd/csrc/model_trace.hip are tested against:
 the reference's recorded tables of crank_nicolson_push_ex3 (tests/golden/crank_nicolson_push_ex3) and its two PetscChecks
 from the restated sums, the identities of the constant envelope, and composition through step0."""
 import os

@@ -1,5 +1,5 @@
 """numpy restatement of the model traces with a time envelope on the model's E (include/xpic_hip.h:
-xpic_field_envelope), the model the GPU kernels of xpic_amd/csrc/timed_trace.hip are tested against:
+xpic_field_envelope), the model the GPU kernels of xpic_amd/csrc/model_trace.hip are tested against:
 
   factor(env, step, dt)     the envelope at t = float(step) * dt, one product: the reference's `t * dt` with its integer
                             loop index (tests/crank_nicolson_push/crank_nicolson_push_ex3.cpp:39-46)

@@ -850,35 +850,45 @@ class Context:
                                                                           "never", keep_samples)
         return state, samples, alive, ex, reg, tot, mx
 
+    _ABSENT = object()  # _model_trace: the library function has no such argument
+
+    def _model_trace(self, fn, P, state, steps, model, region, sample_every, exit_step, step0, keep_samples,
+                     envelope=_ABSENT, sums=_ABSENT):
+        """the ctypes call of the four model traces -> the fields of TimedTrace (OpenTrace's and sums).  envelope follows
+        model and sums ends the argument list where fn has them; sums as model_full_orbit_trace_timed takes it"""
+        state, samples, alive, ex, reg, tot, mx = self._model_args(state, steps, sample_every, region, exit_step, step0,
+                                                                       keep_samples)
+        n = state.shape[0]
+        absent = self._ABSENT
+        if sums is not absent and sums is not None:
+            sums = np.zeros((n, 4)) if sums is True else np.array(sums, dtype=np.float64).reshape(n, 4)
+        removed, i64 = C.c_int64(), C.POINTER(C.c_int64)
+        bare = region is None and exit_step is None  # the closed trace: the library gets no exit_step and no removed
+        args = [self.h, C.c_int64(n), C.byref(P), None if model is None else C.byref(model)]
+        if envelope is not absent:
+            args.append(None if envelope is None else C.byref(envelope))
+        args += [C.c_int64(int(steps)), C.c_int64(int(sample_every)), _dp(state), None if samples is None else _dp(samples),
+                 tot.ctypes.data_as(i64), mx.ctypes.data_as(C.POINTER(C.c_int)), C.byref(reg),
+                 None if bare else ex.ctypes.data_as(i64), alive.ctypes.data_as(i64) if sample_every else None,
+                 None if bare else C.byref(removed)]
+        if sums is not absent:
+            args.append(None if sums is None else _dp(sums))
+        self._ck(fn(*args))
+        return state, samples, ex, alive, removed.value, tot, mx, None if sums is absent else sums
+
     def model_full_orbit_trace(self, state, steps, scheme, qm, dt, model, region=None, sample_every=0, exit_step=None,
                                step0=0, keep_samples=True, atol=1e-7, rtol=1e-7, maxit=30):
         """full_orbit_trace_open on an analytic model -> OpenTrace; steps = 1 is the one-step push"""
-        state, samples, alive, ex, reg, tot, mx = self._model_args(state, steps, sample_every, region, exit_step, step0,
-                                                                       keep_samples)
-        P = self._fo_params(scheme, qm, dt, atol, rtol, maxit)
-        removed, i64 = C.c_int64(), C.POINTER(C.c_int64)
-        bare = region is None and exit_step is None  # the closed trace: the library gets no exit_step and no removed
-        self._ck(self.L.xpic_model_full_orbit_trace(
-            self.h, C.c_int64(state.shape[0]), C.byref(P), None if model is None else C.byref(model), C.c_int64(int(steps)),
-            C.c_int64(int(sample_every)), _dp(state), None if samples is None else _dp(samples), tot.ctypes.data_as(i64),
-            mx.ctypes.data_as(C.POINTER(C.c_int)), C.byref(reg), None if bare else ex.ctypes.data_as(i64),
-            alive.ctypes.data_as(i64) if sample_every else None, None if bare else C.byref(removed)))
-        return OpenTrace(state, samples, ex, alive, removed.value, tot, mx)
+        return OpenTrace(*self._model_trace(
+            self.L.xpic_model_full_orbit_trace, self._fo_params(scheme, qm, dt, atol, rtol, maxit), state, steps, model, region,
+            sample_every, exit_step, step0, keep_samples)[:7])
 
     def model_drift_kinetic_trace(self, state, steps, qm, mp, dt, model, region=None, sample_every=0, exit_step=None,
                                   step0=0, keep_samples=True, eps=1e-12, delta=1e-12, maxit=30):
         """drift_kinetic_trace_open on an analytic model -> OpenTrace; steps = 1 is the one-step push"""
-        state, samples, alive, ex, reg, tot, mx = self._model_args(state, steps, sample_every, region, exit_step, step0,
-                                                                       keep_samples)
-        P = self._dk_params(qm, mp, dt, eps, delta, maxit)
-        removed, i64 = C.c_int64(), C.POINTER(C.c_int64)
-        bare = region is None and exit_step is None  # the closed trace: the library gets no exit_step and no removed
-        self._ck(self.L.xpic_model_drift_kinetic_trace(
-            self.h, C.c_int64(state.shape[0]), C.byref(P), None if model is None else C.byref(model), C.c_int64(int(steps)),
-            C.c_int64(int(sample_every)), _dp(state), None if samples is None else _dp(samples), tot.ctypes.data_as(i64),
-            mx.ctypes.data_as(C.POINTER(C.c_int)), C.byref(reg), None if bare else ex.ctypes.data_as(i64),
-            alive.ctypes.data_as(i64) if sample_every else None, None if bare else C.byref(removed)))
-        return OpenTrace(state, samples, ex, alive, removed.value, tot, mx)
+        return OpenTrace(*self._model_trace(
+            self.L.xpic_model_drift_kinetic_trace, self._dk_params(qm, mp, dt, eps, delta, maxit), state, steps, model, region,
+            sample_every, exit_step, step0, keep_samples)[:7])
 
     # ---- time-dependent analytic fields (include/xpic_hip.h: xpic_field_envelope): the two model traces with a time
     # envelope on the model's E.  envelope: what field_envelope(...) returns, or None (constant: the model trace itself);
@@ -887,37 +897,16 @@ class Context:
                                      exit_step=None, step0=0, keep_samples=True, atol=1e-7, rtol=1e-7, maxit=30, sums=None):
         """model_full_orbit_trace with an envelope -> TimedTrace.  sums: True for sums that start at 0, or the [n][4] array a
         previous call returned, so that calls compose; None: no sums"""
-        state, samples, alive, ex, reg, tot, mx = self._model_args(state, steps, sample_every, region, exit_step, step0,
-                                                                       keep_samples)
-        n = state.shape[0]
-        if sums is not None:
-            sums = np.zeros((n, 4)) if sums is True else np.array(sums, dtype=np.float64).reshape(n, 4)
-        P = self._fo_params(scheme, qm, dt, atol, rtol, maxit)
-        removed, i64 = C.c_int64(), C.POINTER(C.c_int64)
-        bare = region is None and exit_step is None  # the closed trace: the library gets no exit_step and no removed
-        self._ck(self.L.xpic_model_full_orbit_trace_timed(
-            self.h, C.c_int64(n), C.byref(P), None if model is None else C.byref(model),
-            None if envelope is None else C.byref(envelope), C.c_int64(int(steps)), C.c_int64(int(sample_every)), _dp(state),
-            None if samples is None else _dp(samples), tot.ctypes.data_as(i64), mx.ctypes.data_as(C.POINTER(C.c_int)),
-            C.byref(reg), None if bare else ex.ctypes.data_as(i64), alive.ctypes.data_as(i64) if sample_every else None,
-            None if bare else C.byref(removed), None if sums is None else _dp(sums)))
-        return TimedTrace(state, samples, ex, alive, removed.value, tot, mx, sums)
+        return TimedTrace(*self._model_trace(
+            self.L.xpic_model_full_orbit_trace_timed, self._fo_params(scheme, qm, dt, atol, rtol, maxit), state, steps, model,
+            region, sample_every, exit_step, step0, keep_samples, envelope, sums))
 
     def model_drift_kinetic_trace_timed(self, state, steps, qm, mp, dt, model, envelope, region=None, sample_every=0,
                                         exit_step=None, step0=0, keep_samples=True, eps=1e-12, delta=1e-12, maxit=30):
         """model_drift_kinetic_trace with an envelope -> OpenTrace"""
-        state, samples, alive, ex, reg, tot, mx = self._model_args(state, steps, sample_every, region, exit_step, step0,
-                                                                       keep_samples)
-        P = self._dk_params(qm, mp, dt, eps, delta, maxit)
-        removed, i64 = C.c_int64(), C.POINTER(C.c_int64)
-        bare = region is None and exit_step is None
-        self._ck(self.L.xpic_model_drift_kinetic_trace_timed(
-            self.h, C.c_int64(state.shape[0]), C.byref(P), None if model is None else C.byref(model),
-            None if envelope is None else C.byref(envelope), C.c_int64(int(steps)), C.c_int64(int(sample_every)), _dp(state),
-            None if samples is None else _dp(samples), tot.ctypes.data_as(i64), mx.ctypes.data_as(C.POINTER(C.c_int)),
-            C.byref(reg), None if bare else ex.ctypes.data_as(i64), alive.ctypes.data_as(i64) if sample_every else None,
-            None if bare else C.byref(removed)))
-        return OpenTrace(state, samples, ex, alive, removed.value, tot, mx)
+        return OpenTrace(*self._model_trace(
+            self.L.xpic_model_drift_kinetic_trace_timed, self._dk_params(qm, mp, dt, eps, delta, maxit), state, steps, model,
+            region, sample_every, exit_step, step0, keep_samples, envelope)[:7])
 
     def envelope_factors(self, envelope, dt, step0, nsteps):
         """-> the factors of steps step0 .. step0 + nsteps - 1, evaluated on the device as the traces evaluate them"""

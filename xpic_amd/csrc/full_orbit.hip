@@ -33,17 +33,6 @@ namespace {
 constexpr int kBlock = kLaneBlock; // batch.h: lane_grid launches workgroups of this size
 constexpr int kLaunchSteps = XPIC_FO_LAUNCH_STEPS;
 
-__device__ inline void fo_load(const double* __restrict__ s, long n, long q, FOPoint& p)
-{
-  p.r[0] = s[q]; p.r[1] = s[n + q]; p.r[2] = s[2 * n + q];
-  p.p[0] = s[3 * n + q]; p.p[1] = s[4 * n + q]; p.p[2] = s[5 * n + q];
-}
-__device__ inline void fo_store(double* __restrict__ s, long n, long q, const FOPoint& p)
-{
-  s[q] = p.r[0]; s[n + q] = p.r[1]; s[2 * n + q] = p.r[2];
-  s[3 * n + q] = p.p[0]; s[4 * n + q] = p.p[1]; s[5 * n + q] = p.p[2];
-}
-
 // one step of P.scheme; CN: CrankNicolsonPush::process from the guess pn = p0, -> its iteration number
 template <bool CN>
 __device__ inline int fo_one(const GridDev& g, const double* __restrict__ E, const double* __restrict__ B,

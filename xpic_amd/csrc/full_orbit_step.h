@@ -18,6 +18,18 @@ struct FOPoint {
   double r[3], p[3];
 };
 
+// a lane's point in the [6][n] state of the traces
+__device__ inline void fo_load(const double* __restrict__ s, long n, long q, FOPoint& p)
+{
+  p.r[0] = s[q]; p.r[1] = s[n + q]; p.r[2] = s[2 * n + q];
+  p.p[0] = s[3 * n + q]; p.p[1] = s[4 * n + q]; p.p[2] = s[5 * n + q];
+}
+__device__ inline void fo_store(double* __restrict__ s, long n, long q, const FOPoint& p)
+{
+  s[q] = p.r[0]; s[n + q] = p.r[1]; s[2 * n + q] = p.r[2];
+  s[3 * n + q] = p.p[0]; s[4 * n + q] = p.p[1]; s[5 * n + q] = p.p[2];
+}
+
 // Vector3::length (src/utils/vector3.h:160-164) is std::hypot of three arguments
 __device__ inline double fo_len3(const double* a)
 {

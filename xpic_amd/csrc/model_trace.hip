@@ -3,14 +3,23 @@
 //   tests/drift_kinetic_push/drift_kinetic_push_ex1 .. ex5, ex9.cpp     DriftKineticPush (callback at rn)
 //   tests/boris_push/boris_push_ex*.cpp, drift_kinetic_push_ex9.cpp     process_<id> (fields at the particle's r)
 //   tests/crank_nicolson_push/crank_nicolson_push_ex1, ex2.cpp, ex9     CrankNicolsonPush (ex9.cpp:75-78: at (r1 + r0) / 2)
-// for a batch.  The models are field_model.h's; the step arithmetic is full_orbit_step.h's and drift_kinetic_step.h's own
-// text, instantiated with a field source that evaluates the model in registers where the grid source gathers.  One lane
-// per particle, fp64, no cross-lane operation but open_tally's.  One kernel per pusher serves the closed trace, the open
-// trace and the one-step push: the region rule (trace_open.h) is skipped for XPIC_GEOM_NONE, which the host passes as
-// R.kind < 0.  No grid vector is read, so no index is formed from a position and any context will do.
+// for a batch, and the same traces with a time envelope on the model's E: the one pusher example whose
+// callback captures the step index,
+//   tests/crank_nicolson_push/crank_nicolson_push_ex3.cpp:39-58         E_p = E0 * (t * dt); B_p = B0;
+// with the running sums of its two checks (:51-57) kept on the device.  The models are field_model.h's; the step
+// arithmetic is full_orbit_step.h's and drift_kinetic_step.h's own text, instantiated with a field source that evaluates
+// the model in registers where the grid source gathers.  The drift-kinetic kernel is one text for both: its Clock yields
+// the field source of a step, ModelSource (model_source.h) for the static clock and TimedModelSource (timed_source.h)
+// with the factor of step R.step0 + first + done for the envelope clock.  The full-orbit kernel has two texts,
+// k_model_fo_trace<CN> and k_timed_fo_trace<CN, SUMS>, which forms the same source at the top of every step (DESIGN.md
+// 5o has the measurement that keeps them apart).  Either way every field evaluation inside a step sees the
+// same factor.  One lane per particle, fp64, no cross-lane operation but open_tally's.  Each kernel serves the closed
+// trace, the open trace and the one-step push: the region rule (trace_open.h) is skipped for XPIC_GEOM_NONE, which the
+// host passes as R.kind < 0.  No grid vector is read, so no index is formed from a position and any context will do.
 // Every loop is bounded by a constant or by an argument the entry points have range-checked: fo maxit <= XPIC_FO_MAXIT,
 // 1 <= dk maxit <= XPIC_MODEL_DK_MAXIT, at most XPIC_MODEL_LAUNCH_STEPS steps per launch.  Every global index is formed
-// under q < n, row < nsamp or i < nown.  The staging is batch.h's batch_trace_open with the "never" policy.
+// under q < n, row < nsamp, i < nown or i < nsteps.  The staging is batch.h's batch_trace_open with the "never" policy;
+// sums_4 travels as [4][n] in a DevScratch of this file.
 #include <algorithm>
 #include <cmath>
 #include <vector>
@@ -28,6 +37,7 @@
 #include "full_orbit_step.h"
 #include "drift_kinetic_step.h"
 #include "model_source.h"
+#include "timed_source.h"
 
 namespace xpic {
 
@@ -37,18 +47,21 @@ constexpr int kBlock = kLaneBlock; // batch.h: lane_grid launches workgroups of 
 constexpr int kLaunchSteps = XPIC_MODEL_LAUNCH_STEPS;
 static_assert(kLaunchSteps <= kOpenRows, "open_tally holds one row per step of a launch");
 
-// (ModelSource, the analytic field source of the step functions, is model_source.h's)
-
-__device__ inline void fo_load(const double* __restrict__ s, long n, long q, FOPoint& p)
-{
-  p.r[0] = s[q]; p.r[1] = s[n + q]; p.r[2] = s[2 * n + q];
-  p.p[0] = s[3 * n + q]; p.p[1] = s[4 * n + q]; p.p[2] = s[5 * n + q];
-}
-__device__ inline void fo_store(double* __restrict__ s, long n, long q, const FOPoint& p)
-{
-  s[q] = p.r[0]; s[n + q] = p.r[1]; s[2 * n + q] = p.r[2];
-  s[3 * n + q] = p.p[0]; s[4 * n + q] = p.p[1]; s[5 * n + q] = p.p[2];
-}
+// What yields the field source of a step (counted from the start of the whole trace).  k_model_dk_trace takes its clock
+// by value where the model stood in the argument list.  The static clock: the model as it is.
+struct StaticClock {
+  xpic_field_model M;
+  __device__ inline ModelSource at(long long, double) const { return ModelSource{M}; }
+};
+// The envelope clock: the model with the step's factor on E; a constant envelope multiplies nothing (on == false)
+struct EnvelopeClock {
+  xpic_field_model M;
+  xpic_field_envelope V;
+  __device__ inline TimedModelSource at(long long step, double dt) const
+  {
+    return TimedModelSource{{M}, V.kind != XPIC_ENV_CONSTANT, envelope_factor(V, step, dt)};
+  }
+};
 
 __global__ void __launch_bounds__(kBlock) k_model_fields(xpic_field_model M, long n, const double* __restrict__ r3,
   double* __restrict__ out)
@@ -127,16 +140,83 @@ __global__ void __launch_bounds__(kBlock) k_model_fo_trace(GridDev g, xpic_field
   open_tally<kBlock>(live, gone, first + done, first, ns, sample_every, nsamp, alive, removed);
 }
 
-// k_dk_trace_open (drift_kinetic.hip) on the model
-__global__ void __launch_bounds__(kBlock) k_model_dk_trace(GridDev g, xpic_field_model M, xpic_dk_params P, OpenRegion R,
-  long n, double* __restrict__ s, long first, int nsteps, long sample_every, long nsamp, double* __restrict__ samples,
+// the terms of ex3's two checks for the step p0 -> pn (ex3.cpp:51-57), added to the lane's sums: the energy balance
+// with the work of the step's E at the midpoint, and vh.transverse_to(B_s) (Vector3::parallel_to / transverse_to,
+// src/utils/vector3.h:195-205, statement by statement)
+__device__ inline void ex3_sums(const TimedModelSource& src, double qm, double dt, const FOPoint& pn, const FOPoint& p0,
+  double* sum)
+{
+  double vh[3], Es[3], Bs[3];
+#pragma unroll
+  for (int c = 0; c < 3; ++c) vh[c] = 0.5 * (pn.p[c] + p0.p[c]);
+  src.segment(pn.r, p0.r, Es, Bs);
+  sum[0] += 0.5 * (fo_dot3(pn.p, pn.p) - fo_dot3(p0.p, p0.p)) - qm * dt * fo_dot3(vh, Es);
+  const double vb = fo_dot3(vh, Bs), bb = fo_dot3(Bs, Bs);
+#pragma unroll
+  for (int c = 0; c < 3; ++c) sum[1 + c] += vh[c] - (vb * Bs[c]) / bb;
+}
+
+// k_model_fo_trace<CN> with the step's factor; SUMS: sums [4][n], read and written.  It keeps its own text: merged with
+// k_model_fo_trace under a clock, the Chin instance without sums measured 3 % slower
+template <bool CN, bool SUMS>
+__global__ void __launch_bounds__(kBlock) k_timed_fo_trace(GridDev g, xpic_field_model M, xpic_field_envelope V,
+  xpic_fo_params P, OpenRegion R, long n, double* __restrict__ s, long first, int nsteps, long sample_every, long nsamp,
+  double* __restrict__ samples, long long* __restrict__ it_sum, int* __restrict__ it_max, long long* __restrict__ exit_step,
+  unsigned long long* alive, unsigned long long* removed, double* __restrict__ sums)
+{
+  const long q = (long)blockIdx.x * kBlock + threadIdx.x;
+  const bool live = q < n && exit_step[q] < 0;
+  const int ns = nsteps < kLaunchSteps ? nsteps : kLaunchSteps;
+  const bool on = V.kind != XPIC_ENV_CONSTANT;
+  int done = 0;
+  bool gone = false;
+  if (live) {
+    FOPoint pn;
+    fo_load(s, n, q, pn);
+    long long total = CN ? it_sum[q] : 0;
+    int most = CN ? it_max[q] : 0;
+    double sum[4] = {0.0, 0.0, 0.0, 0.0};
+    if (SUMS) {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) sum[k] = sums[k * n + q];
+    }
+    for (; done < ns; ++done) {
+      if (R.kind >= 0 && !open_keep(g, R, pn.r)) { gone = true; break; }
+      const TimedModelSource src{{M}, on, envelope_factor(V, R.step0 + first + done, P.dt)};
+      const FOPoint p0 = pn;
+      int it = 0;
+      if (CN) it = fo_cn_process(src, P.qm, P.dt, P.atol, P.rtol, P.maxit, pn, p0);
+      else fo_step(P.scheme, src, P.qm, P.dt, pn);
+      if (SUMS) ex3_sums(src, P.qm, P.dt, pn, p0, sum);
+      total += it;
+      most = it > most ? it : most;
+      const long step = first + done + 1;
+      if (samples && step % sample_every == 0) {
+        const long row = step / sample_every - 1;
+        if (row < nsamp) fo_store(samples + row * 6 * n, n, q, pn);
+      }
+    }
+    fo_store(s, n, q, pn);
+    if (CN) { it_sum[q] = total; it_max[q] = most; }
+    if (SUMS) {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) sums[k * n + q] = sum[k];
+    }
+    if (gone) exit_step[q] = R.step0 + first + done;
+  }
+  open_tally<kBlock>(live, gone, first + done, first, ns, sample_every, nsamp, alive, removed);
+}
+
+// k_dk_trace_open (drift_kinetic.hip) on the model of the step's clock
+template <class Clock>
+__global__ void __launch_bounds__(kBlock) k_model_dk_trace(GridDev g, Clock C, xpic_dk_params P, OpenRegion R, long n,
+  double* __restrict__ s, long first, int nsteps, long sample_every, long nsamp, double* __restrict__ samples,
   long long* __restrict__ it_total, int* __restrict__ it_max, long long* __restrict__ exit_step, unsigned long long* alive,
   unsigned long long* removed)
 {
   const long q = (long)blockIdx.x * kBlock + threadIdx.x;
   const bool live = q < n && exit_step[q] < 0;
   const int ns = nsteps < kLaunchSteps ? nsteps : kLaunchSteps;
-  const ModelSource src{M};
   int done = 0;
   bool gone = false;
   if (live) {
@@ -146,6 +226,7 @@ __global__ void __launch_bounds__(kBlock) k_model_dk_trace(GridDev g, xpic_field
     int most = it_max[q];
     for (; done < ns; ++done) {
       if (R.kind >= 0 && !open_keep(g, R, pn.r)) { gone = true; break; }
+      const auto src = C.at(R.step0 + first + done, P.dt);
       p0 = pn;
       const int it = dk_process(src, P, p0, pn);
       total += it;
@@ -164,32 +245,73 @@ __global__ void __launch_bounds__(kBlock) k_model_dk_trace(GridDev g, xpic_field
   open_tally<kBlock>(live, gone, first + done, first, ns, sample_every, nsamp, alive, removed);
 }
 
-int model_ok(const char* who, const xpic_field_model* model)
+// the factors of steps step0 .. step0 + nsteps - 1 by the device function the traces call
+__global__ void __launch_bounds__(kBlock) k_envelope_factors(xpic_field_envelope V, double dt, long long step0, long nsteps,
+  double* __restrict__ out)
+{
+  const long i = (long)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= nsteps) return;
+  out[i] = envelope_factor(V, step0 + i, dt);
+}
+
+int model_ok(const std::string& who, const xpic_field_model* model)
 {
   const char* bad = model_check(model);
-  XPIC_CHECK(!bad, std::string(who) + ": " + (bad ? bad : ""));
+  XPIC_CHECK(!bad, who + ": " + (bad ? bad : ""));
+  return 0;
+}
+
+// the envelope a call runs with: a null one is the constant one
+int timed_envelope(const std::string& who, const xpic_field_envelope* in, xpic_field_envelope* V)
+{
+  const char* bad = envelope_check(in);
+  XPIC_CHECK(!bad, who + ": " + (bad ? bad : ""));
+  *V = xpic_field_envelope{};
+  if (in) *V = *in;
   return 0;
 }
 
 // open_region (trace_open.h) with XPIC_GEOM_NONE allowed and `compact` not read
-int model_region(const char* who, const xpic_trace_region* in, OpenRegion* R)
+int model_region(const std::string& who, const xpic_trace_region* in, OpenRegion* R)
 {
-  XPIC_CHECK(in, std::string(who) + ": region is null");
+  XPIC_CHECK(in, who + ": region is null");
   XPIC_CHECK(in->geometry == XPIC_GEOM_NONE || in->geometry == XPIC_GEOM_BOX || in->geometry == XPIC_GEOM_CYLINDER,
-    std::string(who) + ": unknown geometry kind");
-  XPIC_CHECK(in->step0 >= 0, std::string(who) + ": step0 is negative");
+    who + ": unknown geometry kind");
+  XPIC_CHECK(in->step0 >= 0, who + ": step0 is negative");
   R->kind = in->geometry;
   for (int i = 0; i < 7; ++i) R->a[i] = in->geom[i];
   R->step0 = in->step0;
   return 0;
 }
 
-// The checks and the driver the two traces share, after their own checks of params.  Under XPIC_GEOM_NONE the optional
-// outputs that are null get stand-ins here, so the kernel and batch_trace_open see one shape of call.
+// the checks a pusher's timed and untimed entry points make first, up to the model
+int fo_checks(const std::string& who, xpic_ctx* ctx, int64_t n, const xpic_fo_params* params, const xpic_field_model* model)
+{
+  XPIC_CHECK(ctx != nullptr, "null context");
+  XPIC_CHECK(n >= 0, who + ": n is negative");
+  XPIC_CHECK(params, who + ": params is null");
+  XPIC_CHECK(params->scheme >= 0 && params->scheme < XPIC_FO_NSCHEMES, who + ": unknown scheme id");
+  if (params->scheme == XPIC_FO_CN)
+    XPIC_CHECK(params->maxit >= 1 && params->maxit <= XPIC_FO_MAXIT, who + ": maxit must be within 1 .. 64");
+  return model_ok(who, model);
+}
+int dk_checks(const std::string& who, xpic_ctx* ctx, int64_t n, const xpic_dk_params* params, const xpic_field_model* model)
+{
+  XPIC_CHECK(ctx != nullptr, "null context");
+  XPIC_CHECK(n >= 0, who + ": n is negative");
+  XPIC_CHECK(params, who + ": params is null");
+  XPIC_CHECK(params->maxit >= 1 && params->maxit <= XPIC_MODEL_DK_MAXIT, who + ": maxit must be within 1 .. 1024");
+  XPIC_CHECK(params->mp != 0.0, who + ": mp must not be 0");
+  return model_ok(who, model);
+}
+
+// The checks and the driver all four traces share, after their own checks of params.  Under XPIC_GEOM_NONE the optional
+// outputs that are null get stand-ins here, so the kernel and batch_trace_open see one shape of call.  sums_4 (null:
+// none) is staged as [4][n] around the launches.  launch(..., sums): the device's [4][n], null without sums_4.
 template <class Launch>
 int model_trace(xpic_ctx* ctx, const std::string& who, const char* label, int64_t n, bool counters, int64_t steps,
   int64_t sample_every, double* state_6, double* samples, int64_t* it_sum, int* it_max, const OpenRegion& R,
-  int64_t* exit_step, int64_t* alive, int64_t* removed, Launch launch)
+  int64_t* exit_step, int64_t* alive, int64_t* removed, double* sums_4, Launch launch)
 {
   const bool open = R.kind >= 0;
   XPIC_CHECK(n <= ((int64_t)1 << 36), who + ": n is larger than 2^36");
@@ -210,15 +332,42 @@ int model_trace(xpic_ctx* ctx, const std::string& who, const char* label, int64_
     exit_step = ex_own.data();
   }
   int64_t rm_own = 0;
+  std::vector<double> hsum;
+  DevScratch<double> dsum;
+  if (sums_4) {
+    to_soa(sums_4, n, hsum, 4);
+    XPIC_CALL(dsum.alloc(4 * n));
+    XPIC_CALL(upload(dsum, hsum.data(), 4 * n, ctx->stream));
+  }
   XPIC_CALL(batch_trace_open(ctx, label, label, kLaunchSteps, n, steps, sample_every, nsamp, counters, XPIC_COMPACT_NEVER,
     R.step0, state_6, samples, it_sum, it_max, exit_step, alive, removed ? removed : &rm_own,
     [&](double* s, const int64_t*, long, long first, int ns, double* sm, long long* sum, int* mx, long long* ex,
-      unsigned long long* al, unsigned long long* rm) { launch(s, first, ns, (long)nsamp, sm, sum, mx, ex, al, rm); }));
+      unsigned long long* al, unsigned long long* rm) { launch(s, first, ns, (long)nsamp, sm, sum, mx, ex, al, rm, dsum.p); }));
+  if (sums_4) {
+    XPIC_CALL(download(hsum.data(), dsum, 4 * n, ctx->stream));
+    XPIC_HIP(hipStreamSynchronize(ctx->stream));
+    to_aos(hsum.data(), n, sums_4, 4);
+  }
   if (!counters) {
     if (it_sum) std::fill(it_sum, it_sum + n, (int64_t)0);
     if (it_max) std::fill(it_max, it_max + n, 0);
   }
   return 0;
+}
+
+// the drift-kinetic trace of either clock, after the checks: `label` names the profile entry
+template <class Clock>
+int dk_trace(xpic_ctx* ctx, const std::string& who, const char* label, int64_t n, const xpic_dk_params& P, const Clock& C,
+  int64_t steps, int64_t sample_every, double* state_6, double* samples, int64_t* it_total, int* it_max, const OpenRegion& R,
+  int64_t* exit_step, int64_t* alive, int64_t* removed)
+{
+  return model_trace(ctx, who, label, n, true, steps, sample_every, state_6, samples, it_total, it_max, R, exit_step, alive,
+    removed, nullptr,
+    [&](double* s, long first, int ns, long nsamp, double* sm, long long* sum, int* mx, long long* ex, unsigned long long* al,
+      unsigned long long* rm, double*) {
+      hipLaunchKernelGGL(k_model_dk_trace<Clock>, lane_grid(n), dim3(kBlock), 0, ctx->stream, ctx->g, C, P, R, (long)n, s,
+        first, ns, (long)sample_every, nsamp, sm, sum, mx, ex, al, rm);
+    });
 }
 
 }  // namespace
@@ -278,19 +427,14 @@ int xpic_model_full_orbit_trace(xpic_ctx* ctx, int64_t n, const xpic_fo_params* 
   const xpic_trace_region* region, int64_t* exit_step, int64_t* alive, int64_t* removed)
 {
   const std::string who = "model_full_orbit_trace";
-  XPIC_CHECK(ctx != nullptr, "null context");
-  XPIC_CHECK(n >= 0, who + ": n is negative");
-  XPIC_CHECK(params, who + ": params is null");
-  XPIC_CHECK(params->scheme >= 0 && params->scheme < XPIC_FO_NSCHEMES, who + ": unknown scheme id");
-  const bool cn = params->scheme == XPIC_FO_CN;
-  if (cn) XPIC_CHECK(params->maxit >= 1 && params->maxit <= XPIC_FO_MAXIT, who + ": maxit must be within 1 .. 64");
-  XPIC_CALL(model_ok(who.c_str(), model));
+  XPIC_CALL(fo_checks(who, ctx, n, params, model));
   OpenRegion R;
-  XPIC_CALL(model_region(who.c_str(), region, &R));
+  XPIC_CALL(model_region(who, region, &R));
+  const bool cn = params->scheme == XPIC_FO_CN;
   return model_trace(ctx, who, "model_fo_trace", n, cn, steps, sample_every, p_6, samples, iterations_sum, iterations_max, R,
-    exit_step, alive, removed,
+    exit_step, alive, removed, nullptr,
     [&](double* s, long first, int ns, long nsamp, double* sm, long long* sum, int* mx, long long* ex, unsigned long long* al,
-      unsigned long long* rm) {
+      unsigned long long* rm, double*) {
       hipLaunchKernelGGL(cn ? k_model_fo_trace<true> : k_model_fo_trace<false>, lane_grid(n), dim3(kBlock), 0, ctx->stream,
         ctx->g, *model, *params, R, (long)n, s, first, ns, (long)sample_every, nsamp, sm, sum, mx, ex, al, rm);
     });
@@ -301,21 +445,73 @@ int xpic_model_drift_kinetic_trace(xpic_ctx* ctx, int64_t n, const xpic_dk_param
   const xpic_trace_region* region, int64_t* exit_step, int64_t* alive, int64_t* removed)
 {
   const std::string who = "model_drift_kinetic_trace";
-  XPIC_CHECK(ctx != nullptr, "null context");
-  XPIC_CHECK(n >= 0, who + ": n is negative");
-  XPIC_CHECK(params, who + ": params is null");
-  XPIC_CHECK(params->maxit >= 1 && params->maxit <= XPIC_MODEL_DK_MAXIT, who + ": maxit must be within 1 .. 1024");
-  XPIC_CHECK(params->mp != 0.0, who + ": mp must not be 0");
-  XPIC_CALL(model_ok(who.c_str(), model));
+  XPIC_CALL(dk_checks(who, ctx, n, params, model));
   OpenRegion R;
-  XPIC_CALL(model_region(who.c_str(), region, &R));
-  return model_trace(ctx, who, "model_dk_trace", n, true, steps, sample_every, state_6, samples, iterations_total,
-    iterations_max, R, exit_step, alive, removed,
+  XPIC_CALL(model_region(who, region, &R));
+  return dk_trace(ctx, who, "model_dk_trace", n, *params, StaticClock{*model}, steps, sample_every, state_6, samples,
+    iterations_total, iterations_max, R, exit_step, alive, removed);
+}
+
+int xpic_model_full_orbit_trace_timed(xpic_ctx* ctx, int64_t n, const xpic_fo_params* params, const xpic_field_model* model,
+  const xpic_field_envelope* envelope, int64_t steps, int64_t sample_every, double* p_6, double* samples,
+  int64_t* iterations_sum, int* iterations_max, const xpic_trace_region* region, int64_t* exit_step, int64_t* alive,
+  int64_t* removed, double* sums_4)
+{
+  const std::string who = "model_full_orbit_trace_timed";
+  XPIC_CALL(fo_checks(who, ctx, n, params, model));
+  xpic_field_envelope V;
+  XPIC_CALL(timed_envelope(who, envelope, &V));
+  OpenRegion R;
+  XPIC_CALL(model_region(who, region, &R));
+  const bool cn = params->scheme == XPIC_FO_CN, sums = sums_4 != nullptr;
+  auto kernel = cn ? (sums ? k_timed_fo_trace<true, true> : k_timed_fo_trace<true, false>)
+                   : (sums ? k_timed_fo_trace<false, true> : k_timed_fo_trace<false, false>);
+  return model_trace(ctx, who, "timed_fo_trace", n, cn, steps, sample_every, p_6, samples, iterations_sum, iterations_max, R,
+    exit_step, alive, removed, sums_4,
     [&](double* s, long first, int ns, long nsamp, double* sm, long long* sum, int* mx, long long* ex, unsigned long long* al,
-      unsigned long long* rm) {
-      hipLaunchKernelGGL(k_model_dk_trace, lane_grid(n), dim3(kBlock), 0, ctx->stream, ctx->g, *model, *params, R, (long)n, s,
-        first, ns, (long)sample_every, nsamp, sm, sum, mx, ex, al, rm);
+      unsigned long long* rm, double* sd) {
+      hipLaunchKernelGGL(kernel, lane_grid(n), dim3(kBlock), 0, ctx->stream, ctx->g, *model, V, *params, R, (long)n, s, first,
+        ns, (long)sample_every, nsamp, sm, sum, mx, ex, al, rm, sd);
     });
+}
+
+int xpic_model_drift_kinetic_trace_timed(xpic_ctx* ctx, int64_t n, const xpic_dk_params* params,
+  const xpic_field_model* model, const xpic_field_envelope* envelope, int64_t steps, int64_t sample_every, double* state_6,
+  double* samples, int64_t* iterations_total, int* iterations_max, const xpic_trace_region* region, int64_t* exit_step,
+  int64_t* alive, int64_t* removed)
+{
+  const std::string who = "model_drift_kinetic_trace_timed";
+  XPIC_CALL(dk_checks(who, ctx, n, params, model));
+  xpic_field_envelope V;
+  XPIC_CALL(timed_envelope(who, envelope, &V));
+  OpenRegion R;
+  XPIC_CALL(model_region(who, region, &R));
+  return dk_trace(ctx, who, "timed_dk_trace", n, *params, EnvelopeClock{*model, V}, steps, sample_every, state_6, samples,
+    iterations_total, iterations_max, R, exit_step, alive, removed);
+}
+
+int xpic_envelope_factors(xpic_ctx* ctx, const xpic_field_envelope* envelope, double dt, int64_t step0, int64_t nsteps,
+  double* out)
+{
+  const std::string who = "envelope_factors";
+  XPIC_CHECK(ctx != nullptr, "null context");
+  xpic_field_envelope V;
+  XPIC_CALL(timed_envelope(who, envelope, &V));
+  XPIC_CHECK(step0 >= 0, who + ": step0 is negative");
+  XPIC_CHECK(nsteps >= 0 && nsteps <= ((int64_t)1 << 31), who + ": nsteps must be within 0 .. 2^31");
+  XPIC_CHECK(out || nsteps == 0, who + ": out is null");
+  if (nsteps == 0) return 0;
+  DevScratch<double> o;
+  XPIC_CALL(o.alloc(nsteps));
+  {
+    Timed t(ctx, "envelope_factors");
+    hipLaunchKernelGGL(k_envelope_factors, lane_grid(nsteps), dim3(kBlock), 0, ctx->stream, V, dt, (long long)step0,
+      (long)nsteps, o.p);
+    XPIC_HIP(hipGetLastError());
+  }
+  XPIC_CALL(download(out, o, nsteps, ctx->stream));
+  XPIC_HIP(hipStreamSynchronize(ctx->stream));
+  return 0;
 }
 
 }  // extern "C"

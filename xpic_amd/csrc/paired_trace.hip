@@ -41,17 +41,7 @@ constexpr int kLaunchSteps = XPIC_PAIR_LAUNCH_STEPS;
 static_assert(kLaunchSteps <= kOpenRows, "the curve holds one LDS row per step of a launch");
 static_assert(4 * kOpenRows <= kBlock, "one thread per row and statistic finishes the curve");
 
-// fo_load / fo_store / fo_one: full_orbit.hip's
-__device__ inline void fo_load(const double* __restrict__ s, long n, long q, FOPoint& p)
-{
-  p.r[0] = s[q]; p.r[1] = s[n + q]; p.r[2] = s[2 * n + q];
-  p.p[0] = s[3 * n + q]; p.p[1] = s[4 * n + q]; p.p[2] = s[5 * n + q];
-}
-__device__ inline void fo_store(double* __restrict__ s, long n, long q, const FOPoint& p)
-{
-  s[q] = p.r[0]; s[n + q] = p.r[1]; s[2 * n + q] = p.r[2];
-  s[3 * n + q] = p.p[0]; s[4 * n + q] = p.p[1]; s[5 * n + q] = p.p[2];
-}
+// fo_one: full_orbit.hip's
 template <bool CN>
 __device__ inline int fo_one(const GridDev& g, const double* __restrict__ E, const double* __restrict__ B,
   const xpic_fo_params& P, FOPoint& pn)

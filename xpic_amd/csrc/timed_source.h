@@ -9,6 +9,9 @@
 #include <cmath>
 
 #include "field_model.h"
+#ifdef __HIPCC__
+#include "model_source.h"
+#endif
 
 namespace xpic {
 
@@ -41,29 +44,26 @@ namespace {
 // ModelSource with the step's factor on E: E_p = E_model * f component by component (Vector3R * scalar), B_p and
 // gradB_p untouched.  on == false (XPIC_ENV_CONSTANT): no factor at all, ModelSource's values as they are.
 struct TimedModelSource {
-  const xpic_field_model& m;
+  ModelSource src;
   bool on;
   double f;
   __device__ inline void scale(double* Ep) const
   {
     if (on) { Ep[0] = Ep[0] * f; Ep[1] = Ep[1] * f; Ep[2] = Ep[2] * f; }
   }
-  __device__ inline void dk(const double* rn, const double*, double* Ep, double* Bp, double* gBp) const
+  __device__ inline void dk(const double* rn, const double* r0, double* Ep, double* Bp, double* gBp) const
   {
-    model_fields(m, rn, Ep, Bp, gBp);
+    src.dk(rn, r0, Ep, Bp, gBp);
     scale(Ep);
   }
   __device__ inline void at(const double* r, double* Ep, double* Bp) const
   {
-    double gBp[3];
-    model_fields(m, r, Ep, Bp, gBp);
+    src.at(r, Ep, Bp);
     scale(Ep);
   }
   __device__ inline void segment(const double* rn, const double* r0, double* Ep, double* Bp) const
   {
-    const double rm[3] = {(r0[0] + rn[0]) / 2, (r0[1] + rn[1]) / 2, (r0[2] + rn[2]) / 2};
-    double gBp[3];
-    model_fields(m, rm, Ep, Bp, gBp);
+    src.segment(rn, r0, Ep, Bp);
     scale(Ep);
   }
 };

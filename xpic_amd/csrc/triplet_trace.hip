@@ -46,18 +46,6 @@ constexpr int kLaunchSteps = XPIC_TRIPLET_LAUNCH_STEPS;
 constexpr int kStats = XPIC_TRIPLET_NSTATS;
 static_assert(kLaunchSteps <= kOpenRows, "the curve holds one LDS row per step of a launch");
 
-// fo_load / fo_store: full_orbit.hip's
-__device__ inline void fo_load(const double* __restrict__ s, long n, long q, FOPoint& p)
-{
-  p.r[0] = s[q]; p.r[1] = s[n + q]; p.r[2] = s[2 * n + q];
-  p.p[0] = s[3 * n + q]; p.p[1] = s[4 * n + q]; p.p[2] = s[5 * n + q];
-}
-__device__ inline void fo_store(double* __restrict__ s, long n, long q, const FOPoint& p)
-{
-  s[q] = p.r[0]; s[n + q] = p.r[1]; s[2 * n + q] = p.r[2];
-  s[3 * n + q] = p.p[0]; s[4 * n + q] = p.p[1]; s[5 * n + q] = p.p[2];
-}
-
 // (a - b).length()
 __device__ inline double dist3(const double* a, const double* b)
 {
