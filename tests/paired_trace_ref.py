@@ -1,5 +1,5 @@
 """Plain numpy restatement of the reference's comparison of a guiding centre with the full orbit of the same particle,
-the model the kernel of xpic_amd/csrc/paired_trace.hip is tested against:
+the model the kernel of xpic_amd/csrc/compare_trace.hip is tested against:
 
   compare_step(...)   update_comparison_stats, the grid / Boris half   tests/drift_kinetic_push/drift_kinetic_push.h:293-329
   operands(...)       the two numbers each of its four errors is the difference of

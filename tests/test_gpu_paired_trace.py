@@ -1,4 +1,4 @@
-"""The paired trace on the device (xpic_amd/csrc/paired_trace.hip, include/xpic_hip.h: xpic_paired_trace): a guiding
+"""The paired trace on the device (xpic_amd/csrc/compare_trace.hip, include/xpic_hip.h: xpic_paired_trace): a guiding
 centre beside the full orbit of the same particle, with the reference's comparison of the two reduced on the device.  On
 the grid and the seeded fields of drift_kinetic_ref.case_fields (9 x 8 x 7 nodes, unequal spacings) with 300 pairs -- two
 workgroups of 256, the second partial -- over 70 steps, which cross the 64-step launch boundary."""

@@ -1,4 +1,4 @@
-"""The triplet trace on the device (xpic_amd/csrc/triplet_trace.hip, include/xpic_hip.h: xpic_triplet_trace): a guiding
+"""The triplet trace on the device (xpic_amd/csrc/compare_trace.hip, include/xpic_hip.h: xpic_triplet_trace): a guiding
 centre on an analytic model, a guiding centre on the grid filled from that model and a full orbit on the model, with the
 reference's seven-way comparison reduced on the device; and the grid-less pair, the same kernel without the grid member.
 On the grid of tests/test_gpu_paired_trace.py (9 x 8 x 7 nodes, unequal spacings) filled by xpic_set_model_field from a

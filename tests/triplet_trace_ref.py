@@ -1,5 +1,5 @@
 """Plain numpy restatement of the time loop of the reference's grid tests and of all seven maxima of its ComparisonStats,
-the model the kernel of xpic_amd/csrc/triplet_trace.hip is tested against:
+the model the kernel of xpic_amd/csrc/compare_trace.hip is tested against:
 
   grid_from_model(...)   FieldContext::initialize, tests/drift_kinetic_push/drift_kinetic_push.h:176-209: every component of
                          node (i, j, k) is the model at (i dx, j dy, k dz)

@@ -1,7 +1,9 @@
 // batch_host.cpp -- the host half of xpic_amd/csrc/batch.h (the part above its __HIPCC__ line: transposition,
 // trace_sample_bytes, trace_compacts, fill_frozen_samples) in a stand-alone program, so that a plain host compiler and its
 // sanitizers can run it without a GPU, on the shapes of tests/test_gpu_open_trace.py: 775 particles, 21 sample rows,
-// particles removed before their first step, after the 7th, the 146th and the 149th, and one that entered removed.
+// particles removed before their first step, after the 7th, the 146th and the 149th, and one that entered removed; and the
+// windowed transposition of a comparison trace's statistics: 775 records of width 7 with the window 3 .. 6 (columns 0 .. 2
+// keep their sentinels), width 4 with the full window, and no record at all.
 //   g++ -std=c++17 -g -O1 -fsanitize=address,undefined -fno-sanitize-recover=all -I xpic_amd/csrc tools/batch_host.cpp \
 //     -o /tmp/batch_host && /tmp/batch_host
 // prints "batch.h host staging: ok"; tests/test_batch_host.py builds it without the sanitizers and runs it.
@@ -38,6 +40,26 @@ int main()
   assert(!trace_compacts(0, 400, 775) && trace_compacts(0, 387, 775) && !trace_compacts(0, 388, 775));
   assert(!trace_compacts(1, 1, 775) && trace_compacts(2, 774, 775) && !trace_compacts(2, 775, 775) && !trace_compacts(0, 775, 775));
   fill_frozen_samples(0, 0, 1, 0, nullptr, nullptr, nullptr, nullptr);
+  // the statistics of the grid-less pair: columns 3 .. 6 of [n][7] travel as [4][n], columns 0 .. 2 stay as they are
+  std::vector<double> st7(7 * n), w4, out7(7 * n, -7.0);
+  for (size_t i = 0; i < st7.size(); ++i) st7[i] = 0.5 + (double)i;
+  to_soa(st7.data(), n, w4, 4, 7, 3);
+  assert(w4.size() == (size_t)4 * n);
+  for (int64_t q = 0; q < n; ++q)
+    for (int k = 0; k < 4; ++k) assert(w4[k * n + q] == st7[7 * q + 3 + k]);
+  to_aos(w4.data(), n, out7.data(), 4, 7, 3);
+  for (int64_t q = 0; q < n; ++q)
+    for (int k = 0; k < 7; ++k) assert(out7[7 * q + k] == (k < 3 ? -7.0 : st7[7 * q + k]));
+  // a pair's [n][4] with the full window is the plain transposition
+  std::vector<double> st4(st7.begin(), st7.begin() + 4 * n), full, plain, back4(4 * n);
+  to_soa(st4.data(), n, full, 4, 4, 0);
+  to_soa(st4.data(), n, plain, 4);
+  assert(full == plain);
+  to_aos(full.data(), n, back4.data(), 4, 4, 0);
+  assert(back4 == st4);
+  to_soa(nullptr, 0, w4, 4, 7, 3);
+  assert(w4.empty());
+  to_aos(w4.data(), 0, nullptr, 4, 7, 3);
   std::puts("batch.h host staging: ok");
   return 0;
 }

@@ -796,6 +796,31 @@ class Context:
             alive.ctypes.data_as(i64) if sample_every else None, C.byref(removed)))
         return OpenTrace(state, samples, ex, alive, removed.value, tot, mx)
 
+    def _compare_trace(self, fn, mismatch, p, centres, width, middle, steps, scheme, qm, mp, dt, sample_every, stats, atol,
+                       rtol, maxit, eps, delta, dk_maxit):
+        """the ctypes call of paired_trace and triplet_trace.  centres: the guiding centres in fn's order (None: an absent
+        one); width: the columns of stats and curve; middle: fn's arguments between dk and steps; mismatch: the message
+        for batches of different lengths -> the copies p and centres, stats, curve, and a (sum, max) pair of counters for
+        p and for every centre ((None, None) for an absent one)"""
+        members = [np.array(p, dtype=np.float64).reshape(-1, 6)]  # copies: the call works in place
+        members += [None if c is None else np.array(c, dtype=np.float64).reshape(-1, 6) for c in centres]
+        n = members[0].shape[0]
+        if any(m is not None and m.shape[0] != n for m in members):
+            raise XpicError(mismatch)
+        stats = np.zeros((n, width)) if stats is None else np.array(stats, dtype=np.float64).reshape(n, width)
+        nsamp = max(int(steps), 0) // int(sample_every) if sample_every else 0
+        curve = np.zeros((nsamp, width)) if sample_every else None
+        counters = [(None, None) if m is None else (np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int32))
+                    for m in members]
+        F = self._fo_params(scheme, qm, dt, atol, rtol, maxit)
+        D = self._dk_params(qm, mp, dt, eps, delta, dk_maxit)
+        types = (C.POINTER(C.c_int64), C.POINTER(C.c_int))
+        self._ck(fn(
+            self.h, C.c_int64(n), C.byref(F), C.byref(D), *middle, C.c_int64(int(steps)), C.c_int64(int(sample_every)),
+            *[None if m is None else _dp(m) for m in members], _dp(stats), _dp(curve) if sample_every else None,
+            *[None if a is None else a.ctypes.data_as(t) for pair in counters for a, t in zip(pair, types)]))
+        return members[0], members[1:], stats, curve, counters
+
     # ---- paired trace (include/xpic_hip.h: xpic_paired_trace): full_orbit_trace of p and drift_kinetic_trace of state
     # (guiding_centre(p, ..., orbit_centre=True) lays the two side by side) in lock-step, with the reference's comparison
     # of the pair (ComparisonStats, tests/drift_kinetic_push/drift_kinetic_push.h:253-329) kept on the device
@@ -803,25 +828,11 @@ class Context:
                      rtol=1e-7, maxit=30, eps=1e-12, delta=1e-12, dk_maxit=30):
         """-> PairedTrace.  stats: the running maxima a previous call returned (None: zeros), so that calls compose;
         sample_every: the curve's stride (0: no curve); maxit is the full orbit's (CN), dk_maxit the guiding centre's"""
-        p = np.array(p, dtype=np.float64).reshape(-1, 6)  # copies: the call works in place
-        state = np.array(state, dtype=np.float64).reshape(-1, 6)
-        n = p.shape[0]
-        if state.shape[0] != n:
-            raise XpicError("paired_trace: p and state hold different numbers of particles")
-        stats = np.zeros((n, 4)) if stats is None else np.array(stats, dtype=np.float64).reshape(n, 4)
-        nsamp = max(int(steps), 0) // int(sample_every) if sample_every else 0
-        curve = np.zeros((nsamp, 4)) if sample_every else None
-        fsum, fmax = np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int32)
-        dtot, dmax = np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int32)
-        F = self._fo_params(scheme, qm, dt, atol, rtol, maxit)
-        D = self._dk_params(qm, mp, dt, eps, delta, dk_maxit)
-        i64, i32 = C.POINTER(C.c_int64), C.POINTER(C.c_int)
-        self._ck(self.L.xpic_paired_trace(
-            self.h, C.c_int64(n), C.byref(F), C.byref(D), -1 if gradB_field is None else int(gradB_field),
-            C.c_int64(int(steps)), C.c_int64(int(sample_every)), _dp(p), _dp(state), _dp(stats),
-            _dp(curve) if sample_every else None, fsum.ctypes.data_as(i64), fmax.ctypes.data_as(i32),
-            dtot.ctypes.data_as(i64), dmax.ctypes.data_as(i32)))
-        return PairedTrace(p, state, stats, curve, fsum, fmax, dtot, dmax)
+        p, (state,), stats, curve, (fo, dk) = self._compare_trace(
+            self.L.xpic_paired_trace, "paired_trace: p and state hold different numbers of particles", p, [state], 4,
+            [-1 if gradB_field is None else int(gradB_field)], steps, scheme, qm, mp, dt, sample_every, stats, atol, rtol,
+            maxit, eps, delta, dk_maxit)
+        return PairedTrace(p, state, stats, curve, *fo, *dk)
 
     # ---- analytic field models (include/xpic_hip.h: xpic_field_model): the tracers with a closed-form field evaluated
     # on the device in the grid's place.  model: what field_model(...) returns.  region: a geometry dict as in the open
@@ -923,29 +934,13 @@ class Context:
         """-> TripletTrace.  state_grid=None selects the grid-less pair (state_model beside p; gradB_field is not read).
         stats: the running maxima a previous call returned (None: zeros), so that calls compose; sample_every: the curve's
         stride (0: no curve); maxit is the full orbit's (CN), dk_maxit the guiding centres'"""
-        p = np.array(p, dtype=np.float64).reshape(-1, 6)  # copies: the call works in place
-        sm = np.array(state_model, dtype=np.float64).reshape(-1, 6)
         grid = state_grid is not None
-        sg = np.array(state_grid, dtype=np.float64).reshape(-1, 6) if grid else None
-        n = p.shape[0]
-        if sm.shape[0] != n or (grid and sg.shape[0] != n):
-            raise XpicError("triplet_trace: p, state_model and state_grid hold different numbers of particles")
-        stats = np.zeros((n, 7)) if stats is None else np.array(stats, dtype=np.float64).reshape(n, 7)
-        nsamp = max(int(steps), 0) // int(sample_every) if sample_every else 0
-        curve = np.zeros((nsamp, 7)) if sample_every else None
-        fsum, fmax = np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int32)
-        mtot, mmax = np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int32)
-        gtot, gmax = (np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int32)) if grid else (None, None)
-        F = self._fo_params(scheme, qm, dt, atol, rtol, maxit)
-        D = self._dk_params(qm, mp, dt, eps, delta, dk_maxit)
-        i64, i32 = C.POINTER(C.c_int64), C.POINTER(C.c_int)
-        self._ck(self.L.xpic_triplet_trace(
-            self.h, C.c_int64(n), C.byref(F), C.byref(D), None if model is None else C.byref(model), int(grid),
-            -1 if gradB_field is None or not grid else int(gradB_field), C.c_int64(int(steps)), C.c_int64(int(sample_every)),
-            _dp(p), _dp(sm), _dp(sg) if grid else None, _dp(stats), _dp(curve) if sample_every else None,
-            fsum.ctypes.data_as(i64), fmax.ctypes.data_as(i32), mtot.ctypes.data_as(i64), mmax.ctypes.data_as(i32),
-            gtot.ctypes.data_as(i64) if grid else None, gmax.ctypes.data_as(i32) if grid else None))
-        return TripletTrace(p, sm, sg, stats, curve, fsum, fmax, mtot, mmax, gtot, gmax)
+        p, (sm, sg), stats, curve, (fo, dkm, dkg) = self._compare_trace(
+            self.L.xpic_triplet_trace, "triplet_trace: p, state_model and state_grid hold different numbers of particles", p,
+            [state_model, state_grid], 7,
+            [None if model is None else C.byref(model), int(grid), -1 if gradB_field is None or not grid else int(gradB_field)],
+            steps, scheme, qm, mp, dt, sample_every, stats, atol, rtol, maxit, eps, delta, dk_maxit)
+        return TripletTrace(p, sm, sg, stats, curve, *fo, *dkm, *dkg)
 
     def charge_collect(self):
         self._ck(self.L.xpic_charge_collect(self.h))

@@ -1,7 +1,6 @@
 // batch.h -- the host side that the batch particle calls share (eccapfim.hip, drift_kinetic.hip, full_orbit.hip,
-// paired_trace.hip): host arrays of particles are staged on the device, a kernel runs one lane per particle, the results
-// are copied back.  batch_pair_trace is batch_trace for two batches advanced side by side (paired_trace.hip),
-// batch_triplet_trace for three (triplet_trace.hip).
+// compare_trace.hip): host arrays of particles are staged on the device, a kernel runs one lane per particle, the results
+// are copied back.  batch_compare_trace is batch_trace for two or three batches advanced side by side (compare_trace.hip).
 // batch_trace_open is batch_trace for the open traces (trace_open.h, trace_open.hip): exit steps, alive counts, and the
 // list of live particles between launches.
 // DevScratch also owns every other device buffer that lives for one call (fields.hip, particles.hip, commands.hip,
@@ -17,17 +16,20 @@ namespace xpic {
 
 // ---- This part uses nothing from HIP: a plain host compiler compiles it (and a sanitizer build runs it) ----------------
 
-// [n][w] host records -> [w][n], and back; w = 6: a particle, w = 4: the statistics of a pair
-inline void to_soa(const double* aos, int64_t n, std::vector<double>& soa, int w = 6)
+// [n][w] host records -> [w][n], and back; w = 6: a particle.  With a stride: the w columns from `first` on of records
+// `stride` wide (the statistics of a comparison trace); the records' other columns are neither read nor written.
+inline void to_soa(const double* aos, int64_t n, std::vector<double>& soa, int w = 6, int stride = 0, int first = 0)
 {
+  const int s = stride ? stride : w;
   soa.resize((size_t)w * n);
   for (int64_t q = 0; q < n; ++q)
-    for (int k = 0; k < w; ++k) soa[(size_t)k * n + q] = aos[w * q + k];
+    for (int k = 0; k < w; ++k) soa[(size_t)k * n + q] = aos[s * q + first + k];
 }
-inline void to_aos(const double* soa, int64_t n, double* aos, int w = 6)
+inline void to_aos(const double* soa, int64_t n, double* aos, int w = 6, int stride = 0, int first = 0)
 {
+  const int s = stride ? stride : w;
   for (int64_t q = 0; q < n; ++q)
-    for (int k = 0; k < w; ++k) aos[w * q + k] = soa[(size_t)k * n + q];
+    for (int k = 0; k < w; ++k) aos[s * q + first + k] = soa[(size_t)k * n + q];
 }
 
 // The sample buffer of a trace of n >= 0 particles over steps >= 0 steps: a sample after every sample_every-th step
@@ -179,134 +181,85 @@ int batch_trace(xpic_ctx* c, const char* label, int launch_steps, int64_t n, int
   return 0;
 }
 
-// batch_trace for a full orbit and a guiding centre per lane (paired_trace.hip): `steps` steps of n > 0
-// pairs in place in p_6 and state_6, the running maxima stats_4 [n][4] staged as [4][n] (in and out), curve_4 [nsamp][4]
-// (null with nsamp == 0) zeroed on the device and written by the kernel's atomic maxima, the dk counters always and the fo
-// counters with `fo_counters`, all zeroed here.  launch(fo_s, dk_s, stats, first, nsteps, curve, fo_sum, fo_max, dk_sum,
-// dk_max) starts the kernel for steps first + 1 .. first + nsteps (curve: null without one; fo_sum, fo_max: null without
-// fo counters); each launch is timed under `label`.  Everything comes back once, after the last launch.
+// batch_trace for the members of a comparison trace, advanced side by side in one lane (compare_trace.hip; DESIGN.md 5k,
+// 5m, 5p).  A member is a host batch state_6 [n][6], in and out (null: the member is absent and nothing of it is staged),
+// with the sum and the maximum of its iteration counts when `counters` (zeroed here).
+struct CompareMember {
+  double* state_6;
+  int64_t* it_sum;
+  int* it_max;
+  bool counters;
+};
+constexpr int kCompareMembers = 3;
+// what a launch of a comparison trace gets: per member the state [6][n] and the counters (null where the member is absent
+// or has none), the travelling statistics [stats_w][n] and the curve (null without one)
+struct CompareDev {
+  double* s[kCompareMembers];
+  long long* it_sum[kCompareMembers];
+  int* it_max[kCompareMembers];
+  double* stats;
+  unsigned long long* curve;
+};
+
+// `steps` steps of n > 0 lanes in place.  The running maxima stats [n][stats_width] are in and out: the stats_w columns
+// from stats_first on travel, staged as [stats_w][n], and the other columns of the caller's array are neither read nor
+// written (a pair: 4 / 0 / 4; a triplet: 7 / 0 / 7; its grid-less pair: 7 / 3 / 4).  curve [nsamp][curve_width] (null with
+// nsamp == 0) is zeroed on the device and written by the kernel's atomic maxima.  launch(dev, first, nsteps) starts the
+// kernel for steps first + 1 .. first + nsteps; each launch is timed under `label`.  Everything comes back once, after the
+// last launch.
 template <class Launch>
-int batch_pair_trace(xpic_ctx* c, const char* label, int launch_steps, int64_t n, int64_t steps, int64_t nsamp,
-  bool fo_counters, double* p_6, double* state_6, double* stats_4, double* curve_4, int64_t* fo_sum, int* fo_max,
-  int64_t* dk_sum, int* dk_max, Launch launch)
+int batch_compare_trace(xpic_ctx* c, const char* label, int launch_steps, int64_t n, int64_t steps, int64_t nsamp,
+  const CompareMember (&member)[kCompareMembers], double* stats, int stats_width, int stats_first, int stats_w, double* curve,
+  int curve_width, Launch launch)
 {
   const size_t row = (size_t)6 * n; // doubles of one state
-  std::vector<double> hf, hd, hst;
-  to_soa(p_6, n, hf);
-  to_soa(state_6, n, hd);
-  to_soa(stats_4, n, hst, 4);
-  DevScratch<double> fs, ds, st, cv;
-  DevScratch<int64_t> ftot, dtot;
-  DevScratch<int> fmx, dmx;
-  XPIC_CALL(fs.alloc(row)); XPIC_CALL(ds.alloc(row)); XPIC_CALL(st.alloc(4 * n));
-  XPIC_CALL(dtot.alloc(n)); XPIC_CALL(dmx.alloc(n));
-  XPIC_CALL(zero(dtot, n, c->stream)); XPIC_CALL(zero(dmx, n, c->stream));
-  if (fo_counters) {
-    XPIC_CALL(ftot.alloc(n)); XPIC_CALL(fmx.alloc(n));
-    XPIC_CALL(zero(ftot, n, c->stream)); XPIC_CALL(zero(fmx, n, c->stream));
+  std::vector<double> h[kCompareMembers], hst;
+  DevScratch<double> s[kCompareMembers], st, cv;
+  DevScratch<int64_t> tot[kCompareMembers];
+  DevScratch<int> mx[kCompareMembers];
+  for (int m = 0; m < kCompareMembers; ++m) {
+    if (!member[m].state_6) continue;
+    to_soa(member[m].state_6, n, h[m]);
+    XPIC_CALL(s[m].alloc(row));
+    XPIC_CALL(upload(s[m], h[m].data(), row, c->stream));
+    if (!member[m].counters) continue;
+    XPIC_CALL(tot[m].alloc(n)); XPIC_CALL(mx[m].alloc(n));
+    XPIC_CALL(zero(tot[m], n, c->stream)); XPIC_CALL(zero(mx[m], n, c->stream));
   }
+  to_soa(stats, n, hst, stats_w, stats_width, stats_first);
+  XPIC_CALL(st.alloc((size_t)stats_w * n));
+  XPIC_CALL(upload(st, hst.data(), (size_t)stats_w * n, c->stream));
   if (nsamp > 0) {
-    XPIC_CALL(cv.alloc(4 * nsamp));
-    XPIC_CALL(zero(cv, 4 * nsamp, c->stream));
+    XPIC_CALL(cv.alloc(curve_width * nsamp));
+    XPIC_CALL(zero(cv, curve_width * nsamp, c->stream));
   }
-  XPIC_CALL(upload(fs, hf.data(), row, c->stream));
-  XPIC_CALL(upload(ds, hd.data(), row, c->stream));
-  XPIC_CALL(upload(st, hst.data(), 4 * n, c->stream));
+  CompareDev dev{};
+  for (int m = 0; m < kCompareMembers; ++m) {
+    dev.s[m] = s[m].p;
+    dev.it_sum[m] = (long long*)tot[m].p;
+    dev.it_max[m] = mx[m].p;
+  }
+  dev.stats = st.p;
+  dev.curve = (unsigned long long*)cv.p;
   for (int64_t first = 0; first < steps; first += launch_steps) {
     const int ns = (int)std::min<int64_t>(launch_steps, steps - first);
     Timed t(c, label);
-    launch(fs.p, ds.p, st.p, (long)first, ns, (unsigned long long*)cv.p, (long long*)ftot.p, fmx.p, (long long*)dtot.p, dmx.p);
+    launch(dev, (long)first, ns);
     XPIC_HIP(hipGetLastError());
   }
-  XPIC_CALL(download(hf.data(), fs, row, c->stream));
-  XPIC_CALL(download(hd.data(), ds, row, c->stream));
-  XPIC_CALL(download(hst.data(), st, 4 * n, c->stream));
-  XPIC_CALL(download(dk_sum, dtot, n, c->stream));
-  XPIC_CALL(download(dk_max, dmx, n, c->stream));
-  if (fo_counters) {
-    XPIC_CALL(download(fo_sum, ftot, n, c->stream));
-    XPIC_CALL(download(fo_max, fmx, n, c->stream));
+  for (int m = 0; m < kCompareMembers; ++m) {
+    if (s[m].p) XPIC_CALL(download(h[m].data(), s[m], row, c->stream));
+    if (tot[m].p) {
+      XPIC_CALL(download(member[m].it_sum, tot[m], n, c->stream));
+      XPIC_CALL(download(member[m].it_max, mx[m], n, c->stream));
+    }
   }
-  if (nsamp > 0) XPIC_CALL(download(curve_4, cv, 4 * nsamp, c->stream));
+  XPIC_CALL(download(hst.data(), st, (size_t)stats_w * n, c->stream));
+  if (nsamp > 0) XPIC_CALL(download(curve, cv, curve_width * nsamp, c->stream));
   XPIC_HIP(hipStreamSynchronize(c->stream));
-  to_aos(hf.data(), n, p_6);
-  to_aos(hd.data(), n, state_6);
-  to_aos(hst.data(), n, stats_4, 4);
-  return 0;
-}
-
-// batch_pair_trace for three members per lane (triplet_trace.hip): a full orbit p_6, a guiding centre on the
-// analytic model state_model_6 and, with `with_grid`, one on the grid state_grid_6, `steps` steps of n > 0 triplets in
-// place.  The running maxima stats_7 [n][7] are in and out: with the grid all seven columns are staged as [7][n]; without
-// it only columns 3 .. 6 are, as [4][n], and columns 0 .. 2 of the caller's array are neither read nor written.  curve_7
-// [nsamp][7] (null with nsamp == 0) is zeroed on the device and written by the kernel's atomic maxima.  The model
-// centre's counters always, the grid centre's with `with_grid`, the orbit's with `fo_counters`, all zeroed here.
-// launch(fo_s, dm_s, dg_s, stats, first, nsteps, curve, fo_sum, fo_max, dm_sum, dm_max, dg_sum, dg_max) starts the kernel
-// for steps first + 1 .. first + nsteps (null: dg_s, dg_sum, dg_max without the grid; curve without one; fo_sum, fo_max
-// without fo counters); each launch is timed under `label`.  Everything comes back once, after the last launch.
-template <class Launch>
-int batch_triplet_trace(xpic_ctx* c, const char* label, int launch_steps, int64_t n, int64_t steps, int64_t nsamp,
-  bool fo_counters, bool with_grid, double* p_6, double* state_model_6, double* state_grid_6, double* stats_7,
-  double* curve_7, int64_t* fo_sum, int* fo_max, int64_t* dm_sum, int* dm_max, int64_t* dg_sum, int* dg_max, Launch launch)
-{
-  const size_t row = (size_t)6 * n;                  // doubles of one state
-  const int j0 = with_grid ? 0 : 3, w = 7 - j0;      // the columns of stats_7 that travel
-  std::vector<double> hf, hm, hg, hst((size_t)w * n);
-  to_soa(p_6, n, hf);
-  to_soa(state_model_6, n, hm);
-  if (with_grid) to_soa(state_grid_6, n, hg);
-  for (int64_t q = 0; q < n; ++q)
-    for (int k = 0; k < w; ++k) hst[(size_t)k * n + q] = stats_7[7 * q + j0 + k];
-  DevScratch<double> fs, ms, gs, st, cv;
-  DevScratch<int64_t> ftot, mtot, gtot;
-  DevScratch<int> fmx, mmx, gmx;
-  XPIC_CALL(fs.alloc(row)); XPIC_CALL(ms.alloc(row)); XPIC_CALL(st.alloc((size_t)w * n));
-  XPIC_CALL(mtot.alloc(n)); XPIC_CALL(mmx.alloc(n));
-  XPIC_CALL(zero(mtot, n, c->stream)); XPIC_CALL(zero(mmx, n, c->stream));
-  if (with_grid) {
-    XPIC_CALL(gs.alloc(row)); XPIC_CALL(gtot.alloc(n)); XPIC_CALL(gmx.alloc(n));
-    XPIC_CALL(zero(gtot, n, c->stream)); XPIC_CALL(zero(gmx, n, c->stream));
-  }
-  if (fo_counters) {
-    XPIC_CALL(ftot.alloc(n)); XPIC_CALL(fmx.alloc(n));
-    XPIC_CALL(zero(ftot, n, c->stream)); XPIC_CALL(zero(fmx, n, c->stream));
-  }
-  if (nsamp > 0) {
-    XPIC_CALL(cv.alloc(7 * nsamp));
-    XPIC_CALL(zero(cv, 7 * nsamp, c->stream));
-  }
-  XPIC_CALL(upload(fs, hf.data(), row, c->stream));
-  XPIC_CALL(upload(ms, hm.data(), row, c->stream));
-  if (with_grid) XPIC_CALL(upload(gs, hg.data(), row, c->stream));
-  XPIC_CALL(upload(st, hst.data(), (size_t)w * n, c->stream));
-  for (int64_t first = 0; first < steps; first += launch_steps) {
-    const int ns = (int)std::min<int64_t>(launch_steps, steps - first);
-    Timed t(c, label);
-    launch(fs.p, ms.p, gs.p, st.p, (long)first, ns, (unsigned long long*)cv.p, (long long*)ftot.p, fmx.p, (long long*)mtot.p,
-      mmx.p, (long long*)gtot.p, gmx.p);
-    XPIC_HIP(hipGetLastError());
-  }
-  XPIC_CALL(download(hf.data(), fs, row, c->stream));
-  XPIC_CALL(download(hm.data(), ms, row, c->stream));
-  if (with_grid) XPIC_CALL(download(hg.data(), gs, row, c->stream));
-  XPIC_CALL(download(hst.data(), st, (size_t)w * n, c->stream));
-  XPIC_CALL(download(dm_sum, mtot, n, c->stream));
-  XPIC_CALL(download(dm_max, mmx, n, c->stream));
-  if (with_grid) {
-    XPIC_CALL(download(dg_sum, gtot, n, c->stream));
-    XPIC_CALL(download(dg_max, gmx, n, c->stream));
-  }
-  if (fo_counters) {
-    XPIC_CALL(download(fo_sum, ftot, n, c->stream));
-    XPIC_CALL(download(fo_max, fmx, n, c->stream));
-  }
-  if (nsamp > 0) XPIC_CALL(download(curve_7, cv, 7 * nsamp, c->stream));
-  XPIC_HIP(hipStreamSynchronize(c->stream));
-  to_aos(hf.data(), n, p_6);
-  to_aos(hm.data(), n, state_model_6);
-  if (with_grid) to_aos(hg.data(), n, state_grid_6);
-  for (int64_t q = 0; q < n; ++q)
-    for (int k = 0; k < w; ++k) stats_7[7 * q + j0 + k] = hst[(size_t)k * n + q];
+  for (int m = 0; m < kCompareMembers; ++m)
+    if (s[m].p) to_aos(h[m].data(), n, member[m].state_6);
+  to_aos(hst.data(), n, stats, stats_w, stats_width, stats_first);
   return 0;
 }
 

@@ -1,5 +1,5 @@
 // drift_kinetic_step.h -- the device functions of drift_kinetic.hip: the gather and one step of the drift-kinetic pusher,
-// the twin of full_orbit_step.h.  They are in a header so that paired_trace.hip, which advances a guiding centre beside a
+// the twin of full_orbit_step.h.  They are in a header so that compare_trace.hip, which advances a guiding centre beside a
 // full orbit in one lane, inlines the same text as k_dk_push and k_dk_trace.  Included after common.h, device_common.h and
 // ie_shape.h, with `#pragma clang fp contract(on)` in force: contraction per source expression only, so every caller
 // rounds alike.

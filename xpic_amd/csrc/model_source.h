@@ -1,6 +1,6 @@
 // model_source.h -- the analytic field source of the step functions (full_orbit_step.h: FOGrid, drift_kinetic_step.h:
 // DKGrid): where the grid sources gather, this one evaluates a model of field_model.h in registers, at the position the
-// reference's set_fields_callback is given.  Shared by model_trace.hip, triplet_trace.hip and
+// reference's set_fields_callback is given.  Shared by model_trace.hip, compare_trace.hip and
 // timed_source.h, whose TimedModelSource puts a step's factor on this one's E.  Device code only.
 #pragma once
 

@@ -1,4 +1,4 @@
-// pair_compare.h -- what paired_trace.hip and triplet_trace.hip share on the device: the guiding-centre / full-orbit half of
+// pair_compare.h -- what the two kernels of compare_trace.hip share on the device: the guiding-centre / full-orbit half of
 // the reference's update_comparison_stats (tests/drift_kinetic_push/drift_kinetic_push.h:311-328) and the wave maximum of
 // their curves.  Included after full_orbit_step.h and drift_kinetic_step.h, with `#pragma clang fp contract(on)` in force.
 #pragma once
