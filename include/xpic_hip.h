@@ -204,6 +204,22 @@ int xpic_set_tolerances(xpic_ctx* ctx, double rtol, double atol, int maxit);
  * ratio) is positive the polynomial's interval is proven; otherwise the surrogate runs on probation -- an iteration that does
  * not halve the residual, or is not finite, ends it and the solve goes on with kind 1. */
 int xpic_set_preconditioner(xpic_ctx* ctx, int kind, int degree);
+/* Test hooks of the preconditioner (read-only: a solve after them returns the bits it returned before).
+ * xpic_precond_apply: out = P r, as the next xpic_solve(ctx, op, ...) would apply P to a Krylov vector: the same choice
+ * between the polynomial in matM and the one in matM + <matL>, the same degree (XPIC_OP_MATM_GMRES: the "correct" solve's),
+ * the surrogate rebuilt first where a solve rebuilds it (and, as there, dropped for the matM polynomial where it is not
+ * finite).  No probation runs.  r and out are distinct vectors (r's ghost planes are refreshed on z-slabs); collective over
+ * the z-slabs.  Kind 0 and XPIC_OP_MATM_CG have no P: an error.
+ * xpic_precond_get: the surrogate as the last build left it (a solve or xpic_precond_apply with kind >= 3 on
+ * XPIC_OP_MATA_GMRES).  info[XPIC_PRECOND_NINFO] = {interval bottom, interval top, 2 + Gershgorin bound of <matL>, degree
+ * of the next apply on XPIC_OP_MATA_GMRES, rows scaled (0 / 1), interval proven, surrogate valid, largest density ratio
+ * (1 where the rows are not scaled), relative variance <d^2> / <d>^2 - 1 of matL's diagonal per component (kind 5 only; the
+ * other kinds do not sum d^2)}.  abar (or NULL): double[3][XPIC_LSTENCIL + 1], matM + <matL> in xpic_lstencil_decode's
+ * order, all taps (slot XPIC_LSTENCIL: <d^2>).  rscale (or NULL): the density ratios of the rows, widened to double, in
+ * xpic_field_get's layout over the local slab; meaningful only where info[4] is set. */
+#define XPIC_PRECOND_NINFO 11
+int xpic_precond_apply(xpic_ctx* ctx, int op, int r, int out);
+int xpic_precond_get(xpic_ctx* ctx, double* info, double* abar, double* rscale);
 /* The mass-matrix assembly (fill_ecsim_current) has two bodies: kind 0 (default) the classic 4-wave kernel (all grids);
  * kind 1 the warp-specialised kernel (one 16-wave workgroup per CU: a producer wave per SIMD runs the per-particle algebra,
  * two consumer waves the matrix-core accumulation, a flusher the window's read-modify-write), available where nx is a

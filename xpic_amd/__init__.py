@@ -28,7 +28,7 @@ SYMBOLS = [
     "xpic_matL_apply", "xpic_matA_apply", "xpic_matL_get", "xpic_lstencil_decode", "xpic_ecsim_first_push",
     "xpic_update_cells", "xpic_ecsim_fill_current", "xpic_ecsim_second_push", "xpic_basic_push",
     "xpic_ecsimcorr_first_push", "xpic_ecsimcorr_second_push", "xpic_ecsimcorr_final_update",
-    "xpic_calculate_energy", "xpic_ecsimcorr_scalars", "xpic_solve", "xpic_set_tolerances", "xpic_set_preconditioner", "xpic_set_overlap", "xpic_comm_stats", "xpic_set_fill_kernel", "xpic_set_fused_rebin", "xpic_get_fill_variant", "xpic_debug_set", "xpic_step",
+    "xpic_calculate_energy", "xpic_ecsimcorr_scalars", "xpic_solve", "xpic_set_tolerances", "xpic_set_preconditioner", "xpic_precond_apply", "xpic_precond_get", "xpic_set_overlap", "xpic_comm_stats", "xpic_set_fill_kernel", "xpic_set_fused_rebin", "xpic_get_fill_variant", "xpic_debug_set", "xpic_step",
     "xpic_energy", "xpic_momentum", "xpic_charge_density", "xpic_moment_density", "xpic_moment", "xpic_velocity_distribution", "xpic_remove_particles", "xpic_fields_damping",
     "xpic_inject_particles", "xpic_set_coils_field", "xpic_set_mirror_field", "xpic_cell_traversal", "xpic_implicit_esirkepov_interpolate",
     "xpic_implicit_esirkepov_decompose", "xpic_drift_kinetic_interpolate", "xpic_drift_kinetic_push",
@@ -531,6 +531,18 @@ class Context:
 
     def set_preconditioner(self, kind, degree=0):
         self._ck(self.L.xpic_set_preconditioner(self.h, int(kind), int(degree)))
+
+    def precond_apply(self, op, r, out):
+        """out = P r as the next solve(op, ...) would apply its preconditioner to a Krylov vector (test hook)"""
+        self._ck(self.L.xpic_precond_apply(self.h, int(op), int(r), int(out)))
+
+    def precond_get(self):
+        """the surrogate of kinds 3 - 5 as its last build left it (test hook; include/xpic_hip.h: xpic_precond_get):
+        dict of the interval, bounds, degree, flags, `abar` [3][124] and `rscale` in get_field's layout"""
+        info, abar, rs = np.zeros(11), np.zeros((3, LSTENCIL + 1)), np.zeros(self.fshape())
+        self._ck(self.L.xpic_precond_get(self.h, _dp(info), _dp(abar), _dp(rs)))
+        return dict(lo=info[0], hi=info[1], gershgorin=info[2], degree=int(info[3]), scaled=bool(info[4]), proven=bool(info[5]),
+                    valid=bool(info[6]), rmax=info[7], spread=info[8:11].copy(), abar=abar, rscale=rs)
 
     def comm_stats(self, reset=False):
         """(messages sent, bytes sent, all-reduces, all-reduce payload bytes) of this rank since the last reset"""

@@ -727,6 +727,39 @@ int xpic_set_preconditioner(xpic_ctx* ctx, int kind, int degree)
   return ensure_flexible_workspace(ctx);
 }
 
+int xpic_precond_apply(xpic_ctx* ctx, int op, int r, int out)
+{
+  CTX_CHECK(ctx); FIELD_CHECK(r); FIELD_CHECK(out);
+  XPIC_CHECK(ctx->kry_V, "scheme has no Krylov workspace");
+  XPIC_CHECK(r != out, "r and out must differ");
+  return precond_apply(ctx, op, ctx->field[r], ctx->field[out]);
+}
+
+int xpic_precond_get(xpic_ctx* ctx, double* info, double* abar, double* rscale)
+{
+  CTX_CHECK(ctx);
+  XPIC_CHECK(info, "null argument");
+  const bool built = ctx->precond >= 3 && ctx->abar_valid;
+  info[0] = ctx->abar_lo; info[1] = ctx->abar_hi; info[2] = ctx->abar_gershgorin;
+  info[3] = ctx->precond == 0 ? 0 : (built ? cheb_abar_degree(ctx) : ctx->cheb_degree);
+  info[4] = ctx->abar_scaled; info[5] = ctx->abar_proven; info[6] = ctx->abar_valid;
+  info[7] = ctx->abar_rmax;
+  for (int a = 0; a < 3; ++a) info[8 + a] = ctx->abar_spread[a];
+  if (!abar && !rscale) return 0;
+  XPIC_CHECK(ctx->abar_work && ctx->abar_r, "no surrogate was built (kinds 3 - 5)");
+  if (abar)
+    XPIC_HIP(hipMemcpyAsync(abar, ctx->abar_work + 6 * kLPad, sizeof(double) * 3 * kLPad, hipMemcpyDeviceToHost, ctx->stream));
+  std::vector<float> rs(rscale ? ctx->nvec : 0);
+  if (rscale) XPIC_HIP(hipMemcpyAsync(rs.data(), ctx->abar_r, sizeof(float) * ctx->nvec, hipMemcpyDeviceToHost, ctx->stream));
+  XPIC_HIP(hipStreamSynchronize(ctx->stream));
+  if (rscale) {
+    const GridDev& g = ctx->g;
+    for (int c1 = 0; c1 < 3; ++c1)
+      for (long i = 0; i < g.nown; ++i) rscale[i * 3 + c1] = (double)rs[c1 * g.cstride + (long)g.G * g.plane + i];
+  }
+  return 0;
+}
+
 int xpic_set_fused_rebin(xpic_ctx* ctx, int on)
 {
   CTX_CHECK(ctx);

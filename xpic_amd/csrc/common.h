@@ -240,6 +240,8 @@ struct xpic_ctx {
   bool abar_proven = false;        // its Gershgorin bound proves the polynomial's interval; otherwise the surrogate runs on probation
   double debug_surrogate_scale = 1.0; // xpic_debug_set(XPIC_DEBUG_SURROGATE_SCALE): <matL> times this in the surrogate (tests)
   bool abar_scaled = false;        // this solve's surrogate has its rows scaled by the local density (kind 4; kind 5 where it pays)
+  double abar_rmax = 1.0;          // largest density ratio of the last build (1 where the rows are not scaled)
+  double abar_spread[3] = {0, 0, 0}; // relative variance of matL's diagonal per component (k_abar_bounds; kind 5 sums it)
   double* red_partial = nullptr; // reduction partials
   double* red_out = nullptr;     // device results (pinned mirror below)
   double* red_host = nullptr;
@@ -324,6 +326,7 @@ int halo_fill_f32(xpic_ctx* c, float* f, int width);
 int abar_alloc(xpic_ctx* c);                                      // kind 3's buffers (with the context, not inside a solve)
 int abar_update(xpic_ctx* c);                                     // Abar = matM + <matL> from the assembled matL
 int cheb_abar_inverse(xpic_ctx* c, const double* r, double* out); // out ~ Abar^-1 r
+int cheb_abar_degree(const xpic_ctx* c);                          // steps of that iteration (user's, or from the interval)
 int cg_apply_dot_host(xpic_ctx* c, const double* p, double* Ap, double* pAp);                       // Ap = matM p, p . Ap
 int cg_update_host(xpic_ctx* c, double alpha, const double* p, const double* Ap, double* x, double* r, double* rr);
 int div_neg_add(xpic_ctx* c, double* v3, double* out_scalar);
@@ -402,5 +405,6 @@ int peer_order(xpic_ctx* c); // an exchange is about to be issued: order it behi
 // krylov.hip
 int solve(xpic_ctx* c, int op, const double* rhs, double* x, double rtol, double atol, int maxit, int* its,
   int* reason, double* rnorm);
+int precond_apply(xpic_ctx* c, int op, double* r, double* out); // out = P r as the next solve on `op` applies it (test hook)
 
 }  // namespace xpic

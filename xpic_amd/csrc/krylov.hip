@@ -22,6 +22,25 @@ int apply_op(xpic_ctx* c, int op, double* x, double* y)
   return matM_apply(c, x, y, false);
 }
 
+// z = P v: the polynomial in matM + <matL> (abar) or the one in matM, at the degree of the solve on `op`
+int precond_vector(xpic_ctx* c, int op, bool abar, const double* v, double* z)
+{
+  if (abar) return cheb_abar_inverse(c, v, z);
+  return cheb_matM_inverse(c, v, z, op == XPIC_OP_MATM_GMRES ? c->cheb_degree_M : c->cheb_degree);
+}
+
+// which of the two a solve on `op` starts with: kinds 3 - 5 rebuild their surrogate from the matL the solve runs on
+int precond_choose(xpic_ctx* c, int op, bool* abar)
+{
+  *abar = c->precond >= 3 && op == XPIC_OP_MATA_GMRES;
+  if (*abar) {
+    XPIC_CALL(abar_update(c));
+    // (sums that are not finite: nothing to build a surrogate from)
+    if (!c->abar_valid) { *abar = false; if (c->profiling) c->prof["precond_fallback"].launches += 1; }
+  }
+  return 0;
+}
+
 // Right-preconditioned restarted GMRES in its flexible form: z_j = P v_j is kept (kry_Z), the Arnoldi relation is
 // A Z = V H and x = x0 + Z y.  The recurrence residual is the TRUE residual |b - A x|, so the stopping rule is the
 // same with and without P -- and, the z_j being whatever P returned, it stays so when P is applied in reduced
@@ -39,12 +58,8 @@ int gmres(xpic_ctx* c, int op, const double* b, double* x, double rtol, double a
   XPIC_CHECK(!pc || c->kry_Z, "flexible GMRES workspace missing (xpic_set_preconditioner allocates it)");
   // kinds 3, 4: the predict solve's polynomial is in matM + <matL> (4: rows scaled by the local density), rebuilt from the
   // matL this solve runs on
-  bool pc_abar = pc && c->precond >= 3 && op == XPIC_OP_MATA_GMRES;
-  if (pc_abar) {
-    XPIC_CALL(abar_update(c));
-    // (sums that are not finite: nothing to build a surrogate from)
-    if (!c->abar_valid) { pc_abar = false; if (c->profiling) c->prof["precond_fallback"].launches += 1; }
-  }
+  bool pc_abar = false;
+  if (pc) XPIC_CALL(precond_choose(c, op, &pc_abar));
   // A surrogate whose spectral interval is not proven (precond.hip: abar_proven) runs on PROBATION: every iteration must at
   // least halve the residual (a sound one divides it by 70 - 200; the matM polynomial it would fall back to by 1.5) and
   // return finite numbers, or the solve continues with the matM polynomial -- the GMRES is flexible, its preconditioner may
@@ -84,8 +99,7 @@ int gmres(xpic_ctx* c, int op, const double* b, double* x, double rtol, double a
       double* Vj = V + (long)j * c->nvec;
       if (pc) {
         double* Zj = Z + (long)j * c->nvec;
-        if (pc_abar) XPIC_CALL(cheb_abar_inverse(c, Vj, Zj));
-        else XPIC_CALL(cheb_matM_inverse(c, Vj, Zj, op == XPIC_OP_MATM_GMRES ? c->cheb_degree_M : c->cheb_degree));
+        XPIC_CALL(precond_vector(c, op, pc_abar, Vj, Zj));
         XPIC_CALL(apply_op(c, op, Zj, w));
       }
       else XPIC_CALL(apply_op(c, op, Vj, w));
@@ -211,6 +225,15 @@ int cg(xpic_ctx* c, int op, const double* b, double* x, double rtol, double atol
 }
 
 }  // namespace
+
+int precond_apply(xpic_ctx* c, int op, double* r, double* out)
+{
+  XPIC_CHECK((op == XPIC_OP_MATA_GMRES || op == XPIC_OP_MATM_GMRES) && c->precond != 0, "no preconditioner is applied to this solve");
+  XPIC_CHECK(c->kry_Z, "flexible GMRES workspace missing (xpic_set_preconditioner allocates it)");
+  bool abar = false;
+  XPIC_CALL(precond_choose(c, op, &abar));
+  return precond_vector(c, op, abar, r, out);
+}
 
 int solve(xpic_ctx* c, int op, const double* rhs, double* x, double rtol, double atol, int maxit, int* its,
   int* reason, double* rnorm)

@@ -84,12 +84,12 @@ void matM_stencil(const GridDev& g, double* co /* [3][kLPad] */)
 
 // ---- translation average of matL over a sample of its rows ------------------------------------------------------
 // stage 1: one workgroup per sampled row block (c1, zp, y): sums the row's x-blocks; thread t = k * 4 + x % 4
-__global__ void __launch_bounds__(512) k_lbar_rows(GridDev g, const double* __restrict__ matL, int sy, int sz, int nys,
+__global__ void __launch_bounds__(512) k_lbar_rows(GridDev g, const double* __restrict__ matL, int sy, int sz, int nys, int zf,
   double* __restrict__ partial)
 {
   const int t = threadIdx.x;
   const int row = blockIdx.x, c1 = blockIdx.y;
-  const int y = (row % nys) * sy, z = (row / nys) * sz;
+  const int y = (row % nys) * sy, z = zf + (row / nys) * sz;
   if (t >= kLBlock) return;
   const double* base = matL + g.lindex(c1, z + (g.G ? 1 : 0), y, 0, 0) + t;
   double s = 0.0;
@@ -127,11 +127,11 @@ __global__ void __launch_bounds__(512) k_lbar_final(const double* __restrict__ s
 // surrogate): one workgroup per sampled row and component sums d^2 along x in a fixed order; k_diag2_final adds the rows'
 // values, again in a fixed order, into the free slot 123 of `sums` (kLPad = 124), so that it is averaged, all-reduced on
 // slabs and copied into abar64 with the coefficients.
-__global__ void __launch_bounds__(256) k_diag2_rows(GridDev g, const double* __restrict__ matL, int sy, int sz, int nys,
+__global__ void __launch_bounds__(256) k_diag2_rows(GridDev g, const double* __restrict__ matL, int sy, int sz, int nys, int zf,
   double* __restrict__ part2)
 {
   const int row = blockIdx.x, c1 = blockIdx.y;
-  const int y = (row % nys) * sy, z = (row / nys) * sz;
+  const int y = (row % nys) * sy, z = zf + (row / nys) * sz;
   const int kd = lencode(c1, c1, 0, 0, 0);
   double s = 0.0;
   for (int x = threadIdx.x; x < g.nx; x += 256) {
@@ -546,13 +546,16 @@ int halo_fill_f32(xpic_ctx* c, float* f, int width);
 namespace {
 
 // rows of the translation average: every 4th row in y and z of extents that have 16, every 8th of extents that have 64
-// (256^3: 3 x 262 144 rows x 256 nodes, the average's own noise 1e-4 of an entry; the pass reads 0.8 GB instead of 3.1)
-inline void lbar_rows(const GridDev& g, int* sy, int* sz, int* nys, int* nrows)
+// (256^3: 3 x 262 144 rows x 256 nodes, the average's own noise 1e-4 of an entry; the pass reads 0.8 GB instead of 3.1).
+// The extents are the BOX's and the sampled planes are those whose global index is a multiple of the stride: a box cut
+// into z-slabs averages the rows the whole box averages (*zf: the slab's first sampled plane; a thin slab may hold none).
+inline void lbar_rows(const GridDev& g, int* sy, int* sz, int* nys, int* zf, int* nrows)
 {
   *sy = g.ny >= 64 ? 8 : (g.ny >= 16 ? 4 : 1);
-  *sz = g.nzl >= 64 ? 8 : (g.nzl >= 16 ? 4 : 1);
+  *sz = g.nzg >= 64 ? 8 : (g.nzg >= 16 ? 4 : 1);
   *nys = (g.ny + *sy - 1) / *sy;
-  *nrows = *nys * ((g.nzl + *sz - 1) / *sz);
+  *zf = (*sz - g.z0 % *sz) % *sz;
+  *nrows = *zf < g.nzl ? *nys * ((g.nzl - *zf + *sz - 1) / *sz) : 0;
 }
 
 // bounds of Lbar = Abar - matM per row component c1 (one wave each): out[c1] = sum_k |Lbar[c1][k]| (widens the top of the
@@ -586,8 +589,8 @@ int abar_alloc(xpic_ctx* c)
 {
   if (c->abar32) return 0;
   const GridDev& g = c->g;
-  int sy, sz, nys, nrows;
-  lbar_rows(g, &sy, &sz, &nys, &nrows);
+  int sy, sz, nys, zf, nrows;
+  lbar_rows(g, &sy, &sz, &nys, &zf, &nrows);
   const size_t ntab = (size_t)kLinesUsed * kCoefPitch + (size_t)kMLinesUsed * kMPitch; // full table, then matM's own taps
   XPIC_HIP(hipMalloc(&c->abar32, sizeof(float) * ntab));
   XPIC_HIP(hipMemsetAsync(c->abar32, 0, sizeof(float) * ntab, c->stream));
@@ -615,24 +618,24 @@ int abar_update(xpic_ctx* c)
   const GridDev& g = c->g;
   Timed t(c, "precond_setup");
   XPIC_CHECK(c->abar32 && c->abar_work, "kind-3 preconditioner workspace missing (xpic_set_preconditioner allocates it)");
-  int sy, sz, nys, nrows;
-  lbar_rows(g, &sy, &sz, &nys, &nrows);
+  int sy, sz, nys, zf, nrows;
+  lbar_rows(g, &sy, &sz, &nys, &zf, &nrows);
   double* sums = c->abar_work;                  // [3][kLPad]
   double* mco = c->abar_work + 3 * kLPad;       // matM's coefficients
   double* abar64 = c->abar_work + 6 * kLPad;
   double* partial = c->abar_work + 9 * kLPad;
-  hipLaunchKernelGGL(k_lbar_rows, dim3(nrows, 3), dim3(512), 0, c->stream, g, c->matL, sy, sz, nys, partial);
+  if (nrows > 0) hipLaunchKernelGGL(k_lbar_rows, dim3(nrows, 3), dim3(512), 0, c->stream, g, c->matL, sy, sz, nys, zf, partial);
   double* segsum = partial + (size_t)nrows * 3 * kLBlock;
   hipLaunchKernelGGL(k_lbar_segments, dim3(3, kSegs), dim3(512), 0, c->stream, partial, nrows, segsum);
   hipLaunchKernelGGL(k_lbar_final, dim3(3), dim3(512), 0, c->stream, segsum, sums);
   if (c->precond == 5) { // (behind k_lbar_final, which writes all 124 slots of a component)
     double* part2 = segsum + (size_t)kSegs * 3 * kLBlock;
-    hipLaunchKernelGGL(k_diag2_rows, dim3(nrows, 3), dim3(256), 0, c->stream, g, c->matL, sy, sz, nys, part2);
+    if (nrows > 0) hipLaunchKernelGGL(k_diag2_rows, dim3(nrows, 3), dim3(256), 0, c->stream, g, c->matL, sy, sz, nys, zf, part2);
     hipLaunchKernelGGL(k_diag2_final, dim3(3), dim3(256), 0, c->stream, part2, nrows, sums);
   }
   XPIC_HIP(hipGetLastError());
   XPIC_CALL(comm_allreduce_sum(c, sums, 3 * kLPad)); // the same surrogate on every slab
-  const double count = (double)nrows * g.nx * c->comm.nranks;
+  const double count = (double)nys * ((g.nzg + sz - 1) / sz) * g.nx; // sampled nodes of the whole box
   hipLaunchKernelGGL(k_abar, dim3(2), dim3(256), 0, c->stream, sums, mco, 1.0 / count, c->abar32, abar64, c->debug_surrogate_scale);
   double* bounds = c->red_out + 64; // [64, 74): behind the reductions' and the host all-reduce's slots
   hipLaunchKernelGGL(k_abar_bounds, dim3(3), dim3(64), 0, c->stream, abar64, mco, bounds);
@@ -684,6 +687,8 @@ int abar_update(xpic_ctx* c)
   // alike (the residual norms are all-reduced).
   const double rs = std::max(hb[0], std::max(hb[1], hb[2]));
   const double gl = std::min(hb[3], std::min(hb[4], hb[5]));
+  c->abar_rmax = rmax;
+  for (int a = 0; a < 3; ++a) c->abar_spread[a] = hb[7 + a];
   c->abar_lo = 2.0;
   c->abar_hi = 2.0 + 2.0 * g.dt * g.dt * (1.0 / (g.dx * g.dx) + 1.0 / (g.dy * g.dy) + 1.0 / (g.dz * g.dz)) + rmax * rs;
   c->abar_gershgorin = 2.0 + gl;
@@ -691,6 +696,16 @@ int abar_update(xpic_ctx* c)
   c->abar_proven = c->abar_valid && 2.0 + rmax * std::min(gl, 0.0) > 0.0;
   if (c->debug_surrogate_scale != 1.0) c->abar_proven = false; // (test hook: the surrogate below is deliberately wrong)
   return 0;
+}
+
+// error bound 2 rho^k / (1 + rho^2k) <= 2.5 % (what is left for GMRES is the 2 % noise of matL around its average);
+// kind 4 leaves 0.8 % and needs the polynomial at 0.25 % to keep its third iteration below the tolerance (degree 12
+// instead of 8 at dt = 1, h = 0.5: tools/precond_spectrum.py)
+int cheb_abar_degree(const xpic_ctx* c)
+{
+  const double kappa = c->abar_hi / c->abar_lo, rh = (std::sqrt(kappa) - 1.0) / (std::sqrt(kappa) + 1.0);
+  int degree = c->cheb_degree_user > 0 ? c->cheb_degree_user : (int)std::ceil(std::log(c->abar_scaled ? 0.00125 : 0.0125) / std::log(rh));
+  return degree < 2 ? 2 : (degree > 64 ? 64 : degree);
 }
 
 // out ~ Abar^-1 r: `degree` steps of the Chebyshev iteration on [abar_lo, abar_hi]
@@ -701,13 +716,8 @@ int cheb_abar_inverse(xpic_ctx* c, const double* r, double* out)
   XPIC_CHECK(c->abar_valid, "the matL surrogate of the preconditioner was not built (abar_update)");
   const double a = c->abar_lo, b = c->abar_hi;
   const double theta = 0.5 * (b + a), delta = 0.5 * (b - a), sigma1 = theta / delta;
-  // error bound 2 rho^k / (1 + rho^2k) <= 2.5 % (what is left for GMRES is the 2 % noise of matL around its average);
-  // kind 4 leaves 0.8 % and needs the polynomial at 0.25 % to keep its third iteration below the tolerance (degree 12
-  // instead of 8 at dt = 1, h = 0.5: tools/precond_spectrum.py)
   const bool scaled = c->abar_scaled;
-  const double kappa = b / a, rh = (std::sqrt(kappa) - 1.0) / (std::sqrt(kappa) + 1.0);
-  int degree = c->cheb_degree_user > 0 ? c->cheb_degree_user : (int)std::ceil(std::log(scaled ? 0.00125 : 0.0125) / std::log(rh));
-  degree = degree < 2 ? 2 : (degree > 64 ? 64 : degree);
+  const int degree = cheb_abar_degree(c);
   if (c->profiling) c->prof["cheb_steps"].launches += degree - 1; // stencil steps of the polynomial (bench.py: per outer iteration)
   float* d = (float*)c->kry_p[0];
   float* z0 = (float*)c->kry_p[1];
