@@ -302,6 +302,45 @@ def test_argument_checks(X, ctx, particles):
         two.full_orbit_push(p0[:4], "EB2B", R.QM, R.DT)
 
 
+def test_closed_traces_at_the_edges_through_the_c_abi(X, ctx, particles):
+    """What the Python wrappers cannot show, because they always pass fresh zeros: the closed entry points write zeros
+    into counters that came prefilled, with zero steps (every pusher) and for a Chin id, which has no iterations; zero
+    steps leave the state's bytes alone; and the grid's open trace still refuses XPIC_GEOM_NONE, which only the model
+    traces take, although one function now checks the region for both."""
+    import ctypes as C
+
+    L_, n = ctx.L, 3
+    dp, i64, i32 = C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_int)
+    p0 = np.ascontiguousarray(particles[:n])
+    fo = {sid: X.FoParams(R.QM, R.DT, 1e-7, 1e-7, X.FO_SCHEMES[sid], 30) for sid in ("EB2B", "M1A", "CN")}
+    dk = X.DkParams(R.QM, 1.0, R.DT, 1e-12, 1e-12, 30)
+
+    def call(fn, params, steps, *middle):
+        state, tot, mx = p0.copy(), np.full(n, 7, dtype=np.int64), np.full(n, 7, dtype=np.int32)
+        rc = fn(ctx.h, C.c_int64(n), C.byref(params), *middle, C.c_int64(steps), C.c_int64(0), state.ctypes.data_as(dp), None,
+                tot.ctypes.data_as(i64), mx.ctypes.data_as(i32))
+        assert rc == 0, L_.xpic_last_error().decode()
+        return state, tot, mx
+
+    for fn, params, middle in ((L_.xpic_full_orbit_trace, fo["EB2B"], ()), (L_.xpic_full_orbit_trace, fo["CN"], ()),
+                               (L_.xpic_drift_kinetic_trace, dk, (C.c_int(-1),))):
+        state, tot, mx = call(fn, params, 0, *middle)
+        assert state.tobytes() == p0.tobytes()
+        assert not tot.any() and not mx.any()
+    for sid in ("EB2B", "M1A"):
+        state, tot, mx = call(L_.xpic_full_orbit_trace, fo[sid], 65)
+        assert np.isfinite(state).all() and state.tobytes() != p0.tobytes()
+        assert not tot.any() and not mx.any()
+    reg = X.TraceRegion(X.GEOM_NONE, 1, (C.c_double * 7)(), 0)
+    state, ex, tot, mx = p0.copy(), np.full(n, -1, dtype=np.int64), np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int32)
+    removed = C.c_int64(0)
+    assert L_.xpic_full_orbit_trace_open(ctx.h, C.c_int64(n), C.byref(fo["EB2B"]), C.c_int64(2), C.c_int64(0),
+                                         state.ctypes.data_as(dp), None, tot.ctypes.data_as(i64), mx.ctypes.data_as(i32),
+                                         C.byref(reg), ex.ctypes.data_as(i64), None, C.byref(removed)) != 0
+    assert "geometry" in L_.xpic_last_error().decode()
+    assert state.tobytes() == p0.tobytes()
+
+
 def _pair(X, orbit_centre):
     """B = (0, 0, 1), E = (0, 0.01, 0), qm = -1, 200 steps of dt = 0.1: 64 EB2B orbits beside the drift-kinetic trace from
     guiding_centre(..., orbit_centre=orbit_centre) of the same initial points -> the largest and smallest distance, in

@@ -7,7 +7,8 @@ just inside the two field maxima.  Whoever is in the loss cone leaves through an
 
 Reports the lost fraction against the step, and kernel time (the context's profile sections "fo_trace", "fo_trace_open",
 "fo_trace_open_compact"; staging and copies are not counted) per launch of at most 64 steps for
-  closed          xpic_full_orbit_trace of the same batch (this kernel is the one the open trace was added beside)
+  closed          xpic_full_orbit_trace of the same batch (k_fo_trace, the closed text beside k_fo_trace_open: both run on
+                  the one trace driver, batch.h's batch_trace, which reads nothing back between a closed trace's launches)
   open_everywhere the open trace with a region nobody leaves: the cost of the test
   lossy_auto / lossy_never / lossy_always   the trap's region with compact = 0, 1, 2
 with each open case's ratio to `closed`, and checks on the way that the three policies return the same bits.  Prints one
@@ -97,7 +98,8 @@ def main():
     # one run on one box: the pool's box-to-box spread (measured on the assembly) is what a ratio
     # between two cases of this file can be trusted to
     res["box_to_box_spread_quoted"] = 0.04
-    res["closed_is"] = "xpic_full_orbit_trace of this build, same run and box; k_fo_trace is the kernel the open trace was added beside, unchanged"
+    res["closed_is"] = ("xpic_full_orbit_trace of this build, same run and box; k_fo_trace is the closed text that stays beside "
+                        "k_fo_trace_open (DESIGN.md 5q), on the trace driver both share")
     a = outs["auto"]
     res["lost_fraction"] = float(a.removed) / npart
     res["lost_fraction_by_step"] = [[int((k + 1) * X.FO_LAUNCH_STEPS), 1.0 - float(v) / npart] for k, v in enumerate(a.alive)]

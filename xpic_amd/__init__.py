@@ -721,11 +721,8 @@ class Context:
     def drift_kinetic_trace(self, state, steps, qm, mp, dt, gradB_field=None, sample_every=0, eps=1e-12, delta=1e-12, maxit=30):
         """`steps` pushes with the particles kept on the device -> (state, samples [steps // sample_every][n][6] or None,
         iterations_total, iterations_max)"""
-        state = np.array(state, dtype=np.float64).reshape(-1, 6)  # a copy: the call works in place
+        state, samples, _, _, _, tot, mx = self._open_args(state, steps, sample_every, None, None, 0, "never", True)
         n = state.shape[0]
-        nsamp = int(steps) // int(sample_every) if sample_every else 0
-        samples = np.zeros((nsamp, n, 6)) if sample_every else None
-        tot, mx = np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int32)
         P = self._dk_params(qm, mp, dt, eps, delta, maxit)
         self._ck(self.L.xpic_drift_kinetic_trace(self.h, C.c_int64(n), C.byref(P), -1 if gradB_field is None else int(gradB_field),
                                                  C.c_int64(int(steps)), C.c_int64(int(sample_every)), _dp(state),
@@ -753,11 +750,8 @@ class Context:
     def full_orbit_trace(self, state, steps, scheme, qm, dt, sample_every=0, atol=1e-7, rtol=1e-7, maxit=30):
         """`steps` pushes with the particles kept on the device -> (state, samples [steps // sample_every][n][6] or None,
         iterations_sum, iterations_max); sample k is the state after step (k + 1) * sample_every"""
-        state = np.array(state, dtype=np.float64).reshape(-1, 6)  # a copy: the call works in place
+        state, samples, _, _, _, tot, mx = self._open_args(state, steps, sample_every, None, None, 0, "never", True)
         n = state.shape[0]
-        nsamp = max(int(steps), 0) // int(sample_every) if sample_every else 0
-        samples = np.zeros((nsamp, n, 6)) if sample_every else None
-        tot, mx = np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int32)
         P = self._fo_params(scheme, qm, dt, atol, rtol, maxit)
         self._ck(self.L.xpic_full_orbit_trace(self.h, C.c_int64(n), C.byref(P), C.c_int64(int(steps)),
                                               C.c_int64(int(sample_every)), _dp(state), _dp(samples) if sample_every else None,
@@ -769,7 +763,8 @@ class Context:
     # (None: everybody alive), step0: the steps that call and its predecessors made; compact: a key of COMPACT or its number
     # ("never" by default: at 2^20 particles rebuilding the list gained 1.5 - 3.4 %, inside the +- 4 % box-to-box spread --
     # DESIGN.md 5j, "Measured")
-    # keep_samples=False: alive only, no sample rows (samples is None)
+    # keep_samples=False: alive only, no sample rows (samples is None).  _open_args builds the arrays of every trace of one
+    # batch; region None: no region (XPIC_GEOM_NONE, which only the model traces take; the closed traces pass no region)
     def _open_args(self, state, steps, sample_every, region, exit_step, step0, compact, keep_samples):
         state = np.array(state, dtype=np.float64).reshape(-1, 6)  # a copy: the call works in place
         n = state.shape[0]
@@ -777,7 +772,7 @@ class Context:
         samples = np.zeros((nsamp, n, 6)) if sample_every and keep_samples else None
         alive = np.zeros(nsamp, dtype=np.int64) if sample_every else None
         ex = np.full(n, -1, dtype=np.int64) if exit_step is None else np.array(exit_step, dtype=np.int64).reshape(n)
-        kind, gp = _geom7(region)
+        kind, gp = (GEOM_NONE, [0.0] * 7) if region is None else _geom7(region)
         reg = TraceRegion(kind, int(COMPACT.get(compact, compact)), (C.c_double * 7)(*gp[:7]), int(step0))
         return state, samples, alive, ex, reg, np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int32)
 
@@ -862,25 +857,14 @@ class Context:
         ids = [-1 if f is None else int(f) for f in (E_field, B_field, gradB_field)]
         self._ck(self.L.xpic_set_model_field(self.h, None if model is None else C.byref(model), *ids))
 
-    def _model_args(self, state, steps, sample_every, region, exit_step, step0, keep_samples):
-        if region is None:
-            state, samples, alive, ex, reg, tot, mx = self._open_args(
-                state, steps, sample_every, {"name": "box", "min": (0, 0, 0), "max": (0, 0, 0)}, exit_step, step0, "never",
-                keep_samples)
-            reg.geometry = GEOM_NONE
-        else:
-            state, samples, alive, ex, reg, tot, mx = self._open_args(state, steps, sample_every, region, exit_step, step0,
-                                                                          "never", keep_samples)
-        return state, samples, alive, ex, reg, tot, mx
-
     _ABSENT = object()  # _model_trace: the library function has no such argument
 
     def _model_trace(self, fn, P, state, steps, model, region, sample_every, exit_step, step0, keep_samples,
                      envelope=_ABSENT, sums=_ABSENT):
         """the ctypes call of the four model traces -> the fields of TimedTrace (OpenTrace's and sums).  envelope follows
         model and sums ends the argument list where fn has them; sums as model_full_orbit_trace_timed takes it"""
-        state, samples, alive, ex, reg, tot, mx = self._model_args(state, steps, sample_every, region, exit_step, step0,
-                                                                       keep_samples)
+        state, samples, alive, ex, reg, tot, mx = self._open_args(state, steps, sample_every, region, exit_step, step0,
+                                                                      "never", keep_samples)
         n = state.shape[0]
         absent = self._ABSENT
         if sums is not absent and sums is not None:

@@ -1,8 +1,9 @@
 // batch.h -- the host side that the batch particle calls share (eccapfim.hip, drift_kinetic.hip, full_orbit.hip,
-// compare_trace.hip): host arrays of particles are staged on the device, a kernel runs one lane per particle, the results
-// are copied back.  batch_compare_trace is batch_trace for two or three batches advanced side by side (compare_trace.hip).
-// batch_trace_open is batch_trace for the open traces (trace_open.h, trace_open.hip): exit steps, alive counts, and the
-// list of live particles between launches.
+// model_trace.hip, compare_trace.hip): host arrays of particles are staged on the device, a kernel runs one lane per
+// particle, the results are copied back.  batch_trace is the one driver of every trace of one batch, closed or open
+// (trace_open.h, trace_open.hip: exit steps, alive counts, and the list of live particles between launches); the entry
+// points reach it through trace_call.h.  batch_compare_trace is the driver for two or three batches advanced side by side
+// (compare_trace.hip).
 // DevScratch also owns every other device buffer that lives for one call (fields.hip, particles.hip, commands.hip,
 // api.hip).  Host code only: no kernel or device function is declared here.
 #pragma once
@@ -44,7 +45,7 @@ inline int64_t trace_sample_bytes(int64_t n, int64_t steps, int64_t sample_every
   return fits ? bytes : -1;
 }
 
-// An open trace (batch_trace_open): whether the list of `listed` entries, `live` of them alive, is rebuilt before the next
+// An open trace (batch_trace): whether the list of `listed` entries, `live` of them alive, is rebuilt before the next
 // launch.  policy: enum xpic_trace_compact (0: when fewer than half are alive, 1: never, 2: whenever one is not).
 inline bool trace_compacts(int policy, int64_t live, int64_t listed)
 {
@@ -138,50 +139,7 @@ int batch_push(xpic_ctx* c, const char* label, int64_t n, bool counters, const d
   return 0;
 }
 
-// `steps` steps of n > 0 particles in place in state_6, the particles kept on the device; nsamp samples
-// (trace_sample_bytes) into samples[nsamp][n][6]; with `counters` the sum and the maximum of each particle's iteration
-// counts.  launch(s, first, nsteps, samples, it_sum, it_max) starts the kernel for steps first + 1 .. first + nsteps
-// (samples: null without samples; it_sum, it_max: null without counters); each launch is timed under `label`.
-template <class Launch>
-int batch_trace(xpic_ctx* c, const char* label, int launch_steps, int64_t n, int64_t steps, int64_t nsamp, bool counters,
-  double* state_6, double* samples, int64_t* it_sum, int* it_max, Launch launch)
-{
-  const size_t row = (size_t)6 * n; // doubles of one state
-  std::vector<double> h, hs;
-  to_soa(state_6, n, h);
-  DevScratch<double> s, sm;
-  DevScratch<int64_t> tot;
-  DevScratch<int> mx;
-  XPIC_CALL(s.alloc(row));
-  if (counters) {
-    XPIC_CALL(tot.alloc(n)); XPIC_CALL(mx.alloc(n));
-    XPIC_CALL(zero(tot, n, c->stream)); XPIC_CALL(zero(mx, n, c->stream));
-  }
-  if (nsamp > 0) XPIC_CALL(sm.alloc(row * nsamp));
-  XPIC_CALL(upload(s, h.data(), row, c->stream));
-  // one launch covers at most launch_steps steps, so no launch runs for seconds however long the trace
-  for (int64_t first = 0; first < steps; first += launch_steps) {
-    const int ns = (int)std::min<int64_t>(launch_steps, steps - first);
-    Timed t(c, label);
-    launch(s.p, (long)first, ns, sm.p, (long long*)tot.p, mx.p);
-    XPIC_HIP(hipGetLastError());
-  }
-  XPIC_CALL(download(h.data(), s, row, c->stream));
-  if (counters) {
-    XPIC_CALL(download(it_sum, tot, n, c->stream));
-    XPIC_CALL(download(it_max, mx, n, c->stream));
-  }
-  if (nsamp > 0) {
-    hs.resize(row * nsamp);
-    XPIC_CALL(download(hs.data(), sm, row * nsamp, c->stream)); // the samples, once
-  }
-  XPIC_HIP(hipStreamSynchronize(c->stream));
-  to_aos(h.data(), n, state_6);
-  for (int64_t k = 0; k < nsamp; ++k) to_aos(hs.data() + row * k, n, samples + row * k);
-  return 0;
-}
-
-// batch_trace for the members of a comparison trace, advanced side by side in one lane (compare_trace.hip; DESIGN.md 5k,
+// The trace driver for the members of a comparison trace, advanced side by side in one lane (compare_trace.hip; DESIGN.md 5k,
 // 5m, 5p).  A member is a host batch state_6 [n][6], in and out (null: the member is absent and nothing of it is staged),
 // with the sum and the maximum of its iteration counts when `counters` (zeroed here).
 struct CompareMember {
@@ -268,24 +226,31 @@ int batch_compare_trace(xpic_ctx* c, const char* label, int launch_steps, int64_
 int live_compact(xpic_ctx* c, const char* label, const int64_t* exit_step, const int64_t* list, int64_t m, int64_t cap,
   int64_t* out, double* blk, int64_t* off);
 
-// batch_trace with the region rule of an open trace (include/xpic_hip.h: xpic_trace_region).  exit_step
-// [n] in and out, alive [nsamp] or null, *removed as the entry points document them; nsamp counts the rows of samples
-// and of alive, either of which may be null.  launch(s, list, m, first, nsteps, samples, it_sum, it_max, exit_step,
-// alive, removed) starts the kernel for steps first + 1 .. first + nsteps over the m entries of list (null: the particles
-// 0 .. m - 1); the kernel adds to alive[row] and to *removed (device, zeroed here).  After every launch the count removed
-// so far comes back (8 bytes), so the host knows how many entries are alive: when none is, the remaining launches are
-// skipped, and by `policy` (trace_compacts) the list is rebuilt for the next launch, timed under `compact_label`.
-// The sample rows behind a removed particle's last step are filled here, on the host, from the final state
-// (fill_frozen_samples): a launch no longer covers a particle that compaction has dropped.
+// `steps` steps of n > 0 particles in place in state_6, the particles kept on the device, with the region rule of an open
+// trace (include/xpic_hip.h: xpic_trace_region) when the kernel applies one.  nsamp (trace_sample_bytes)
+// counts the rows of samples [nsamp][n][6] and of alive [nsamp], either of which may be null; with `counters` the sum and
+// the maximum of each particle's iteration counts.  exit_step [n] in and out and *removed as the open entry points
+// document them.  A closed trace passes a null exit_step (everybody enters alive: a stand-in of -1 is staged) and a null
+// removed (nothing can leave: see below).  launch(s, list, m, first, nsteps, samples, it_sum, it_max, exit_step, alive,
+// removed) starts the kernel for steps first + 1 .. first + nsteps over the m entries of list (null: the particles
+// 0 .. m - 1); samples, it_sum / it_max and alive are null where the call has none; the kernel adds to alive[row] and to
+// *removed (device, zeroed here); each launch is timed under `label`.  With `removed`, the count removed so far comes back
+// after every launch (8 bytes), so the host knows how many entries are alive: when none is, the remaining launches are
+// skipped, and by `policy` (trace_compacts) the list is rebuilt for the next launch, timed under `compact_label`.  Without
+// it nothing is read back and nothing synchronises between the launches.  The sample rows behind a removed particle's last
+// step are filled here, on the host, from the final state (fill_frozen_samples): a launch no longer covers a particle that
+// compaction has dropped.
 template <class Launch>
-int batch_trace_open(xpic_ctx* c, const char* label, const char* compact_label, int launch_steps, int64_t n, int64_t steps,
+int batch_trace(xpic_ctx* c, const char* label, const char* compact_label, int launch_steps, int64_t n, int64_t steps,
   int64_t sample_every, int64_t nsamp, bool counters, int policy, int64_t step0, double* state_6, double* samples,
   int64_t* it_sum, int* it_max, int64_t* exit_step, int64_t* alive, int64_t* removed, Launch launch)
 {
   const size_t row = (size_t)6 * n; // doubles of one state
   std::vector<double> h, hs;
   to_soa(state_6, n, h);
-  const std::vector<int64_t> exit_in(exit_step, exit_step + n);
+  std::vector<int64_t> exit_in(n, -1), exit_own(exit_step ? 0 : n); // the closed trace's stand-ins
+  if (exit_step) exit_in.assign(exit_step, exit_step + n);
+  else exit_step = exit_own.data();
   int64_t live = 0;
   for (int64_t q = 0; q < n; ++q) live += exit_in[q] < 0;
   DevScratch<double> s, sm, blk;
@@ -315,6 +280,7 @@ int batch_trace_open(xpic_ctx* c, const char* label, const char* compact_label, 
         (unsigned long long*)al.p, (unsigned long long*)rm.p);
       XPIC_HIP(hipGetLastError());
     }
+    if (!removed) continue;
     int64_t g = 0;
     XPIC_CALL(download(&g, rm, 1, c->stream));
     XPIC_HIP(hipStreamSynchronize(c->stream));
@@ -350,7 +316,7 @@ int batch_trace_open(xpic_ctx* c, const char* label, const char* compact_label, 
     for (int64_t k = 0; k < nsamp; ++k) to_aos(hs.data() + row * k, n, samples + row * k);
     fill_frozen_samples(n, nsamp, sample_every, step0, exit_in.data(), exit_step, state_6, samples);
   }
-  *removed = gone;
+  if (removed) *removed = gone;
   return 0;
 }
 

@@ -298,8 +298,8 @@ void compare_launch(xpic_ctx* ctx, const double* gradB, const xpic_field_model& 
       d.it_sum[0], d.it_max[0], d.it_sum[2], d.it_max[2]);
 }
 
-// The checks of fo_check (full_orbit.hip) and of dk_check / dk_check_params (drift_kinetic.hip) and what the comparison
-// adds; with a model member those of the model traces (model_trace.hip); the grid's only with the grid member.  `who`
+// The checks of fo_check (full_orbit.hip), of dk_check (drift_kinetic.hip) and of fo_check_params / dk_check_params
+// (trace_call.h), in this file's own wording, and what the comparison adds; with a model member those of the model traces (model_trace.hip); the grid's only with the grid member.  `who`
 // ("paired_trace", "triplet_trace") heads every message.
 int compare_check(xpic_ctx* ctx, const char* who, int64_t n, const xpic_fo_params* F, const xpic_dk_params* D,
   bool with_model, const xpic_field_model* model, bool with_grid, int gradB_field, const double** gradB)

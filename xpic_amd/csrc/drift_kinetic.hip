@@ -7,11 +7,13 @@
 // not folded into the box: the gathers wrap their node indices (ie_node), folding is the caller's business as
 // correct_coordinates is in the reference.  Single z-slab contexts only (G == 0: every index wraps, so no position,
 // however far out, reads outside a field vector).  The C entry points and their argument checks are at the end of the
-// file; the staging of the host records, the push and trace drivers and the sample buffer's size are batch.h's.
+// file; the staging of the host records, the push and trace drivers and the sample buffer's size are batch.h's, the
+// trace's checks and its call trace_call.h's.
 #include "batch.h"
 #include "common.h"
 #include "device_common.h"
 #include "ie_shape.h"
+#include "trace_call.h"
 #include "trace_open.h"
 
 // The pusher's own expressions are contracted per source expression only (not across statements), so k_dk_push and
@@ -82,7 +84,9 @@ __global__ void __launch_bounds__(kBlock) k_dk_trace(GridDev g, const double* __
 }
 
 // k_dk_trace with the region rule of an open trace (trace_open.h) over the m entries of `list` (null: the
-// particles 0 .. m - 1): as k_fo_trace_open, the step being dk_process as in k_dk_push and k_dk_trace.
+// particles 0 .. m - 1): as k_fo_trace_open, the step being dk_process as in k_dk_push and k_dk_trace.  The two traces
+// stay two texts: folded as k_model_dk_trace is, the closed trace measured 0.8 - 1.1 % slower, outside the margin
+// (DESIGN.md 5q).
 static_assert(XPIC_DK_LAUNCH_STEPS <= kOpenRows, "open_tally holds one row per step of a launch");
 template <bool GRAD>
 __global__ void __launch_bounds__(kBlock) k_dk_trace_open(GridDev g, const double* __restrict__ E,
@@ -135,12 +139,27 @@ int dk_check(xpic_ctx* ctx, int64_t n, int gradB_field, const double** gradB)
   return 0;
 }
 
-int dk_check_params(const xpic_dk_params* P)
+// both traces, after dk_check; region: null for the closed trace
+int dk_trace(xpic_ctx* ctx, const TraceEntry& E, const char* label, const char* compact_label, int64_t n,
+  const xpic_dk_params* params, const double* gradB, int64_t steps, int64_t sample_every, double* state_6, double* samples,
+  int64_t* iterations_total, int* iterations_max, const xpic_trace_region* region, int64_t* exit_step, int64_t* alive,
+  int64_t* removed)
 {
-  XPIC_CHECK(P, "drift_kinetic: params is null");
-  XPIC_CHECK(P->maxit >= 1, "drift_kinetic: maxit must be >= 1");
-  XPIC_CHECK(P->mp != 0.0, "drift_kinetic: mp must not be 0");
-  return 0;
+  XPIC_CALL(dk_check_params("drift_kinetic", params, 0));
+  OpenRegion R{XPIC_GEOM_NONE, {}, 0};
+  if (!E.closed) XPIC_CALL(trace_region(E.who, region, false, true, &R));
+  return trace_call(ctx, E, label, compact_label, XPIC_DK_LAUNCH_STEPS, n, true, steps, sample_every, state_6, samples,
+    iterations_total, iterations_max, R, E.closed ? XPIC_COMPACT_NEVER : region->compact, exit_step, alive, removed, nullptr,
+    [&](double* s, const long long* list, long m, long first, int ns, long nsamp, double* sm, long long* it_sum, int* it_max,
+      long long* ex, unsigned long long* al, unsigned long long* rm, double*) {
+      if (E.closed) // its text takes no region: the driver's stand-ins for exit_step and removed stay unused
+        hipLaunchKernelGGL(gradB ? k_dk_trace<true> : k_dk_trace<false>, lane_grid(n), dim3(kBlock), 0, ctx->stream, ctx->g,
+          ctx->field[XPIC_E], ctx->field[XPIC_B], gradB, *params, (long)n, s, first, ns, (long)sample_every, sm, it_sum, it_max);
+      else
+        hipLaunchKernelGGL(gradB ? k_dk_trace_open<true> : k_dk_trace_open<false>, lane_grid(m), dim3(kBlock), 0, ctx->stream,
+          ctx->g, ctx->field[XPIC_E], ctx->field[XPIC_B], gradB, *params, R, (long)n, s, list, m, first, ns, (long)sample_every,
+          nsamp, sm, it_sum, it_max, ex, al, rm);
+    });
 }
 
 }  // namespace
@@ -185,7 +204,7 @@ int xpic_drift_kinetic_push(xpic_ctx* ctx, int64_t n, const xpic_dk_params* para
 { // DriftKineticPush::process, drift_kinetic_push.cpp:48-108
   const double* gradB;
   XPIC_CALL(dk_check(ctx, n, gradB_field, &gradB));
-  XPIC_CALL(dk_check_params(params));
+  XPIC_CALL(dk_check_params("drift_kinetic", params, 0));
   XPIC_CHECK(p0_6, "drift_kinetic_push: p0_6 is null");
   XPIC_CHECK(pn_6, "drift_kinetic_push: pn_6 is null");
   XPIC_CHECK(iterations, "drift_kinetic_push: iterations is null");
@@ -201,21 +220,9 @@ int xpic_drift_kinetic_trace(xpic_ctx* ctx, int64_t n, const xpic_dk_params* par
 {
   const double* gradB;
   XPIC_CALL(dk_check(ctx, n, gradB_field, &gradB));
-  XPIC_CALL(dk_check_params(params));
-  XPIC_CHECK(steps >= 0, "drift_kinetic_trace: steps is negative");
-  XPIC_CHECK(!samples || sample_every >= 1, "drift_kinetic_trace: sample_every must be >= 1 when samples are asked for");
-  XPIC_CHECK(state_6, "drift_kinetic_trace: state_6 is null");
-  XPIC_CHECK(iterations_total, "drift_kinetic_trace: iterations_total is null");
-  XPIC_CHECK(iterations_max, "drift_kinetic_trace: iterations_max is null");
-  int64_t nsamp;
-  XPIC_CHECK(trace_sample_bytes(n, steps, sample_every, samples != nullptr, &nsamp) >= 0,
-    "drift_kinetic_trace: the sample buffer (48 n steps / sample_every bytes) is too large");
-  if (n == 0) return 0;
-  return batch_trace(ctx, "dk_trace", XPIC_DK_LAUNCH_STEPS, n, steps, nsamp, true, state_6, samples, iterations_total,
-    iterations_max, [&](double* s, long first, int ns, double* sm, long long* it_sum, int* it_max) {
-      hipLaunchKernelGGL(gradB ? k_dk_trace<true> : k_dk_trace<false>, lane_grid(n), dim3(kBlock), 0, ctx->stream, ctx->g,
-        ctx->field[XPIC_E], ctx->field[XPIC_B], gradB, *params, (long)n, s, first, ns, (long)sample_every, sm, it_sum, it_max);
-    });
+  return dk_trace(ctx, {"drift_kinetic_trace", "state_6", "iterations_total", "iterations_max", true}, "dk_trace", "dk_trace",
+    n, params, gradB, steps, sample_every, state_6, samples, iterations_total, iterations_max, nullptr, nullptr, nullptr,
+    nullptr);
 }
 
 int xpic_drift_kinetic_trace_open(xpic_ctx* ctx, int64_t n, const xpic_dk_params* params, int gradB_field, int64_t steps,
@@ -224,30 +231,9 @@ int xpic_drift_kinetic_trace_open(xpic_ctx* ctx, int64_t n, const xpic_dk_params
 { // xpic_drift_kinetic_trace with RemoveParticles::execute (remove_particles.cpp:22-38) at the top of every step
   const double* gradB;
   XPIC_CALL(dk_check(ctx, n, gradB_field, &gradB));
-  XPIC_CALL(dk_check_params(params));
-  OpenRegion R;
-  XPIC_CALL(open_region("drift_kinetic_trace_open", region, &R));
-  XPIC_CHECK(steps >= 0, "drift_kinetic_trace_open: steps is negative");
-  XPIC_CHECK((!samples && !alive) || sample_every >= 1,
-    "drift_kinetic_trace_open: sample_every must be >= 1 when samples or alive are asked for");
-  XPIC_CHECK(state_6, "drift_kinetic_trace_open: state_6 is null");
-  XPIC_CHECK(exit_step, "drift_kinetic_trace_open: exit_step is null");
-  XPIC_CHECK(removed, "drift_kinetic_trace_open: removed is null");
-  XPIC_CHECK(iterations_total, "drift_kinetic_trace_open: iterations_total is null");
-  XPIC_CHECK(iterations_max, "drift_kinetic_trace_open: iterations_max is null");
-  int64_t nsamp;
-  XPIC_CHECK(trace_sample_bytes(samples ? n : 0, steps, sample_every, samples || alive, &nsamp) >= 0,
-    "drift_kinetic_trace_open: the sample buffer (48 n steps / sample_every bytes) is too large");
-  *removed = 0;
-  if (n == 0 || steps == 0) return 0;
-  return batch_trace_open(ctx, "dk_trace_open", "dk_trace_open_compact", XPIC_DK_LAUNCH_STEPS, n, steps, sample_every, nsamp,
-    true, region->compact, region->step0, state_6, samples, iterations_total, iterations_max, exit_step, alive, removed,
-    [&](double* s, const int64_t* list, long m, long first, int ns, double* sm, long long* it_sum, int* it_max, long long* ex,
-      unsigned long long* al, unsigned long long* rm) {
-      hipLaunchKernelGGL(gradB ? k_dk_trace_open<true> : k_dk_trace_open<false>, lane_grid(m), dim3(kBlock), 0, ctx->stream,
-        ctx->g, ctx->field[XPIC_E], ctx->field[XPIC_B], gradB, *params, R, (long)n, s, (const long long*)list, m, first, ns,
-        (long)sample_every, (long)nsamp, sm, it_sum, it_max, ex, al, rm);
-    });
+  return dk_trace(ctx, {"drift_kinetic_trace_open", "state_6", "iterations_total", "iterations_max", false}, "dk_trace_open",
+    "dk_trace_open_compact", n, params, gradB, steps, sample_every, state_6, samples, iterations_total, iterations_max, region,
+    exit_step, alive, removed);
 }
 
 }  // extern "C"

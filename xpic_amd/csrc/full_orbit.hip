@@ -10,7 +10,8 @@
 // (G == 0: every index wraps, so no position, however far out, reads outside a field vector).
 // Every loop is bounded by a constant or by an argument the entry points have range-checked: at most 4 nodes per axis,
 // maxit <= XPIC_FO_MAXIT iterations, at most XPIC_FO_LAUNCH_STEPS steps per launch.  The staging of the host records, the
-// push and trace drivers and the sample buffer's size are batch.h's, shared with drift_kinetic.hip.
+// push and trace drivers and the sample buffer's size are batch.h's, the trace's checks and its call trace_call.h's, shared
+// with drift_kinetic.hip and model_trace.hip.
 #include <algorithm>
 #include <cmath>
 
@@ -18,6 +19,7 @@
 #include "common.h"
 #include "device_common.h"
 #include "ie_shape.h"
+#include "trace_call.h"
 #include "trace_open.h"
 
 // contracted per source expression only (not across statements), so k_fo_push and k_fo_trace, which inline the same
@@ -92,7 +94,9 @@ __global__ void __launch_bounds__(kBlock) k_fo_trace(GridDev g, const double* __
 // k_fo_trace with the region rule of an open trace (trace_open.h) over the m entries of `list` (null:
 // the particles 0 .. m - 1).  A lane whose particle is alive tests the corner of its cell at the top of every step and
 // leaves the loop when the test fails: exit_step = step0 + the steps completed, the state as it was.  The step itself is
-// fo_one, as in k_fo_push and k_fo_trace.  Every thread reaches open_tally.
+// fo_one, as in k_fo_push and k_fo_trace.  Every thread reaches open_tally.  The two traces stay two texts: folded as
+// k_dk_trace is (drift_kinetic.hip), the closed Crank-Nicolson instance would run one wave per SIMD where it runs two
+// (DESIGN.md 5q).
 static_assert(kLaunchSteps <= kOpenRows, "open_tally holds one row per step of a launch");
 template <bool CN>
 __global__ void __launch_bounds__(kBlock) k_fo_trace_open(GridDev g, const double* __restrict__ E,
@@ -130,7 +134,7 @@ __global__ void __launch_bounds__(kBlock) k_fo_trace_open(GridDev g, const doubl
   open_tally<kBlock>(live, gone, first + done, first, ns, sample_every, nsamp, alive, removed);
 }
 
-// the checks the two calls share
+// the checks the three calls share
 int fo_check(xpic_ctx* ctx, int64_t n, const xpic_fo_params* P)
 {
   XPIC_CHECK(ctx != nullptr, "null context");
@@ -138,12 +142,32 @@ int fo_check(xpic_ctx* ctx, int64_t n, const xpic_fo_params* P)
   XPIC_CHECK(n <= ((int64_t)1 << 36), "full_orbit: n is larger than 2^36");
   XPIC_CHECK(ctx->geom.nranks == 1 && ctx->g.G == 0,
     "full_orbit: a context of several z-slabs (or a self_ring one) is not supported: the gathers wrap z in the kernel");
-  XPIC_CHECK(P, "full_orbit: params is null");
-  XPIC_CHECK(P->scheme >= 0 && P->scheme < XPIC_FO_NSCHEMES, "full_orbit: unknown scheme id");
-  if (P->scheme == XPIC_FO_CN)
-    XPIC_CHECK(P->maxit >= 1 && P->maxit <= XPIC_FO_MAXIT, "full_orbit: maxit must be within 1 .. 64");
+  XPIC_CALL(fo_check_params("full_orbit", P));
   XPIC_CHECK(ctx->field[XPIC_E] && ctx->field[XPIC_B], "full_orbit: the context has no E or B");
   return 0;
+}
+
+// both traces, after fo_check; region: null for the closed trace
+int fo_trace(xpic_ctx* ctx, const TraceEntry& E, const char* label, const char* compact_label, int64_t n,
+  const xpic_fo_params& P, int64_t steps, int64_t sample_every, double* p_6, double* samples, int64_t* iterations_sum,
+  int* iterations_max, const xpic_trace_region* region, int64_t* exit_step, int64_t* alive, int64_t* removed)
+{
+  const bool cn = P.scheme == XPIC_FO_CN;
+  OpenRegion R{XPIC_GEOM_NONE, {}, 0};
+  if (!E.closed) XPIC_CALL(trace_region(E.who, region, false, true, &R));
+  // a Chin id has no iterations: its launches get null counters
+  return trace_call(ctx, E, label, compact_label, kLaunchSteps, n, cn, steps, sample_every, p_6, samples, iterations_sum,
+    iterations_max, R, E.closed ? XPIC_COMPACT_NEVER : region->compact, exit_step, alive, removed, nullptr,
+    [&](double* s, const long long* list, long m, long first, int ns, long nsamp, double* sm, long long* it_sum, int* it_max,
+      long long* ex, unsigned long long* al, unsigned long long* rm, double*) {
+      if (E.closed) // its text takes no region: the driver's stand-ins for exit_step and removed stay unused
+        hipLaunchKernelGGL(cn ? k_fo_trace<true> : k_fo_trace<false>, lane_grid(n), dim3(kBlock), 0, ctx->stream, ctx->g,
+          ctx->field[XPIC_E], ctx->field[XPIC_B], P, (long)n, s, first, ns, (long)sample_every, nsamp, sm, it_sum, it_max);
+      else
+        hipLaunchKernelGGL(cn ? k_fo_trace_open<true> : k_fo_trace_open<false>, lane_grid(m), dim3(kBlock), 0, ctx->stream,
+          ctx->g, ctx->field[XPIC_E], ctx->field[XPIC_B], P, R, (long)n, s, list, m, first, ns, (long)sample_every, nsamp, sm,
+          it_sum, it_max, ex, al, rm);
+    });
 }
 
 }  // namespace
@@ -175,28 +199,8 @@ int xpic_full_orbit_trace(xpic_ctx* ctx, int64_t n, const xpic_fo_params* params
   double* p_6, double* samples, int64_t* iterations_sum, int* iterations_max)
 { // the time loops of boris_push_ex1.cpp:51-60 and crank_nicolson_push_ex2.cpp:43-56
   XPIC_CALL(fo_check(ctx, n, params));
-  const bool cn = params->scheme == XPIC_FO_CN;
-  XPIC_CHECK(steps >= 0, "full_orbit_trace: steps is negative");
-  XPIC_CHECK(!samples || sample_every >= 1, "full_orbit_trace: sample_every must be >= 1 when samples are asked for");
-  XPIC_CHECK(p_6, "full_orbit_trace: p_6 is null");
-  XPIC_CHECK(iterations_sum || !cn, "full_orbit_trace: iterations_sum is null");
-  XPIC_CHECK(iterations_max || !cn, "full_orbit_trace: iterations_max is null");
-  int64_t nsamp;
-  XPIC_CHECK(trace_sample_bytes(n, steps, sample_every, samples != nullptr, &nsamp) >= 0,
-    "full_orbit_trace: the sample buffer (48 n steps / sample_every bytes) is too large");
-  if (n == 0) return 0;
-  // a Chin id has no iterations: its launches get null counters, and the caller's are zeroed here
-  XPIC_CALL(batch_trace(ctx, "fo_trace", kLaunchSteps, n, steps, nsamp, cn, p_6, samples, iterations_sum, iterations_max,
-    [&](double* s, long first, int ns, double* sm, long long* it_sum, int* it_max) {
-      hipLaunchKernelGGL(cn ? k_fo_trace<true> : k_fo_trace<false>, lane_grid(n), dim3(kBlock), 0, ctx->stream, ctx->g,
-        ctx->field[XPIC_E], ctx->field[XPIC_B], *params, (long)n, s, first, ns, (long)sample_every, (long)nsamp, sm, it_sum,
-        it_max);
-    }));
-  if (!cn) {
-    if (iterations_sum) std::fill(iterations_sum, iterations_sum + n, (int64_t)0);
-    if (iterations_max) std::fill(iterations_max, iterations_max + n, 0);
-  }
-  return 0;
+  return fo_trace(ctx, {"full_orbit_trace", "p_6", "iterations_sum", "iterations_max", true}, "fo_trace", "fo_trace", n,
+    *params, steps, sample_every, p_6, samples, iterations_sum, iterations_max, nullptr, nullptr, nullptr, nullptr);
 }
 
 int xpic_full_orbit_trace_open(xpic_ctx* ctx, int64_t n, const xpic_fo_params* params, int64_t steps, int64_t sample_every,
@@ -204,35 +208,9 @@ int xpic_full_orbit_trace_open(xpic_ctx* ctx, int64_t n, const xpic_fo_params* p
   int64_t* exit_step, int64_t* alive, int64_t* removed)
 { // xpic_full_orbit_trace with RemoveParticles::execute (remove_particles.cpp:22-38) at the top of every step
   XPIC_CALL(fo_check(ctx, n, params));
-  const bool cn = params->scheme == XPIC_FO_CN;
-  OpenRegion R;
-  XPIC_CALL(open_region("full_orbit_trace_open", region, &R));
-  XPIC_CHECK(steps >= 0, "full_orbit_trace_open: steps is negative");
-  XPIC_CHECK((!samples && !alive) || sample_every >= 1,
-    "full_orbit_trace_open: sample_every must be >= 1 when samples or alive are asked for");
-  XPIC_CHECK(p_6, "full_orbit_trace_open: p_6 is null");
-  XPIC_CHECK(exit_step, "full_orbit_trace_open: exit_step is null");
-  XPIC_CHECK(removed, "full_orbit_trace_open: removed is null");
-  XPIC_CHECK(iterations_sum || !cn, "full_orbit_trace_open: iterations_sum is null");
-  XPIC_CHECK(iterations_max || !cn, "full_orbit_trace_open: iterations_max is null");
-  int64_t nsamp;
-  XPIC_CHECK(trace_sample_bytes(samples ? n : 0, steps, sample_every, samples || alive, &nsamp) >= 0,
-    "full_orbit_trace_open: the sample buffer (48 n steps / sample_every bytes) is too large");
-  *removed = 0;
-  if (n == 0 || steps == 0) return 0;
-  XPIC_CALL(batch_trace_open(ctx, "fo_trace_open", "fo_trace_open_compact", kLaunchSteps, n, steps, sample_every, nsamp, cn,
-    region->compact, region->step0, p_6, samples, iterations_sum, iterations_max, exit_step, alive, removed,
-    [&](double* s, const int64_t* list, long m, long first, int ns, double* sm, long long* it_sum, int* it_max, long long* ex,
-      unsigned long long* al, unsigned long long* rm) {
-      hipLaunchKernelGGL(cn ? k_fo_trace_open<true> : k_fo_trace_open<false>, lane_grid(m), dim3(kBlock), 0, ctx->stream,
-        ctx->g, ctx->field[XPIC_E], ctx->field[XPIC_B], *params, R, (long)n, s, (const long long*)list, m, first, ns,
-        (long)sample_every, (long)nsamp, sm, it_sum, it_max, ex, al, rm);
-    }));
-  if (!cn) {
-    if (iterations_sum) std::fill(iterations_sum, iterations_sum + n, (int64_t)0);
-    if (iterations_max) std::fill(iterations_max, iterations_max + n, 0);
-  }
-  return 0;
+  return fo_trace(ctx, {"full_orbit_trace_open", "p_6", "iterations_sum", "iterations_max", false}, "fo_trace_open",
+    "fo_trace_open_compact", n, *params, steps, sample_every, p_6, samples, iterations_sum, iterations_max, region, exit_step,
+    alive, removed);
 }
 
 }  // extern "C"

@@ -18,8 +18,8 @@
 // host passes as R.kind < 0.  No grid vector is read, so no index is formed from a position and any context will do.
 // Every loop is bounded by a constant or by an argument the entry points have range-checked: fo maxit <= XPIC_FO_MAXIT,
 // 1 <= dk maxit <= XPIC_MODEL_DK_MAXIT, at most XPIC_MODEL_LAUNCH_STEPS steps per launch.  Every global index is formed
-// under q < n, row < nsamp, i < nown or i < nsteps.  The staging is batch.h's batch_trace_open with the "never" policy;
-// sums_4 travels as [4][n] in a DevScratch of this file.
+// under q < n, row < nsamp, i < nown or i < nsteps.  The trace's checks and its call are trace_call.h's, shared with the
+// grid traces; the staging is batch.h's batch_trace with the "never" policy; sums_4 travels as [4][n] beside it.
 #include <algorithm>
 #include <cmath>
 #include <vector>
@@ -29,6 +29,7 @@
 #include "device_common.h"
 #include "field_model.h"
 #include "ie_shape.h"
+#include "trace_call.h"
 #include "trace_open.h"
 
 // as in full_orbit.hip and drift_kinetic.hip: contracted per source expression only
@@ -99,7 +100,7 @@ __global__ void __launch_bounds__(kBlock) k_set_model_field(GridDev g, xpic_fiel
   }
 }
 
-// k_fo_trace_open (full_orbit.hip) on the model; R.kind < 0: no region rule
+// k_fo_trace_open (full_orbit.hip) on the model, without a list; R.kind < 0: no region rule
 template <bool CN>
 __global__ void __launch_bounds__(kBlock) k_model_fo_trace(GridDev g, xpic_field_model M, xpic_fo_params P, OpenRegion R,
   long n, double* __restrict__ s, long first, int nsteps, long sample_every, long nsamp, double* __restrict__ samples,
@@ -207,7 +208,7 @@ __global__ void __launch_bounds__(kBlock) k_timed_fo_trace(GridDev g, xpic_field
   open_tally<kBlock>(live, gone, first + done, first, ns, sample_every, nsamp, alive, removed);
 }
 
-// k_dk_trace_open (drift_kinetic.hip) on the model of the step's clock
+// k_dk_trace_open (drift_kinetic.hip) on the model of the step's clock, without a list
 template <class Clock>
 __global__ void __launch_bounds__(kBlock) k_model_dk_trace(GridDev g, Clock C, xpic_dk_params P, OpenRegion R, long n,
   double* __restrict__ s, long first, int nsteps, long sample_every, long nsamp, double* __restrict__ samples,
@@ -271,88 +272,26 @@ int timed_envelope(const std::string& who, const xpic_field_envelope* in, xpic_f
   return 0;
 }
 
-// open_region (trace_open.h) with XPIC_GEOM_NONE allowed and `compact` not read
-int model_region(const std::string& who, const xpic_trace_region* in, OpenRegion* R)
-{
-  XPIC_CHECK(in, who + ": region is null");
-  XPIC_CHECK(in->geometry == XPIC_GEOM_NONE || in->geometry == XPIC_GEOM_BOX || in->geometry == XPIC_GEOM_CYLINDER,
-    who + ": unknown geometry kind");
-  XPIC_CHECK(in->step0 >= 0, who + ": step0 is negative");
-  R->kind = in->geometry;
-  for (int i = 0; i < 7; ++i) R->a[i] = in->geom[i];
-  R->step0 = in->step0;
-  return 0;
-}
-
 // the checks a pusher's timed and untimed entry points make first, up to the model
 int fo_checks(const std::string& who, xpic_ctx* ctx, int64_t n, const xpic_fo_params* params, const xpic_field_model* model)
 {
   XPIC_CHECK(ctx != nullptr, "null context");
   XPIC_CHECK(n >= 0, who + ": n is negative");
-  XPIC_CHECK(params, who + ": params is null");
-  XPIC_CHECK(params->scheme >= 0 && params->scheme < XPIC_FO_NSCHEMES, who + ": unknown scheme id");
-  if (params->scheme == XPIC_FO_CN)
-    XPIC_CHECK(params->maxit >= 1 && params->maxit <= XPIC_FO_MAXIT, who + ": maxit must be within 1 .. 64");
+  XPIC_CALL(fo_check_params(who, params));
   return model_ok(who, model);
 }
 int dk_checks(const std::string& who, xpic_ctx* ctx, int64_t n, const xpic_dk_params* params, const xpic_field_model* model)
 {
   XPIC_CHECK(ctx != nullptr, "null context");
   XPIC_CHECK(n >= 0, who + ": n is negative");
-  XPIC_CHECK(params, who + ": params is null");
-  XPIC_CHECK(params->maxit >= 1 && params->maxit <= XPIC_MODEL_DK_MAXIT, who + ": maxit must be within 1 .. 1024");
-  XPIC_CHECK(params->mp != 0.0, who + ": mp must not be 0");
+  XPIC_CALL(dk_check_params(who, params, XPIC_MODEL_DK_MAXIT));
   return model_ok(who, model);
 }
 
-// The checks and the driver all four traces share, after their own checks of params.  Under XPIC_GEOM_NONE the optional
-// outputs that are null get stand-ins here, so the kernel and batch_trace_open see one shape of call.  sums_4 (null:
-// none) is staged as [4][n] around the launches.  launch(..., sums): the device's [4][n], null without sums_4.
-template <class Launch>
-int model_trace(xpic_ctx* ctx, const std::string& who, const char* label, int64_t n, bool counters, int64_t steps,
-  int64_t sample_every, double* state_6, double* samples, int64_t* it_sum, int* it_max, const OpenRegion& R,
-  int64_t* exit_step, int64_t* alive, int64_t* removed, double* sums_4, Launch launch)
+// how the four model traces' messages name their arrays (trace_call.h)
+TraceEntry model_entry(const std::string& who)
 {
-  const bool open = R.kind >= 0;
-  XPIC_CHECK(n <= ((int64_t)1 << 36), who + ": n is larger than 2^36");
-  XPIC_CHECK(steps >= 0, who + ": steps is negative");
-  XPIC_CHECK((!samples && !alive) || sample_every >= 1, who + ": sample_every must be >= 1 when samples or alive are asked for");
-  XPIC_CHECK(state_6, who + ": the particle array is null");
-  XPIC_CHECK(exit_step || !open, who + ": exit_step is null");
-  XPIC_CHECK(removed || !open, who + ": removed is null");
-  XPIC_CHECK((it_sum && it_max) || !counters, who + ": an iteration counter is null");
-  int64_t nsamp;
-  XPIC_CHECK(trace_sample_bytes(samples ? n : 0, steps, sample_every, samples || alive, &nsamp) >= 0,
-    who + ": the sample buffer (48 n steps / sample_every bytes) is too large");
-  if (removed) *removed = 0;
-  if (n == 0 || steps == 0) return 0;
-  std::vector<int64_t> ex_own;
-  if (!exit_step) {
-    ex_own.assign((size_t)n, -1);
-    exit_step = ex_own.data();
-  }
-  int64_t rm_own = 0;
-  std::vector<double> hsum;
-  DevScratch<double> dsum;
-  if (sums_4) {
-    to_soa(sums_4, n, hsum, 4);
-    XPIC_CALL(dsum.alloc(4 * n));
-    XPIC_CALL(upload(dsum, hsum.data(), 4 * n, ctx->stream));
-  }
-  XPIC_CALL(batch_trace_open(ctx, label, label, kLaunchSteps, n, steps, sample_every, nsamp, counters, XPIC_COMPACT_NEVER,
-    R.step0, state_6, samples, it_sum, it_max, exit_step, alive, removed ? removed : &rm_own,
-    [&](double* s, const int64_t*, long, long first, int ns, double* sm, long long* sum, int* mx, long long* ex,
-      unsigned long long* al, unsigned long long* rm) { launch(s, first, ns, (long)nsamp, sm, sum, mx, ex, al, rm, dsum.p); }));
-  if (sums_4) {
-    XPIC_CALL(download(hsum.data(), dsum, 4 * n, ctx->stream));
-    XPIC_HIP(hipStreamSynchronize(ctx->stream));
-    to_aos(hsum.data(), n, sums_4, 4);
-  }
-  if (!counters) {
-    if (it_sum) std::fill(it_sum, it_sum + n, (int64_t)0);
-    if (it_max) std::fill(it_max, it_max + n, 0);
-  }
-  return 0;
+  return {who.c_str(), "the particle array", "an iteration counter", "an iteration counter", false};
 }
 
 // the drift-kinetic trace of either clock, after the checks: `label` names the profile entry
@@ -361,10 +300,10 @@ int dk_trace(xpic_ctx* ctx, const std::string& who, const char* label, int64_t n
   int64_t steps, int64_t sample_every, double* state_6, double* samples, int64_t* it_total, int* it_max, const OpenRegion& R,
   int64_t* exit_step, int64_t* alive, int64_t* removed)
 {
-  return model_trace(ctx, who, label, n, true, steps, sample_every, state_6, samples, it_total, it_max, R, exit_step, alive,
-    removed, nullptr,
-    [&](double* s, long first, int ns, long nsamp, double* sm, long long* sum, int* mx, long long* ex, unsigned long long* al,
-      unsigned long long* rm, double*) {
+  return trace_call(ctx, model_entry(who), label, label, kLaunchSteps, n, true, steps, sample_every, state_6, samples,
+    it_total, it_max, R, XPIC_COMPACT_NEVER, exit_step, alive, removed, nullptr,
+    [&](double* s, const long long*, long, long first, int ns, long nsamp, double* sm, long long* sum, int* mx, long long* ex,
+      unsigned long long* al, unsigned long long* rm, double*) {
       hipLaunchKernelGGL(k_model_dk_trace<Clock>, lane_grid(n), dim3(kBlock), 0, ctx->stream, ctx->g, C, P, R, (long)n, s,
         first, ns, (long)sample_every, nsamp, sm, sum, mx, ex, al, rm);
     });
@@ -429,12 +368,12 @@ int xpic_model_full_orbit_trace(xpic_ctx* ctx, int64_t n, const xpic_fo_params* 
   const std::string who = "model_full_orbit_trace";
   XPIC_CALL(fo_checks(who, ctx, n, params, model));
   OpenRegion R;
-  XPIC_CALL(model_region(who, region, &R));
+  XPIC_CALL(trace_region(who, region, true, false, &R));
   const bool cn = params->scheme == XPIC_FO_CN;
-  return model_trace(ctx, who, "model_fo_trace", n, cn, steps, sample_every, p_6, samples, iterations_sum, iterations_max, R,
-    exit_step, alive, removed, nullptr,
-    [&](double* s, long first, int ns, long nsamp, double* sm, long long* sum, int* mx, long long* ex, unsigned long long* al,
-      unsigned long long* rm, double*) {
+  return trace_call(ctx, model_entry(who), "model_fo_trace", "model_fo_trace", kLaunchSteps, n, cn, steps, sample_every, p_6,
+    samples, iterations_sum, iterations_max, R, XPIC_COMPACT_NEVER, exit_step, alive, removed, nullptr,
+    [&](double* s, const long long*, long, long first, int ns, long nsamp, double* sm, long long* sum, int* mx, long long* ex,
+      unsigned long long* al, unsigned long long* rm, double*) {
       hipLaunchKernelGGL(cn ? k_model_fo_trace<true> : k_model_fo_trace<false>, lane_grid(n), dim3(kBlock), 0, ctx->stream,
         ctx->g, *model, *params, R, (long)n, s, first, ns, (long)sample_every, nsamp, sm, sum, mx, ex, al, rm);
     });
@@ -447,7 +386,7 @@ int xpic_model_drift_kinetic_trace(xpic_ctx* ctx, int64_t n, const xpic_dk_param
   const std::string who = "model_drift_kinetic_trace";
   XPIC_CALL(dk_checks(who, ctx, n, params, model));
   OpenRegion R;
-  XPIC_CALL(model_region(who, region, &R));
+  XPIC_CALL(trace_region(who, region, true, false, &R));
   return dk_trace(ctx, who, "model_dk_trace", n, *params, StaticClock{*model}, steps, sample_every, state_6, samples,
     iterations_total, iterations_max, R, exit_step, alive, removed);
 }
@@ -462,14 +401,14 @@ int xpic_model_full_orbit_trace_timed(xpic_ctx* ctx, int64_t n, const xpic_fo_pa
   xpic_field_envelope V;
   XPIC_CALL(timed_envelope(who, envelope, &V));
   OpenRegion R;
-  XPIC_CALL(model_region(who, region, &R));
+  XPIC_CALL(trace_region(who, region, true, false, &R));
   const bool cn = params->scheme == XPIC_FO_CN, sums = sums_4 != nullptr;
   auto kernel = cn ? (sums ? k_timed_fo_trace<true, true> : k_timed_fo_trace<true, false>)
                    : (sums ? k_timed_fo_trace<false, true> : k_timed_fo_trace<false, false>);
-  return model_trace(ctx, who, "timed_fo_trace", n, cn, steps, sample_every, p_6, samples, iterations_sum, iterations_max, R,
-    exit_step, alive, removed, sums_4,
-    [&](double* s, long first, int ns, long nsamp, double* sm, long long* sum, int* mx, long long* ex, unsigned long long* al,
-      unsigned long long* rm, double* sd) {
+  return trace_call(ctx, model_entry(who), "timed_fo_trace", "timed_fo_trace", kLaunchSteps, n, cn, steps, sample_every, p_6,
+    samples, iterations_sum, iterations_max, R, XPIC_COMPACT_NEVER, exit_step, alive, removed, sums_4,
+    [&](double* s, const long long*, long, long first, int ns, long nsamp, double* sm, long long* sum, int* mx, long long* ex,
+      unsigned long long* al, unsigned long long* rm, double* sd) {
       hipLaunchKernelGGL(kernel, lane_grid(n), dim3(kBlock), 0, ctx->stream, ctx->g, *model, V, *params, R, (long)n, s, first,
         ns, (long)sample_every, nsamp, sm, sum, mx, ex, al, rm, sd);
     });
@@ -485,7 +424,7 @@ int xpic_model_drift_kinetic_trace_timed(xpic_ctx* ctx, int64_t n, const xpic_dk
   xpic_field_envelope V;
   XPIC_CALL(timed_envelope(who, envelope, &V));
   OpenRegion R;
-  XPIC_CALL(model_region(who, region, &R));
+  XPIC_CALL(trace_region(who, region, true, false, &R));
   return dk_trace(ctx, who, "timed_dk_trace", n, *params, EnvelopeClock{*model, V}, steps, sample_every, state_6, samples,
     iterations_total, iterations_max, R, exit_step, alive, removed);
 }

@@ -1,7 +1,7 @@
-// trace_open.h -- what the open traces of full_orbit.hip and drift_kinetic.hip share on the device: the region rule of
-// RemoveParticles (src/commands/remove_particles.cpp:22-38) for one particle, and the workgroup's tally of the lanes
-// that are still alive at each sample of a launch and of the lanes the launch removed.  The list of live particles and
-// its compaction are trace_open.hip's, the host driver is batch.h's batch_trace_open.
+// trace_open.h -- what the traces of full_orbit.hip, drift_kinetic.hip and model_trace.hip share on the device: the region
+// rule of RemoveParticles (src/commands/remove_particles.cpp:22-38) for one particle, and the workgroup's tally of the
+// lanes that are still alive at each sample of a launch and of the lanes the launch removed.  The list of live particles
+// and its compaction are trace_open.hip's, the host driver is batch.h's batch_trace.
 #pragma once
 
 #include "common.h"
@@ -10,21 +10,23 @@
 namespace xpic {
 
 struct OpenRegion {
-  int kind;        // XPIC_GEOM_BOX, XPIC_GEOM_CYLINDER
+  int kind;        // XPIC_GEOM_BOX, XPIC_GEOM_CYLINDER; < 0 (XPIC_GEOM_NONE): no region, the closed trace
   double a[7];     // within()'s
   long long step0; // steps the batch has been traced before this call
 };
 
 constexpr int kOpenRows = 64; // sample rows one launch can reach: its steps, at most XPIC_FO_ / XPIC_DK_LAUNCH_STEPS
 
-// the checks of an xpic_trace_region that the two entry points share
-inline int open_region(const char* who, const xpic_trace_region* in, OpenRegion* R)
+// the checks of an xpic_trace_region.  allow_none: XPIC_GEOM_NONE, "no region", is a geometry (the model traces);
+// read_compact: the call compacts its list, so `compact` is checked (the grid traces)
+inline int trace_region(const std::string& who, const xpic_trace_region* in, bool allow_none, bool read_compact, OpenRegion* R)
 {
-  XPIC_CHECK(in, std::string(who) + ": region is null");
-  XPIC_CHECK(in->geometry == XPIC_GEOM_BOX || in->geometry == XPIC_GEOM_CYLINDER, std::string(who) + ": unknown geometry kind");
-  XPIC_CHECK(in->compact >= XPIC_COMPACT_AUTO && in->compact <= XPIC_COMPACT_ALWAYS,
-    std::string(who) + ": compact must be 0 (auto), 1 (never) or 2 (always)");
-  XPIC_CHECK(in->step0 >= 0, std::string(who) + ": step0 is negative");
+  XPIC_CHECK(in, who + ": region is null");
+  XPIC_CHECK((allow_none && in->geometry == XPIC_GEOM_NONE) || in->geometry == XPIC_GEOM_BOX ||
+      in->geometry == XPIC_GEOM_CYLINDER, who + ": unknown geometry kind");
+  XPIC_CHECK(!read_compact || (in->compact >= XPIC_COMPACT_AUTO && in->compact <= XPIC_COMPACT_ALWAYS),
+    who + ": compact must be 0 (auto), 1 (never) or 2 (always)");
+  XPIC_CHECK(in->step0 >= 0, who + ": step0 is negative");
   R->kind = in->geometry;
   for (int i = 0; i < 7; ++i) R->a[i] = in->geom[i];
   R->step0 = in->step0;

@@ -1,4 +1,4 @@
-// trace_open.hip -- the list of live particles of an open trace: between two launches batch_trace_open
+// trace_open.hip -- the list of live particles of an open trace: between two launches batch_trace
 // (batch.h) may replace the list the next launch covers by its live entries, in their order.  A scan and a scatter:
 //   k_live_count    one count per workgroup of 256 entries (block_reduce_store, device_common.h)
 //   k_live_offsets  their exclusive prefix, one workgroup
