@@ -71,7 +71,7 @@ const char* xpic_last_error(void);
 /* XPIC_VERSION, with XPIC_VERSION_EXPERIMENT_BIT set when any object of the library was built with -DXPIC_EXPERIMENT
  * (ablation switches and in-kernel timers of the kernels; some produce wrong physics by design): refuse such a library
  * for production runs. */
-#define XPIC_VERSION 6
+#define XPIC_VERSION 7
 #define XPIC_VERSION_EXPERIMENT_BIT 0x40000000
 int xpic_version(void);
 
@@ -359,6 +359,42 @@ typedef struct xpic_inject_params {
 } xpic_inject_params;
 int xpic_inject_particles(xpic_ctx* ctx, int ionized, int ejected, const xpic_inject_params* params, int64_t pairs,
   int64_t step, int64_t* added, double energy2[2]);
+/* Binary Coulomb collisions between the records of one cell (Takizuka and Abe, J. Comput. Phys. 25, 205, 1977),
+ * non-relativistic.  AN EXTENSION: the reference has no collision operator, so no file:line of it is cited here.
+ * A call collides sort_a with sort_b (the same sort: intra-species) inside every local cell, independently of every other
+ * cell; positions and the order of the records are never touched.  The two sorts must carry the same weight n / Np.
+ * Per cell: Na, Nb from cell_start; n_L = (n / Np) min(Na, Nb).  One stream key per (seed, step, sort_a, sort_b, GLOBAL
+ * cell ((z0 + cz) ny + cy) nx + cx) -- z-slabs and the single box draw the same numbers -- with sub-streams for the
+ * permutation of a, of b, and the draws of pair p.  Record i of the cell gets a 64-bit key; the permutation pi orders the
+ * records by (key, i).  Intra-species pairs: (pi0, pi1), (pi2, pi3), ... (p = 0, 1, ...); an odd N >= 3 starts with
+ * (pi0, pi1), (pi1, pi2), (pi2, pi0), one after the other with dt / 2 each (p = 0, 1, 2), then (pi3, pi4), ... (p = 3, ...);
+ * N < 2: nothing.  Inter-species: the sort with fewer records in the cell is the short side (equal counts: sort_b); record
+ * pi_long[j] meets pi_short[j mod N_short], p = j, the meetings of one short record in increasing j; an empty side: nothing.
+ * One collision of a-record and b-record (the call's order; intra-species: first and second of the pair):
+ * u = v_a - v_b, m_ab = m_a m_b / (m_a + m_b), sigma^2 = strength q_a^2 q_b^2 n_L dt / (m_ab^2 |u|^3);
+ * delta = sigma sqrt(-2 ln u1) cos(2 pi u2), Phi = 2 pi u3; sin Theta = 2 delta / (1 + delta^2),
+ * 1 - cos Theta = 2 delta^2 / (1 + delta^2); the relative velocity is rotated by (Theta, Phi) (Takizuka-Abe's eq. 4a-4c;
+ * for u_perp == 0: du = (u sin Theta cos Phi, u sin Theta sin Phi, -u_z (1 - cos Theta))), v_a += (m_ab / m_a) du,
+ * v_b -= (m_ab / m_b) du.  A pair with |u| == 0 is skipped and counted.  Momentum and energy of every pair are conserved.
+ * strength: in the reference's units (velocities in c, time in 1 / w_pe, densities in n0) it is ln Lambda / (8 pi) times the
+ * inverse number of particles in a skin-depth cube, 1 / (n0 (c / w_pe)^3).
+ * out4 = {pairs collided, pairs skipped (|u| == 0), sum of sigma^2 over the collided pairs, pairs with sigma^2 > 1}, summed
+ * over the z-slabs (the call is collective): the mean sigma^2 and the count above 1 say whether the small-angle step is
+ * resolved.  Works for all three schemes (it reads nothing but the sorts).  Argument errors (a bad sort, unequal weights, a
+ * null pointer, a negative strength) are refused on every slab before anything changes.  A pair so slow that sigma^2 or
+ * delta^2 exceeds 1e300 (or overflows) scatters by Theta = pi (the limit: sin Theta = 0, 1 - cos Theta = 2); an overflowed sigma^2
+ * is counted above 1 and left out of the sum.  Cells of more than XPIC_COLLIDE_LDS_CELL records of a sort take a second
+ * path that uses the sort's binning scratch.
+ * xpic_collide_info: out2 = {XPIC_COLLIDE_LDS_CELL as the library was built, the LOCAL cells of the context's last
+ * xpic_collide that took the second path (not summed over the slabs)}. */
+#define XPIC_COLLIDE_LDS_CELL 256
+typedef struct xpic_collision_params {
+  double strength;   /* S above; 0: the call changes nothing, bit for bit */
+  double dt;         /* collision time step; <= 0: the context's dt */
+  uint64_t seed;
+} xpic_collision_params;
+int xpic_collide(xpic_ctx* ctx, int sort_a, int sort_b, const xpic_collision_params* p, int64_t step, double out4[4]);
+int xpic_collide_info(xpic_ctx* ctx, int64_t out2[2]);
 /* SetCoilsField::operator() (src/commands/set_magnetic_field.cpp:38-150): field += the field of the coils {z0, R, I}
  * (coils3[3 i ..]) about the axis (geom_x / 2, geom_y / 2), by the reference's 2000-point quadrature with its
  * denominator_tolerance, at the positions it writes: Bx at (x, y + 1/2, z + 1/2) d, By at (x + 1/2, y, z + 1/2) d,

@@ -30,7 +30,7 @@ SYMBOLS = [
     "xpic_ecsimcorr_first_push", "xpic_ecsimcorr_second_push", "xpic_ecsimcorr_final_update",
     "xpic_calculate_energy", "xpic_ecsimcorr_scalars", "xpic_solve", "xpic_set_tolerances", "xpic_set_preconditioner", "xpic_precond_apply", "xpic_precond_get", "xpic_set_overlap", "xpic_comm_stats", "xpic_set_fill_kernel", "xpic_set_fused_rebin", "xpic_get_fill_variant", "xpic_debug_set", "xpic_step",
     "xpic_energy", "xpic_momentum", "xpic_charge_density", "xpic_moment_density", "xpic_moment", "xpic_velocity_distribution", "xpic_remove_particles", "xpic_fields_damping",
-    "xpic_inject_particles", "xpic_set_coils_field", "xpic_set_mirror_field", "xpic_cell_traversal", "xpic_implicit_esirkepov_interpolate",
+    "xpic_inject_particles", "xpic_collide", "xpic_collide_info", "xpic_set_coils_field", "xpic_set_mirror_field", "xpic_cell_traversal", "xpic_implicit_esirkepov_interpolate",
     "xpic_implicit_esirkepov_decompose", "xpic_drift_kinetic_interpolate", "xpic_drift_kinetic_push",
     "xpic_drift_kinetic_trace", "xpic_full_orbit_push", "xpic_full_orbit_trace", "xpic_full_orbit_trace_open",
     "xpic_drift_kinetic_trace_open", "xpic_paired_trace", "xpic_model_fields", "xpic_set_model_field",
@@ -82,6 +82,13 @@ class MomentumParams(C.Structure):
 class InjectParams(C.Structure):
     _fields_ = [("coordinate", C.c_int32), ("reserved", C.c_int32), ("geom", C.c_double * 7),
                 ("momentum", MomentumParams * 2), ("seed", C.c_uint64)]
+
+
+class CollisionParams(C.Structure):  # include/xpic_hip.h: xpic_collision_params
+    _fields_ = [("strength", C.c_double), ("dt", C.c_double), ("seed", C.c_uint64)]
+
+
+COLLIDE_LDS_CELL = 256  # include/xpic_hip.h: XPIC_COLLIDE_LDS_CELL (Context.collide_info reads the library's own)
 
 
 def _geom7(geometry):
@@ -662,6 +669,23 @@ class Context:
         self._ck(self.L.xpic_inject_particles(self.h, ionized, ejected, C.byref(p), C.c_int64(int(pairs)),
                                               C.c_int64(int(step)), C.byref(added), _dp(e2)))
         return added.value, (float(e2[0]), float(e2[1]))
+
+    def collide(self, sort_a, sort_b, strength, step, seed=0, dt=None):
+        """Takizuka-Abe binary collisions of sort_a with sort_b (the same sort: intra-species) inside every cell
+        (include/xpic_hip.h: xpic_collide; an extension, the reference has no collision operator) -> dict of the pairs
+        collided, the pairs skipped (|u| == 0), the sum of sigma^2 over the collided pairs and the pairs with
+        sigma^2 > 1, summed over the slabs.  dt: None for the context's."""
+        p = CollisionParams(float(strength), 0.0 if dt is None else float(dt), int(seed))
+        o = np.zeros(4)
+        self._ck(self.L.xpic_collide(self.h, int(sort_a), int(sort_b), C.byref(p), C.c_int64(int(step)), _dp(o)))
+        return dict(pairs=int(o[0]), skipped=int(o[1]), sigma2_sum=float(o[2]), sigma2_over_1=int(o[3]))
+
+    def collide_info(self):
+        """dict of the kernel's LDS-path limit (XPIC_COLLIDE_LDS_CELL as the library was built) and the local cells of
+        the last collide() that took the second path"""
+        o = (C.c_int64 * 2)()
+        self._ck(self.L.xpic_collide_info(self.h, o))
+        return dict(lds_cell=int(o[0]), large_cells=int(o[1]))
 
     def set_coils_field(self, coils, field=B0):
         """SetCoilsField: field += the field of the coils [(z0, R, I), ...]"""

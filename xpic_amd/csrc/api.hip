@@ -977,6 +977,23 @@ int xpic_set_mirror_field(xpic_ctx* ctx, int field, double D, double R, double I
   return set_mirror_field(ctx, ctx->field[field], D, R, I);
 }
 
+int xpic_collide(xpic_ctx* ctx, int sort_a, int sort_b, const xpic_collision_params* p, int64_t step, double out4[4])
+{ // Takizuka-Abe binary collisions (collide.hip): an extension, the reference has no collision operator
+  CTX_CHECK(ctx);
+  SORT_CHECK(sort_a); SORT_CHECK(sort_b);
+  XPIC_CHECK(p && out4, "null argument");
+  return collide(ctx, sort_a, sort_b, *p, step, out4);
+}
+
+int xpic_collide_info(xpic_ctx* ctx, int64_t out2[2])
+{
+  CTX_CHECK(ctx);
+  XPIC_CHECK(out2, "null argument");
+  out2[0] = XPIC_COLLIDE_LDS_CELL;
+  out2[1] = ctx->collide_large_cells;
+  return 0;
+}
+
 int xpic_charge_collect(xpic_ctx* ctx) // ChargeConservation::initialize, charge_conservation.cpp:117-123
 {
   CTX_CHECK(ctx);

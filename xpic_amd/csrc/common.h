@@ -253,6 +253,7 @@ struct xpic_ctx {
   int* cmd_add = nullptr;
   int* cmd_rank = nullptr;
   int64_t cmd_rank_n = 0;
+  int64_t collide_large_cells = 0; // collide.hip: local cells of the last call that took the second path
   double rtol = 1e-7, atol = 1e-7;
   int maxit = 100;
   xpic::Comm comm;
@@ -381,6 +382,9 @@ int inject_particles(xpic_ctx* c, Sort& si, Sort& se, const xpic_inject_params& 
   int64_t* added, double* energy2);
 int set_coils_field(xpic_ctx* c, double* F, int ncoils, const double* coils3);
 int set_mirror_field(xpic_ctx* c, double* F, double D, double R, double I);
+
+// collide.hip (an extension: the reference has no collision operator)
+int collide(xpic_ctx* c, int sort_a, int sort_b, const xpic_collision_params& p, int64_t step, double* out4);
 
 // ecsim.hip
 int ecsim_fill_sort(xpic_ctx* c, Sort& s, const double* B, double* currI_sort, double* matL, bool first_sort, bool post_ghost_rows);

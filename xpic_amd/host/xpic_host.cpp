@@ -539,6 +539,21 @@ PetscErrorCode InjectParticles::execute(PetscInt t) // inject_particles.cpp:26-6
   return 0;
 }
 
+BinaryCollisions::BinaryCollisions(interfaces::Simulation& sim, interfaces::Particles& a, interfaces::Particles& b,
+  const xpic_collision_params& params)
+  : sim_(sim), a_(a), b_(b), params_(params)
+{
+}
+
+PetscErrorCode BinaryCollisions::execute(PetscInt t) // (an extension: no counterpart in the reference)
+{
+  double out4[4] = {0, 0, 0, 0};
+  HIPCALL(xpic_collide(sim_.ctx, a_.sort_id, b_.sort_id, &params_, t, out4));
+  LOG("  Binary collisions \"" << a_.parameters.sort_name << "\" - \"" << b_.parameters.sort_name << "\": " << (long)out4[0]
+    << " pairs, mean sigma^2 " << (out4[0] > 0 ? out4[2] / out4[0] : 0.0) << ", " << (long)out4[3] << " above 1");
+  return 0;
+}
+
 // build_commands (src/commands/builders/command_builder.cpp:16-62) with ParticlesBuilder::load_coordinate /
 // load_momentum (particles_builder.cpp:9-68) and SetMagneticFieldBuilder (set_magnetic_field_builder.cpp:11-63)
 PetscErrorCode build_commands(interfaces::Simulation& simulation, const std::string& name,
@@ -713,6 +728,30 @@ PetscErrorCode build_commands(interfaces::Simulation& simulation, const std::str
       LOG("  InjectParticles command is added with ionized: \"" << ionized.parameters.sort_name << "\", ejected: \""
         << ejected.parameters.sort_name << "\", " << schedule.per_step << " pairs per step in [" << schedule.start << ", "
         << schedule.end << "]");
+    }
+    else if (command == "BinaryCollisions") { // an extension of the reference's JSON surface (no collision command there)
+      const auto& pi = info.at("particles");
+      std::string na, nb;
+      if (pi.is_string()) na = nb = pi.as_string();
+      else {
+        if (pi.arr.empty() || pi.arr.size() > 2) throw std::runtime_error("BinaryCollisions: \"particles\" takes one or two sort names");
+        na = pi.arr.front().as_string();
+        nb = pi.arr.back().as_string();
+      }
+      auto& a = simulation.get_named_particles(na);
+      auto& b = simulation.get_named_particles(nb);
+      xpic_collision_params p{};
+      p.strength = info.at("strength").as_double();
+      p.dt = info.contains("dt") ? info.at("dt").as_double() : 0.0; // (0: the simulation's dt)
+      p.seed = (uint64_t)result.size(); // (the command's place in its list, as InjectParticles' seed)
+      if (info.contains("seed")) {
+        const double sd = info.at("seed").as_double(); // (the reader's numbers are doubles)
+        if (!(sd >= 0.0 && sd <= 9007199254740992.0) || sd != std::floor(sd))
+          throw std::runtime_error("BinaryCollisions: \"seed\" must be a whole number in [0, 2^53]");
+        p.seed = (uint64_t)sd;
+      }
+      result.emplace_back(std::make_unique<BinaryCollisions>(simulation, a, b, p));
+      LOG("  BinaryCollisions command is added for \"" << na << "\" and \"" << nb << "\", strength " << p.strength);
     }
     else throw std::runtime_error("Unknown command name " + command);
   }

@@ -286,6 +286,24 @@ private:
   PetscReal energy_i_ = 0, energy_e_ = 0;
 };
 
+// "BinaryCollisions": Takizuka-Abe binary collisions between the records of one cell (xpic_collide).  AN EXTENSION of the
+// reference's JSON surface, which has no collision command: {"command": "BinaryCollisions", "particles": [a, b] or a,
+// "strength": S, "seed": ...}; one name (or the same name twice) collides a sort with itself.  "seed" is a JSON number
+// (the reader holds numbers as doubles: whole values up to 2^53; a larger or fractional one is refused); without it the
+// seed is the command's place in its list, so two commands draw different streams and reordering the list changes them:
+// give seeds to keep the streams of a run whose presets are rearranged.
+class BinaryCollisions : public interfaces::Command {
+public:
+  BinaryCollisions(interfaces::Simulation& sim, interfaces::Particles& a, interfaces::Particles& b,
+    const xpic_collision_params& params);
+  PetscErrorCode execute(PetscInt t) override;
+
+private:
+  interfaces::Simulation& sim_;
+  interfaces::Particles &a_, &b_;
+  xpic_collision_params params_;
+};
+
 PetscErrorCode build_commands(interfaces::Simulation& simulation, const std::string& name,
   std::vector<std::unique_ptr<interfaces::Command>>& result);
 
