@@ -678,6 +678,64 @@ int xpic_model_drift_kinetic_trace_timed(xpic_ctx* ctx, int64_t n, const xpic_dk
 int xpic_envelope_factors(xpic_ctx* ctx, const xpic_field_envelope* envelope, double dt, int64_t step0, int64_t nsteps,
   double* out);
 
+/* ---- collisional traces: xpic_model_full_orbit_trace and xpic_model_drift_kinetic_trace with Coulomb scattering of the
+ * test particles off Maxwellian background species, by xpic_collide's pair collision (Takizuka and Abe).  AN EXTENSION, as
+ * xpic_collide is: the reference has no collision operator, so no file:line of it is cited.  Everything that is not said
+ * here is the model traces': region semantics with XPIC_GEOM_NONE, samples, counters, checks, launches of at most
+ * XPIC_MODEL_LAUNCH_STEPS steps, any context.  The envelope traces, the grid traces and the paired and triplet traces have
+ * no collisional form.
+ * When: after the push of step k and before that step's sample is stored, where k = region->step0 + the steps this call
+ * has completed + 1 is the step's global index; the step collides iff k % every == 0, with dt_c = every * dt (dt is
+ * params->dt), against the backgrounds b = 0 .. nbg - 1 in this order.  A removed particle collides no more.
+ * Streams (splitmix / u01 as everywhere in this library): one per (seed, particle0 + q, k, b), q the particle's index in
+ * the batch.  step key: x = seed; splitmix(x); x ^= k * 0xD1342543DE82EF95; key = splitmix(x) (xpic_collide's first two
+ * mixes).  particle key: y = key ^ ((particle0 + q) * 0xD6E8FEB86659FD93); splitmix(y).  stream state: z = particle key ^
+ * ((b + 1) * 0xA0761D6478BD642F); st = splitmix(z).  From st come seven u01 draws in this order: a1 a2 a3 a4, a5, u1 u2 u3.
+ * Partner: w = drift + vth (g1, g2, g3), g1 = sqrt(-2 ln a1) cos(2 pi a2), g2 = sqrt(-2 ln a1) sin(2 pi a2),
+ * g3 = sqrt(-2 ln a3) cos(2 pi a4); vth is the background's thermal speed per component, sqrt(T_b / m_b).
+ * Collision: xpic_collide's text with v_a = v, v_b = w, q_a = qm * mass, m_a = mass, n_L = bg.n, dt = dt_c and (u1, u2, u3)
+ * as its three draws; only the test particle is updated, v += (m_ab / m_a) du.  The partner's side is not stored.  |u| == 0
+ * is skipped and counted, and leaves the record's bits.  The Theta = pi limit and the overflow rule are xpic_collide's.
+ * All of this is rounded operation by operation (no contraction), sigma^2's factor as
+ * ((S (q_a q_a) (q_b q_b) / (m_ab m_ab)) n_L) dt_c with dt_c = (double)every * dt.
+ * Full orbit: v is the record's p; a5 is drawn and discarded.  The staggered LF ids collide their p as it stands.
+ * Guiding centre: B = the model at the pushed position, |B| = sqrt(Bx Bx + By By + Bz Bz), b = B / |B|; |B| == 0 skips the
+ * step's collisions for that particle and counts nbg skipped.  e1 = normalize(b x e_c), e_c the coordinate axis with the
+ * smallest |b_c| (a tie: the lowest index), e2 = b x e1; for every background psi = 2 pi a5,
+ * v = p_parallel b + p_perp (cos psi e1 + sin psi e2), collided as above to v'; then p_parallel' = v' . b,
+ * p_perp' = |v' - p_parallel' b|, mu_p' = mp p_perp'^2 / (2 |B|).  The position is NOT moved: the displacement of the
+ * guiding centre in a collision is left out, so this is velocity-space scattering (pitch-angle and energy), not classical
+ * cross-field transport.
+ * coll_4 (or NULL) = {collisions made, skipped, sum of sigma^2 over the collisions made, collisions with sigma^2 > 1} of this
+ * call; written, not accumulated.
+ * Refused before anything changes: nbg outside 0 .. XPIC_TRACE_BG_MAX, every < 1, particle0 < 0, a negative (or not finite)
+ * strength, mass <= 0, a background with m <= 0, n < 0 or vth < 0.
+ * Guarantees: (a) collisions == NULL, nbg == 0 or strength == 0 is the model trace, bit for bit -- state, samples, counters,
+ * exit_step, alive and removed -- and coll_4 is zeros; (b) a call of s1 + s2 steps equals a call of s1 steps followed by
+ * one of s2 steps with step0 advanced by s1 (and the first call's exit_step), bit for bit; (c) a batch split in two, the
+ * second part with particle0 advanced by the first part's size, gives the bits of the whole batch; (d) momentum and energy
+ * of every test-particle / partner pair are conserved (the partner's side is not stored: tests/collisional_trace_ref.py
+ * checks it). */
+#define XPIC_TRACE_BG_MAX 4
+typedef struct xpic_trace_background { double q, m, n, vth, drift[3]; } xpic_trace_background;
+typedef struct xpic_trace_collisions {
+  int32_t nbg;        /* 0 .. XPIC_TRACE_BG_MAX; 0: no collisions */
+  int32_t every;      /* >= 1: collide after the steps whose global index is a multiple of it, with dt_c = every * dt */
+  uint64_t seed;
+  int64_t particle0;  /* the batch's first particle has the global index particle0 (>= 0) */
+  double strength;    /* S of xpic_collide; 0: no collisions */
+  double mass;        /* m_a of the test particle; q_a = qm * mass */
+  xpic_trace_background bg[XPIC_TRACE_BG_MAX];
+} xpic_trace_collisions;
+int xpic_model_full_orbit_trace_collisional(xpic_ctx* ctx, int64_t n, const xpic_fo_params* params,
+  const xpic_field_model* model, int64_t steps, int64_t sample_every, double* p_6, double* samples, int64_t* iterations_sum,
+  int* iterations_max, const xpic_trace_region* region, int64_t* exit_step, int64_t* alive, int64_t* removed,
+  const xpic_trace_collisions* collisions, double* coll_4);
+int xpic_model_drift_kinetic_trace_collisional(xpic_ctx* ctx, int64_t n, const xpic_dk_params* params,
+  const xpic_field_model* model, int64_t steps, int64_t sample_every, double* state_6, double* samples,
+  int64_t* iterations_total, int* iterations_max, const xpic_trace_region* region, int64_t* exit_step, int64_t* alive,
+  int64_t* removed, const xpic_trace_collisions* collisions, double* coll_4);
+
 /* ---- triplet trace: the whole time loop of the reference's grid tests
  * (tests/drift_kinetic_push/drift_kinetic_grid_boris_ex1..4.cpp, ex1.cpp:79-98) for n triplets, with all seven maxima of
  * ComparisonStats (tests/drift_kinetic_push/drift_kinetic_push.h:253-329) reduced on the device.  Triplet q is three

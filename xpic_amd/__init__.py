@@ -35,7 +35,8 @@ SYMBOLS = [
     "xpic_drift_kinetic_trace", "xpic_full_orbit_push", "xpic_full_orbit_trace", "xpic_full_orbit_trace_open",
     "xpic_drift_kinetic_trace_open", "xpic_paired_trace", "xpic_model_fields", "xpic_set_model_field",
     "xpic_model_full_orbit_trace", "xpic_model_drift_kinetic_trace", "xpic_model_full_orbit_trace_timed",
-    "xpic_model_drift_kinetic_trace_timed", "xpic_envelope_factors", "xpic_triplet_trace", "xpic_charge_collect", "xpic_charge_columns", "xpic_comm_rccl_unique_id", "xpic_comm_init_rccl", "xpic_comm_init_callbacks", "xpic_comm_size", "xpic_comm_peer_export", "xpic_comm_peer_import",
+    "xpic_model_drift_kinetic_trace_timed", "xpic_envelope_factors", "xpic_model_full_orbit_trace_collisional",
+    "xpic_model_drift_kinetic_trace_collisional", "xpic_triplet_trace", "xpic_charge_collect", "xpic_charge_columns", "xpic_comm_rccl_unique_id", "xpic_comm_init_rccl", "xpic_comm_init_callbacks", "xpic_comm_size", "xpic_comm_peer_export", "xpic_comm_peer_import",
     "xpic_profile_enable", "xpic_profile_reset", "xpic_profile_get", "xpic_probe_copy_bandwidth",
 ]
 
@@ -175,6 +176,38 @@ class FieldEnvelope(C.Structure):  # include/xpic_hip.h: xpic_field_envelope
 ENVELOPE_KINDS = {"constant": 0, "ramp": 1, "harmonic": 2}
 
 
+TRACE_BG_MAX = 4  # include/xpic_hip.h: XPIC_TRACE_BG_MAX
+
+
+class TraceBackground(C.Structure):  # include/xpic_hip.h: xpic_trace_background
+    _fields_ = [("q", C.c_double), ("m", C.c_double), ("n", C.c_double), ("vth", C.c_double), ("drift", C.c_double * 3)]
+
+
+class TraceCollisions(C.Structure):  # include/xpic_hip.h: xpic_trace_collisions
+    _fields_ = [("nbg", C.c_int32), ("every", C.c_int32), ("seed", C.c_uint64), ("particle0", C.c_int64),
+                ("strength", C.c_double), ("mass", C.c_double), ("bg", TraceBackground * TRACE_BG_MAX)]
+
+
+def trace_collisions(backgrounds, strength, mass, every=1, seed=0, particle0=0):
+    """The collisions of a collisional trace (include/xpic_hip.h: xpic_trace_collisions).  backgrounds: at most
+    TRACE_BG_MAX dicts of q, m, n, vth (the thermal speed per component, sqrt(T / m)) and drift (three components; not
+    given: at rest); strength: S of Context.collide; mass: the test particle's (its charge is qm * mass); every: collide
+    after every every-th step with every * dt; particle0: the global index of the batch's first particle."""
+    backgrounds = list(backgrounds)
+    if len(backgrounds) > TRACE_BG_MAX:
+        raise XpicError("trace_collisions: more than %d backgrounds" % TRACE_BG_MAX)
+    c = TraceCollisions()
+    c.nbg, c.every, c.seed, c.particle0 = len(backgrounds), int(every), int(seed), int(particle0)
+    c.strength, c.mass = float(strength), float(mass)
+    for i, b in enumerate(backgrounds):
+        extra = set(b) - {"q", "m", "n", "vth", "drift"}
+        if extra:
+            raise XpicError("trace_collisions: no background parameter %r" % (sorted(extra)[0],))
+        c.bg[i] = TraceBackground(float(b["q"]), float(b["m"]), float(b["n"]), float(b["vth"]),
+                                  (C.c_double * 3)(*[float(x) for x in b.get("drift", (0.0, 0.0, 0.0))]))
+    return c
+
+
 def field_envelope(kind, **params):
     """A time envelope of a model's E (include/xpic_hip.h: xpic_field_envelope).  kind: a key of ENVELOPE_KINDS or its
     number; params: the members the kind reads -- ramp: a, b (f = a + b t); harmonic: omega, phase
@@ -238,6 +271,13 @@ class TimedTrace(collections.namedtuple(
     """What Context.model_full_orbit_trace_timed returns: OpenTrace's fields and sums [n][4] (None when not asked for), the
     running sums of crank_nicolson_push_ex3's two checks: the energy balance and the three components of the mean
     transverse velocity, neither divided by the step count."""
+    __slots__ = ()
+
+
+class CollisionalTrace(collections.namedtuple(
+        "CollisionalTrace", "state samples exit_step alive removed iterations_sum iterations_max coll")):
+    """What Context.model_full_orbit_trace_collisional / model_drift_kinetic_trace_collisional return: OpenTrace's fields
+    and coll [4] = (collisions made, skipped, sum of sigma^2, collisions with sigma^2 > 1) of the call."""
     __slots__ = ()
 
 
@@ -884,9 +924,11 @@ class Context:
     _ABSENT = object()  # _model_trace: the library function has no such argument
 
     def _model_trace(self, fn, P, state, steps, model, region, sample_every, exit_step, step0, keep_samples,
-                     envelope=_ABSENT, sums=_ABSENT):
-        """the ctypes call of the four model traces -> the fields of TimedTrace (OpenTrace's and sums).  envelope follows
-        model and sums ends the argument list where fn has them; sums as model_full_orbit_trace_timed takes it"""
+                     envelope=_ABSENT, sums=_ABSENT, collisions=_ABSENT):
+        """the ctypes call of the model traces -> the fields of TimedTrace (OpenTrace's and sums).  envelope follows
+        model and sums ends the argument list where fn has them; sums as model_full_orbit_trace_timed takes it.
+        collisions (what trace_collisions(...) returns, or None) and coll_4 end the list of the collisional traces:
+        then the last field is coll [4]"""
         state, samples, alive, ex, reg, tot, mx = self._open_args(state, steps, sample_every, region, exit_step, step0,
                                                                       "never", keep_samples)
         n = state.shape[0]
@@ -904,7 +946,12 @@ class Context:
                  None if bare else C.byref(removed)]
         if sums is not absent:
             args.append(None if sums is None else _dp(sums))
+        if collisions is not absent:
+            coll = np.zeros(4)
+            args += [None if collisions is None else C.byref(collisions), _dp(coll)]
         self._ck(fn(*args))
+        if collisions is not absent:
+            return state, samples, ex, alive, removed.value, tot, mx, coll
         return state, samples, ex, alive, removed.value, tot, mx, None if sums is absent else sums
 
     def model_full_orbit_trace(self, state, steps, scheme, qm, dt, model, region=None, sample_every=0, exit_step=None,
@@ -938,6 +985,25 @@ class Context:
         return OpenTrace(*self._model_trace(
             self.L.xpic_model_drift_kinetic_trace_timed, self._dk_params(qm, mp, dt, eps, delta, maxit), state, steps, model,
             region, sample_every, exit_step, step0, keep_samples, envelope)[:7])
+
+    # ---- collisional traces (include/xpic_hip.h: xpic_trace_collisions): the two model traces with Coulomb scattering
+    # off Maxwellian backgrounds after the push.  collisions: what trace_collisions(...) returns, or None (the model trace
+    # itself); step0 also fixes which steps collide and their streams
+    def model_full_orbit_trace_collisional(self, state, steps, scheme, qm, dt, model, collisions, region=None,
+                                           sample_every=0, exit_step=None, step0=0, keep_samples=True, atol=1e-7,
+                                           rtol=1e-7, maxit=30):
+        """model_full_orbit_trace with collisions -> CollisionalTrace"""
+        return CollisionalTrace(*self._model_trace(
+            self.L.xpic_model_full_orbit_trace_collisional, self._fo_params(scheme, qm, dt, atol, rtol, maxit), state, steps,
+            model, region, sample_every, exit_step, step0, keep_samples, collisions=collisions))
+
+    def model_drift_kinetic_trace_collisional(self, state, steps, qm, mp, dt, model, collisions, region=None,
+                                              sample_every=0, exit_step=None, step0=0, keep_samples=True, eps=1e-12,
+                                              delta=1e-12, maxit=30):
+        """model_drift_kinetic_trace with collisions -> CollisionalTrace"""
+        return CollisionalTrace(*self._model_trace(
+            self.L.xpic_model_drift_kinetic_trace_collisional, self._dk_params(qm, mp, dt, eps, delta, maxit), state, steps,
+            model, region, sample_every, exit_step, step0, keep_samples, collisions=collisions))
 
     def envelope_factors(self, envelope, dt, step0, nsteps):
         """-> the factors of steps step0 .. step0 + nsteps - 1, evaluated on the device as the traces evaluate them"""

@@ -10,11 +10,13 @@
 // of a sort take the same body with the keys recomputed where they are compared and the slots in the sort's rank[] array
 // (binning scratch: the callers drop the pre-binning anyway, its keys describe the old velocities).
 //
-// Compiled without floating-point contraction: the collision is rounded operation by operation, as numpy rounds it.
+// Compiled without floating-point contraction: the collision is rounded operation by operation, as numpy rounds it.  The
+// collision itself and the streams are collide_pair.h's, shared with collide_trace.hip.
 #include <cmath>
 
 #include "common.h"
 #include "device_common.h"
+#include "collide_pair.h"
 
 #pragma clang fp contract(off)
 
@@ -36,25 +38,7 @@ struct ColDev {
   double fa, fb; // m_ab / m_a, m_ab / m_b
 };
 
-// streams: cell <- (call, global cell); sub-stream <- (cell, tag); item i of a sub-stream: its state starts at
-// key + i * (odd constant), as commands.hip's pair_stream
-constexpr int kTagPermA = 0, kTagPermB = 1, kTagPairs = 2;
-__device__ inline uint64_t cell_key(uint64_t call, long gcell)
-{
-  uint64_t k = call ^ ((uint64_t)gcell * 0xD6E8FEB86659FD93ull);
-  return splitmix(k);
-}
-__device__ inline uint64_t sub_key(uint64_t cell, int tag)
-{
-  uint64_t k = cell ^ ((uint64_t)(tag + 1) * 0xA0761D6478BD642Full);
-  return splitmix(k);
-}
-__device__ inline uint64_t item_state(uint64_t sub, int i) { return sub + (uint64_t)i * 0x2545F4914F6CDD1Dull; }
-__device__ inline uint64_t item_key(uint64_t sub, int i)
-{
-  uint64_t st = item_state(sub, i);
-  return splitmix(st);
-}
+constexpr int kTagPermA = 0, kTagPermB = 1, kTagPairs = 2; // the sub-streams of a cell (collide_pair.h: sub_key)
 
 // what one lane wrote is read by the other lanes of its wave: LDS operations of a wave complete in order, the fence keeps
 // the compiler from moving them; the second path's slots go through global memory
@@ -89,47 +73,10 @@ __device__ inline void permute(uint64_t sub, int n, uint64_t* keys, int* slot, i
   wave_sync<LDS>(); // (the slots are read, and the keys rewritten, by other lanes)
 }
 
-// one collision (include/xpic_hip.h: xpic_collide); cdt = c0 n_L dt of this pair
+// one collision of pair p of the cell's pair stream (collide_pair.h); cdt = c0 n_L dt of this pair
 __device__ inline void collide_pair(const ColDev& P, double cdt, uint64_t pairs, int p, double* va, double* vb, double* t)
 {
-  const double ux = va[0] - vb[0], uy = va[1] - vb[1], uz = va[2] - vb[2];
-  const double u = sqrt(ux * ux + uy * uy + uz * uz);
-  if (u == 0.0) {
-    t[1] += 1.0;
-    return;
-  }
-  const double s2 = cdt / (u * u * u);
-  uint64_t st = item_state(pairs, p);
-  const double u1 = u01(st), u2 = u01(st), u3 = u01(st);
-  const double delta = sqrt(s2) * sqrt(-2.0 * log(u1)) * cos(2.0 * M_PI * u2);
-  const double phi = 2.0 * M_PI * u3;
-  const double d2 = delta * delta;
-  // sin Theta, 1 - cos Theta; a relative velocity so small that sigma^2 or delta^2 leaves the range of a double (or
-  // comes within a factor of it: 2 delta^2 must not overflow) scatters by Theta = pi, the limit of both expressions,
-  // which they have reached to the last place long before (inf / inf otherwise)
-  const bool back = !(d2 <= 1e300);
-  const double sinT = back ? 0.0 : 2.0 * delta / (1.0 + d2), omc = back ? 2.0 : 2.0 * d2 / (1.0 + d2);
-  const double cp = cos(phi), sp = sin(phi);
-  const double up = sqrt(ux * ux + uy * uy);
-  double d[3];
-  if (up == 0.0) {
-    d[0] = u * sinT * cp;
-    d[1] = u * sinT * sp;
-    d[2] = -uz * omc;
-  }
-  else {
-    d[0] = (ux / up) * uz * sinT * cp - (uy / up) * u * sinT * sp - ux * omc;
-    d[1] = (uy / up) * uz * sinT * cp + (ux / up) * u * sinT * sp - uy * omc;
-    d[2] = -up * sinT * cp - uz * omc;
-  }
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    va[k] += P.fa * d[k];
-    vb[k] -= P.fb * d[k];
-  }
-  t[0] += 1.0;
-  if (s2 <= 1.79769313486231570815e308) t[2] += s2; // (an overflowed sigma^2 is counted above 1 and left out of the sum)
-  if (s2 > 1.0) t[3] += 1.0;
+  collide_pair(P.fa, P.fb, cdt, item_state(pairs, p), va, vb, t);
 }
 
 __device__ inline void load_v(const SortDev& s, int i, double* v) { v[0] = s.v[0][i]; v[1] = s.v[1][i]; v[2] = s.v[2][i]; }
