@@ -395,6 +395,34 @@ typedef struct xpic_collision_params {
 } xpic_collision_params;
 int xpic_collide(xpic_ctx* ctx, int sort_a, int sort_b, const xpic_collision_params* p, int64_t step, double out4[4]);
 int xpic_collide_info(xpic_ctx* ctx, int64_t out2[2]);
+/* Binary collisions between two sorts of UNEQUAL weight (Nanbu and Yonemura, J. Comput. Phys. 145, 639, 1998; the density
+ * factor for repeated meetings after Higginson et al., J. Comput. Phys. 413, 109450, 2020).  AN EXTENSION, as xpic_collide
+ * is.  Everything xpic_collide's comment says holds, except the following.
+ * Weights: w_a = n_a / Np_a and w_b = n_b / Np_b may differ; both must be finite and positive.  w_max = max(w_a, w_b) and
+ * r = min(w_a, w_b) / w_max are formed once on the host in fp64 and passed to the kernel; r is never recomputed on the device.
+ * Density factor: n_L = w_max N_short.  (With a the lighter-weighted sort: an a-record is always updated and must see
+ * n_b = w_b N_b over a step; a b-record is updated with probability w_a / w_b per meeting and must see n_a = w_a N_a.  The
+ * long side's record j meets the short side's j mod N_short, so a short record has N_long / N_short meetings: both
+ * conditions give n_L = w_b N_short, whichever side is long.)  At w_a == w_b this is (n / Np) min(N_a, N_b), xpic_collide's
+ * factor, formed by the same operations in the same order.
+ * Pairing and streams: xpic_collide's, the call key of (seed, step, sort_a, sort_b) included.  A fourth draw u4 is taken
+ * from the pair's stream state after u3; a skipped pair (|u| == 0) draws nothing.
+ * Update: the collision is evaluated as written; the lighter-weighted record takes its new velocity; the heavier-weighted
+ * record takes its new velocity iff u4 < r, otherwise its three components keep their bits (r == 1: both are updated at
+ * every meeting, u4 < 1 always; equal weights: sort_b counts as the heavier side).  A rejected update still counts as a
+ * collision made and its sigma^2 is tallied.  When the heavier-weighted side is the short side, each meeting of its record
+ * sees the velocity the meetings before it left, updated or not.
+ * sort_a == sort_b forwards to xpic_collide's path and gives its bits.  Two different sorts of equal weight: the records
+ * and out6[0..3] equal xpic_collide's bit for bit.
+ * out6 = xpic_collide's out4, the heavier-side updates made, the heavier-side updates rejected; all six summed over the
+ * z-slabs.  Equal weights (and sort_a == sort_b): out6[4] == out6[0], out6[5] == 0.
+ * Refused on every slab before anything changes: a bad sort, a null pointer, a negative or non-finite strength, a sort
+ * without mass, Np or positive n.  strength == 0 launches nothing.  xpic_collide_info also reports this call's
+ * second-path cells.
+ * Momentum and energy are conserved in expectation only (w_a . 1 . dp - w_b (w_a / w_b) dp = 0 for a pair); a single
+ * pair does not conserve them, and there is no per-cell repair step. */
+int xpic_collide_weighted(xpic_ctx* ctx, int sort_a, int sort_b, const xpic_collision_params* p, int64_t step,
+  double out6[6]);
 /* SetCoilsField::operator() (src/commands/set_magnetic_field.cpp:38-150): field += the field of the coils {z0, R, I}
  * (coils3[3 i ..]) about the axis (geom_x / 2, geom_y / 2), by the reference's 2000-point quadrature with its
  * denominator_tolerance, at the positions it writes: Bx at (x, y + 1/2, z + 1/2) d, By at (x + 1/2, y, z + 1/2) d,

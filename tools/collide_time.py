@@ -11,7 +11,11 @@ records of a sort), from Context.collide_info, and the sort's occupancy.
 --sorts 1 loads one sort only and times the intra-species call alone (256^3 x 64: two sorts of that size do not fit beside
 the step's buffers).  Prints one JSON object; with --out it is also written to that file.  profiles/collide_time.json is
 the list of such objects: --n 128, and --n 256 --sorts 1.
-usage: collide_time.py [--n 128] [--ppc 64] [--reps 3] [--sorts 2] [--out FILE]"""
+--weighted R times the inter-species call of xpic_collide_weighted ("cmd_collide_weighted") on two sorts whose weights
+are in the ratio R (the second sort's density is R, at the same ppc); at R = 1 the same state also goes through
+xpic_collide ("inter"), the call the weighted one is held against.  profiles/collide_weighted_time.json is the list of
+these objects for R = 1, 0.5 and 0.125.
+usage: collide_time.py [--n 128] [--ppc 64] [--reps 3] [--sorts 2] [--weighted R] [--out FILE]"""
 import argparse
 import json
 import os
@@ -24,12 +28,12 @@ import numpy as np  # noqa: E402
 import xpic_amd as X  # noqa: E402
 
 
-def run(n, ppc, reps, vth, profile, strength, sorts):
+def run(n, ppc, reps, vth, profile, strength, sorts, weighted=None):
     d = 0.5
     ctx = X.Context("ecsim", (n, n, n), (d,) * 3, 1.0, device=0)
     cap = int(ppc * ctx.N * 1.02) + 1024
     a = ctx.add_sort(ppc, 1.0, -1.0, 1.0, capacity=cap)
-    b = ctx.add_sort(ppc, 1.0, 1.0, 100.0, capacity=cap if sorts == 2 else 64)
+    b = ctx.add_sort(ppc, 1.0 if weighted is None else weighted, 1.0, 100.0, capacity=cap if sorts == 2 else 64)
     param = (0.25, n / 16.0) if profile == "blob" else (0.0, 0.0)
     ctx.load_synthetic(a, ppc, vth, seed=1234, profile=profile, param=param)
     if sorts == 2:
@@ -66,9 +70,18 @@ def run(n, ppc, reps, vth, profile, strength, sorts):
         step[0] += 1
         return ctx.collide(sa, sb, strength, step[0], seed=7)
 
-    res["intra"], out = timed("cmd_collide", lambda: collide(a, a), ctx.count(a))
-    res["intra"].update(out)
-    if sorts == 2:
+    def collide_weighted(sa, sb):
+        step[0] += 1
+        return ctx.collide_weighted(sa, sb, strength, step[0], seed=7)
+
+    if weighted is not None:
+        res["weight_ratio"] = weighted
+        res["inter_weighted"], out = timed("cmd_collide_weighted", lambda: collide_weighted(a, b), ctx.count(a) + ctx.count(b))
+        res["inter_weighted"].update(out)
+    else:
+        res["intra"], out = timed("cmd_collide", lambda: collide(a, a), ctx.count(a))
+        res["intra"].update(out)
+    if sorts == 2 and (weighted is None or weighted == 1.0):
         res["inter"], out = timed("cmd_collide", lambda: collide(a, b), ctx.count(a) + ctx.count(b))
         res["inter"].update(out)
     sp, _ = timed("second_push", lambda: ctx.ecsim_second_push(a), ctx.count(a))
@@ -85,10 +98,14 @@ def main():
     ap.add_argument("--vth", type=float, default=0.014)  # bench.py's default
     ap.add_argument("--strength", type=float, default=1e-9)
     ap.add_argument("--sorts", type=int, default=2, choices=(1, 2))
+    ap.add_argument("--weighted", type=float, default=None, metavar="R")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.weighted is not None and args.sorts != 2:
+        ap.error("--weighted needs two sorts")
     res = {"grid": f"{args.n}^3", "ppc": args.ppc, "reps": args.reps, "sorts": args.sorts, "lds_cell": X.COLLIDE_LDS_CELL,
-           "runs": [run(args.n, args.ppc, args.reps, args.vth, p, args.strength, args.sorts) for p in ("poisson", "blob")]}
+           "runs": [run(args.n, args.ppc, args.reps, args.vth, p, args.strength, args.sorts, args.weighted)
+                    for p in (("poisson",) if args.weighted is not None else ("poisson", "blob"))]}
     txt = json.dumps(res, indent=1)
     print(txt)
     if args.out:

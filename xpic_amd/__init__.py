@@ -30,7 +30,7 @@ SYMBOLS = [
     "xpic_ecsimcorr_first_push", "xpic_ecsimcorr_second_push", "xpic_ecsimcorr_final_update",
     "xpic_calculate_energy", "xpic_ecsimcorr_scalars", "xpic_solve", "xpic_set_tolerances", "xpic_set_preconditioner", "xpic_precond_apply", "xpic_precond_get", "xpic_set_overlap", "xpic_comm_stats", "xpic_set_fill_kernel", "xpic_set_fused_rebin", "xpic_get_fill_variant", "xpic_debug_set", "xpic_step",
     "xpic_energy", "xpic_momentum", "xpic_charge_density", "xpic_moment_density", "xpic_moment", "xpic_velocity_distribution", "xpic_remove_particles", "xpic_fields_damping",
-    "xpic_inject_particles", "xpic_collide", "xpic_collide_info", "xpic_set_coils_field", "xpic_set_mirror_field", "xpic_cell_traversal", "xpic_implicit_esirkepov_interpolate",
+    "xpic_inject_particles", "xpic_collide", "xpic_collide_info", "xpic_collide_weighted", "xpic_set_coils_field", "xpic_set_mirror_field", "xpic_cell_traversal", "xpic_implicit_esirkepov_interpolate",
     "xpic_implicit_esirkepov_decompose", "xpic_drift_kinetic_interpolate", "xpic_drift_kinetic_push",
     "xpic_drift_kinetic_trace", "xpic_full_orbit_push", "xpic_full_orbit_trace", "xpic_full_orbit_trace_open",
     "xpic_drift_kinetic_trace_open", "xpic_paired_trace", "xpic_model_fields", "xpic_set_model_field",
@@ -307,6 +307,8 @@ def guiding_centre(points6, B3, mp, qm, *, orbit_centre=False):
 
 _lib = None
 c_dp = C.POINTER(C.c_double)
+# include/xpic_hip.h: int xpic_collide_weighted(xpic_ctx*, int, int, const xpic_collision_params*, int64_t, double[6])
+COLLIDE_WEIGHTED_ARGTYPES = [C.c_void_p, C.c_int, C.c_int, C.POINTER(CollisionParams), C.c_int64, c_dp]
 
 
 def load_library():
@@ -319,6 +321,8 @@ def load_library():
                         "xpic_amd has no CPU fallback")
     L = C.CDLL(LIB_PATH)
     L.xpic_last_error.restype = C.c_char_p
+    L.xpic_collide_weighted.restype = C.c_int
+    L.xpic_collide_weighted.argtypes = COLLIDE_WEIGHTED_ARGTYPES
     if L.xpic_version() & VERSION_EXPERIMENT_BIT and os.environ.get("XPIC_ALLOW_EXPERIMENT") != "1":
         raise XpicError(f"{LIB_PATH} was built with -DXPIC_EXPERIMENT (ablation switches / in-kernel timers: its results "
                         "may be wrong by design); rebuild with `make clean all`, or set XPIC_ALLOW_EXPERIMENT=1 for a "
@@ -719,6 +723,18 @@ class Context:
         o = np.zeros(4)
         self._ck(self.L.xpic_collide(self.h, int(sort_a), int(sort_b), C.byref(p), C.c_int64(int(step)), _dp(o)))
         return dict(pairs=int(o[0]), skipped=int(o[1]), sigma2_sum=float(o[2]), sigma2_over_1=int(o[3]))
+
+    def collide_weighted(self, sort_a, sort_b, strength, step, seed=0, dt=None):
+        """Nanbu-Yonemura binary collisions of sort_a with sort_b, whose weights n / Np may differ (include/xpic_hip.h:
+        xpic_collide_weighted; an extension): the lighter-weighted record of a pair is always updated, the
+        heavier-weighted one with probability w_min / w_max -> Context.collide's dict plus the heavier-side updates made
+        (heavy_updates) and rejected (heavy_rejected), summed over the slabs.  Momentum and energy are conserved in
+        expectation only.  dt: None for the context's."""
+        p = CollisionParams(float(strength), 0.0 if dt is None else float(dt), int(seed))
+        o = np.zeros(6)
+        self._ck(self.L.xpic_collide_weighted(self.h, int(sort_a), int(sort_b), C.byref(p), int(step), _dp(o)))
+        return dict(pairs=int(o[0]), skipped=int(o[1]), sigma2_sum=float(o[2]), sigma2_over_1=int(o[3]),
+                    heavy_updates=int(o[4]), heavy_rejected=int(o[5]))
 
     def collide_info(self):
         """dict of the kernel's LDS-path limit (XPIC_COLLIDE_LDS_CELL as the library was built) and the local cells of

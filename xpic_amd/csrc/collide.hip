@@ -11,12 +11,14 @@
 // (binning scratch: the callers drop the pre-binning anyway, its keys describe the old velocities).
 //
 // Compiled without floating-point contraction: the collision is rounded operation by operation, as numpy rounds it.  The
-// collision itself and the streams are collide_pair.h's, shared with collide_trace.hip.
+// collision itself and the streams are collide_pair.h's, shared with collide_trace.hip; the permutation and the wave-level
+// hand-over are collide_perm.h's, shared with collide_weighted.hip.
 #include <cmath>
 
 #include "common.h"
 #include "device_common.h"
 #include "collide_pair.h"
+#include "collide_perm.h"
 
 #pragma clang fp contract(off)
 
@@ -39,39 +41,6 @@ struct ColDev {
 };
 
 constexpr int kTagPermA = 0, kTagPermB = 1, kTagPairs = 2; // the sub-streams of a cell (collide_pair.h: sub_key)
-
-// what one lane wrote is read by the other lanes of its wave: LDS operations of a wave complete in order, the fence keeps
-// the compiler from moving them; the second path's slots go through global memory
-template <bool LDS>
-__device__ inline void wave_sync()
-{
-  if (LDS) {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-  }
-  else __threadfence();
-}
-
-// slot[rank of record i] = i for the n records of a cell, ordered by (key, i)
-template <bool LDS>
-__device__ inline void permute(uint64_t sub, int n, uint64_t* keys, int* slot, int lane)
-{
-  if (LDS) {
-    for (int i = lane; i < n; i += 64) keys[i] = item_key(sub, i);
-    wave_sync<LDS>();
-  }
-  for (int i = lane; i < n; i += 64) {
-    const uint64_t ki = LDS ? keys[i] : item_key(sub, i);
-    int r = 0;
-    for (int j = 0; j < n; ++j) {
-      const uint64_t kj = LDS ? keys[j] : item_key(sub, j);
-      r += (kj < ki || (kj == ki && j < i)) ? 1 : 0;
-    }
-    slot[r] = i;
-  }
-  wave_sync<LDS>(); // (the slots are read, and the keys rewritten, by other lanes)
-}
 
 // one collision of pair p of the cell's pair stream (collide_pair.h); cdt = c0 n_L dt of this pair
 __device__ inline void collide_pair(const ColDev& P, double cdt, uint64_t pairs, int p, double* va, double* vb, double* t)

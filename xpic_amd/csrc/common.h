@@ -253,7 +253,7 @@ struct xpic_ctx {
   int* cmd_add = nullptr;
   int* cmd_rank = nullptr;
   int64_t cmd_rank_n = 0;
-  int64_t collide_large_cells = 0; // collide.hip: local cells of the last call that took the second path
+  int64_t collide_large_cells = 0; // collide.hip, collide_weighted.hip: local cells of the last call that took the second path
   double rtol = 1e-7, atol = 1e-7;
   int maxit = 100;
   xpic::Comm comm;
@@ -385,6 +385,8 @@ int set_mirror_field(xpic_ctx* c, double* F, double D, double R, double I);
 
 // collide.hip (an extension: the reference has no collision operator)
 int collide(xpic_ctx* c, int sort_a, int sort_b, const xpic_collision_params& p, int64_t step, double* out4);
+// collide_weighted.hip (Nanbu-Yonemura: sorts of unequal weight; sort_a == sort_b forwards to collide)
+int collide_weighted(xpic_ctx* c, int sort_a, int sort_b, const xpic_collision_params& p, int64_t step, double* out6);
 
 // ecsim.hip
 int ecsim_fill_sort(xpic_ctx* c, Sort& s, const double* B, double* currI_sort, double* matL, bool first_sort, bool post_ghost_rows);

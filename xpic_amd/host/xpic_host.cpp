@@ -540,17 +540,20 @@ PetscErrorCode InjectParticles::execute(PetscInt t) // inject_particles.cpp:26-6
 }
 
 BinaryCollisions::BinaryCollisions(interfaces::Simulation& sim, interfaces::Particles& a, interfaces::Particles& b,
-  const xpic_collision_params& params)
-  : sim_(sim), a_(a), b_(b), params_(params)
+  const xpic_collision_params& params, bool weighted)
+  : sim_(sim), a_(a), b_(b), params_(params), weighted_(weighted)
 {
 }
 
 PetscErrorCode BinaryCollisions::execute(PetscInt t) // (an extension: no counterpart in the reference)
 {
-  double out4[4] = {0, 0, 0, 0};
-  HIPCALL(xpic_collide(sim_.ctx, a_.sort_id, b_.sort_id, &params_, t, out4));
-  LOG("  Binary collisions \"" << a_.parameters.sort_name << "\" - \"" << b_.parameters.sort_name << "\": " << (long)out4[0]
-    << " pairs, mean sigma^2 " << (out4[0] > 0 ? out4[2] / out4[0] : 0.0) << ", " << (long)out4[3] << " above 1");
+  double out6[6] = {0, 0, 0, 0, 0, 0};
+  if (weighted_) HIPCALL(xpic_collide_weighted(sim_.ctx, a_.sort_id, b_.sort_id, &params_, t, out6));
+  else HIPCALL(xpic_collide(sim_.ctx, a_.sort_id, b_.sort_id, &params_, t, out6));
+  LOG("  Binary collisions" << (weighted_ ? " (weighted)" : "") << " \"" << a_.parameters.sort_name << "\" - \""
+    << b_.parameters.sort_name << "\": " << (long)out6[0] << " pairs, mean sigma^2 " << (out6[0] > 0 ? out6[2] / out6[0] : 0.0)
+    << ", " << (long)out6[3] << " above 1");
+  if (weighted_) LOG("    heavier-side updates: " << (long)out6[4] << " made, " << (long)out6[5] << " rejected");
   return 0;
 }
 
@@ -750,8 +753,10 @@ PetscErrorCode build_commands(interfaces::Simulation& simulation, const std::str
           throw std::runtime_error("BinaryCollisions: \"seed\" must be a whole number in [0, 2^53]");
         p.seed = (uint64_t)sd;
       }
-      result.emplace_back(std::make_unique<BinaryCollisions>(simulation, a, b, p));
-      LOG("  BinaryCollisions command is added for \"" << na << "\" and \"" << nb << "\", strength " << p.strength);
+      const bool weighted = info.contains("weighted") && info.at("weighted").as_bool();
+      result.emplace_back(std::make_unique<BinaryCollisions>(simulation, a, b, p, weighted));
+      LOG("  BinaryCollisions command is added for \"" << na << "\" and \"" << nb << "\", strength " << p.strength
+        << (weighted ? ", weighted path (xpic_collide_weighted)" : ", equal-weight path (xpic_collide)"));
     }
     else throw std::runtime_error("Unknown command name " + command);
   }

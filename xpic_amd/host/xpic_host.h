@@ -291,17 +291,20 @@ private:
 // "strength": S, "seed": ...}; one name (or the same name twice) collides a sort with itself.  "seed" is a JSON number
 // (the reader holds numbers as doubles: whole values up to 2^53; a larger or fractional one is refused); without it the
 // seed is the command's place in its list, so two commands draw different streams and reordering the list changes them:
-// give seeds to keep the streams of a run whose presets are rearranged.
+// give seeds to keep the streams of a run whose presets are rearranged.  "weighted": true (optional, default false) calls
+// xpic_collide_weighted (Nanbu-Yonemura), which accepts two sorts of different weight n / Np; without it the command is
+// xpic_collide and refuses such a pair.
 class BinaryCollisions : public interfaces::Command {
 public:
   BinaryCollisions(interfaces::Simulation& sim, interfaces::Particles& a, interfaces::Particles& b,
-    const xpic_collision_params& params);
+    const xpic_collision_params& params, bool weighted);
   PetscErrorCode execute(PetscInt t) override;
 
 private:
   interfaces::Simulation& sim_;
   interfaces::Particles &a_, &b_;
   xpic_collision_params params_;
+  bool weighted_;
 };
 
 PetscErrorCode build_commands(interfaces::Simulation& simulation, const std::string& name,
