@@ -444,7 +444,16 @@ int xpic_charge_columns(xpic_ctx* ctx, double* out);
 /* ---- inner kernels of the `eccapfim` scheme, batch form over n path segments r0 -> rn (host arrays,
  * 3 doubles per point).  The scheme's outer loops are not part of this library.
  * cell_traversal (src/impls/eccapfim/cell_traversal.cpp:3-77): for every segment the points start, face crossings of the
- * node-centred cells, end -> pts[(q * max_pts + i) * 3 ..], counts[q] (may exceed max_pts: then the tail is dropped). */
+ * node-centred cells, end -> pts[(q * max_pts + i) * 3 ..], counts[q] (may exceed max_pts: then the tail is dropped and
+ * counts[q] is still the full count; pts behind the points of a segment is zero).  The points are the reference's bit for
+ * bit (the kernel is compiled without contraction).  A guard the reference does not have: after 64 crossings the walk
+ * stops and the end is appended, so counts[q] <= 66, and counts[q] == 66 marks a walk cut short.  That is a move of more
+ * than 64 crossings, or one of the exact ties on which the reference's ladder (z before y before x) steps an axis whose
+ * end coordinate lies on a face and rounds back into its cell, and never returns; the points of such a walk run on past
+ * the end.
+ * These three calls are single-slab calls (nranks == 1, no self_ring): there every node index is folded into the box on
+ * all three axes, so positions may lie any distance outside it.  On a z-slab of several the z index is not folded and
+ * positions are not checked against the ghost planes. */
 int xpic_cell_traversal(xpic_ctx* ctx, int64_t n, const double* end3, const double* start3, int max_pts, double* pts,
   int* counts);
 /* ImplicitEsirkepov::interpolate (src/algorithms/implicit_esirkepov.cpp:60-90): E_p with the segment's 54-weight shape,

@@ -284,6 +284,13 @@ struct Grid {
     return (((long)(z + ST) * g[1] + (y + ST)) * g[0] + (x + ST)) * 3 + c;
   }
   long sl(int x, int y, int z) const { return ((long)(z + ST) * g[1] + (y + ST)) * g[0] + (x + ST); }
+  /* vl() for any node: within the ghost width the element the reference addresses, beyond it (where the reference's
+   * local array ends) the owned node it folds onto, which holds the same value after global_to_local and is added to
+   * the same global node by local_to_global_add */
+  long vlw(int x, int y, int z, int c) const
+  {
+    return inside_ghost(x, y, z) ? vl(x, y, z, c) : vl(wrap(x, n[0]), wrap(y, n[1]), wrap(z, n[2]), c);
+  }
   bool inside_ghost(int x, int y, int z) const
   {
     return x >= -ST && x < n[0] + ST && y >= -ST && y < n[1] + ST && z >= -ST && z < n[2] + ST;
@@ -1861,10 +1868,16 @@ void orc_implicit_esirkepov_interpolate(orc_sim* s, long n, const double* rn3, c
     Shape sh_m;
     V3 mid(0.5 * (rn[X] + r0[X]), 0.5 * (rn[Y] + r0[Y]), 0.5 * (rn[Z] + r0[Z]));
     sh_m.setup(gr.d, mid, 1.5, spline_of(2)); /* shape_radius / shape_function, sort_parameters.h:44-46 */
-    simple_interpolation(gr, sh_m, nullptr, Bl.data(), none, B_p);
+    for (int i = 0; i < sh_m.elements(); ++i) { /* SimpleInterpolation::process, B only, any distance from the box */
+      int g_x = sh_m.start[X] + i % sh_m.size[X];
+      int g_y = sh_m.start[Y] + (i / sh_m.size[X]) % sh_m.size[Y];
+      int g_z = sh_m.start[Z] + (i / sh_m.size[X]) / sh_m.size[Y];
+      V3 sm = sh_m.magnetic(i);
+      for (int c = 0; c < 3; ++c) B_p[c] += Bl[gr.vlw(g_x, g_y, g_z, c)] * sm[c];
+    }
     ImplicitShape sh_e;
     sh_e.setup(gr.d, rn, r0);
-    sh_e.for_each([&](int gx, int gy, int gz, int c, double w) { E_p[c] += El[gr.vl(gx, gy, gz, c)] * w; });
+    sh_e.for_each([&](int gx, int gy, int gz, int c, double w) { E_p[c] += El[gr.vlw(gx, gy, gz, c)] * w; });
     for (int c = 0; c < 3; ++c) { Ep3[3 * q + c] = E_p[c]; Bp3[3 * q + c] = B_p[c]; }
   }
 }
@@ -1880,7 +1893,7 @@ int orc_implicit_esirkepov_decompose(orc_sim* s, long n, const double* alpha, co
   for (long q = 0; q < n; ++q) {
     ImplicitShape sh_e;
     sh_e.setup(gr.d, V3(rn3 + 3 * q), V3(r03 + 3 * q));
-    sh_e.for_each([&](int gx, int gy, int gz, int c, double w) { Jl[gr.vl(gx, gy, gz, c)] += alpha[q] * v3[3 * q + c] * w; });
+    sh_e.for_each([&](int gx, int gy, int gz, int c, double w) { Jl[gr.vlw(gx, gy, gz, c)] += alpha[q] * v3[3 * q + c] * w; });
   }
   local_to_global_add(gr, Jl, *F, 3);
   return 0;

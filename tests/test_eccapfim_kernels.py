@@ -4,31 +4,16 @@ The reference's only fixture for this scheme is the `eccapfim_ex1` integration r
 Crank-Nicolson scheme: these kernels alone are **parity unpinned** against reference outputs.  What pins them here is
 physics they must satisfy together with an already pinned kernel: the current deposited segment by segment obeys the
 discrete continuity equation with the 2nd-order charge density of ChargeConservation (pinned by the golden
-charge_conservation tables) to round-off, and the segments of cell_traversal tile the path exactly."""
+charge_conservation tables) to round-off, and the segments of cell_traversal tile the path exactly.
+tests/eccapfim_ref.py restates the kernels in float64 on its own; tests/test_eccapfim_ref.py and
+tests/test_gpu_eccapfim.py hold the oracle and the device to it at the edges (wrap, folding stencils, ties, long and
+degenerate moves)."""
 import numpy as np
 import pytest
 
+from eccapfim_ref import random_moves, segments
+
 N, D, DT = (9, 8, 7), (0.5, 0.4, 0.3), 0.7
-
-
-def random_moves(rng, n, max_cells=1.4):
-    L = np.array(N) * np.array(D)
-    r0 = rng.random((n, 3)) * L * 0.6 + L * 0.2
-    rn = r0 + (rng.random((n, 3)) * 2 - 1) * max_cells * np.array(D)
-    return rn, r0
-
-
-def segments(traverse, rn, r0):
-    """[(segment end, segment start, fraction of the path)] per move, from cell_traversal's points."""
-    out = []
-    for q in range(rn.shape[0]):
-        pts, cnt = traverse(rn[q], r0[q])
-        assert cnt == len(pts)
-        d = np.linalg.norm(rn[q] - r0[q])
-        for s in range(1, cnt):
-            ds = np.linalg.norm(pts[s] - pts[s - 1])
-            out.append((q, pts[s], pts[s - 1], ds / d if d > 0 else 1.0))
-    return out
 
 
 def test_oracle_cell_traversal_tiles_the_path(oracle):

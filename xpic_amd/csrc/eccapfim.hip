@@ -5,7 +5,9 @@
 //   ImplicitEsirkepov::interpolate     :60-90   (E with the segment shape, B with Shape(midpoint) + SimpleInterpolation)
 //   ImplicitEsirkepov::decompose       :92-117
 // One lane per segment, the host arrays staged through batch.h.  The scheme's outer loops (Crank-Nicolson sub-stepping,
-// SNES) are not part of this build.
+// SNES) are not part of this build.  The three entry points are single-slab calls: with G == 0 ie_node folds every index
+// on all three axes; on a z-slab of several it does not fold z and nothing checks a position against the ghost planes.
+// Held to tests/eccapfim_ref.py by tests/test_gpu_eccapfim.py.
 #include <cfloat>
 
 #include "batch.h"
@@ -96,6 +98,11 @@ __global__ void __launch_bounds__(kBlock) k_ie_decompose(GridDev g, double* J, l
 __global__ void __launch_bounds__(kBlock) k_cell_traversal(GridDev g, long n, const double* end3, const double* start3,
   int max_pts, double* pts, int* counts)
 {
+  // Compiled without contraction, as device_common.h's within(): a fused (curr + sg / 2) * d - st moves a crossing
+  // parameter by ulp(face) / 2 / dir[c], which the other axes see magnified by dir[c'] / dir[c] in start + dir * t, and
+  // it may order two near crossings differently from the reference's ladder.  Rounded step by step the points are the
+  // reference's bit for bit.
+#pragma clang fp contract(off)
   const long q = (long)blockIdx.x * kBlock + threadIdx.x;
   if (q >= n) return;
   const double d[3] = {g.dx, g.dy, g.dz};
