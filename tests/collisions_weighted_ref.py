@@ -1,6 +1,6 @@
 """Binary collisions between two sorts of unequal weight (Nanbu and Yonemura, J. Comput. Phys. 145, 639, 1998) restated in
 numpy float64: the second statement of include/xpic_hip.h: xpic_collide_weighted, which
-xpic_amd/csrc/collide_weighted.hip is held to.  An extension: the reference has no collision operator.
+xpic_amd/csrc/collide.hip is held to.  An extension: the reference has no collision operator.
 
 The streams, the cell layout, the inter-species pairing and the pair collision are tests/collisions_ref.py's, imported
 and used as they stand.  Stated here: the density factor n_L = w_max N_short, the fourth draw u4 from the pair's stream

@@ -1,5 +1,5 @@
 """Binary collisions between sorts of unequal weight on the GPU (xpic_collide_weighted,
-xpic_amd/csrc/collide_weighted.hip) against tests/collisions_weighted_ref.py on the same records: parity and identical
+xpic_amd/csrc/collide.hip) against tests/collisions_weighted_ref.py on the same records: parity and identical
 update decisions on hand-populated cells, xpic_collide's bits at equal weights, determinism, refusals, three z-slabs, the
 relaxation rate whichever side carries the heavy weight, the weighted sums in expectation, and the host executable.  An
 extension: the reference has no collision operator; the restatement is the second statement of the definition."""

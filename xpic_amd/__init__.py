@@ -719,10 +719,14 @@ class Context:
         (include/xpic_hip.h: xpic_collide; an extension, the reference has no collision operator) -> dict of the pairs
         collided, the pairs skipped (|u| == 0), the sum of sigma^2 over the collided pairs and the pairs with
         sigma^2 > 1, summed over the slabs.  dt: None for the context's."""
+        return self._collide(self.L.xpic_collide, sort_a, sort_b, strength, C.c_int64(int(step)), seed, dt, 4)[0]
+
+    def _collide(self, entry, sort_a, sort_b, strength, step, seed, dt, counters):
+        """xpic_collide or xpic_collide_weighted -> (Context.collide's dict, the entry point's counters)"""
         p = CollisionParams(float(strength), 0.0 if dt is None else float(dt), int(seed))
-        o = np.zeros(4)
-        self._ck(self.L.xpic_collide(self.h, int(sort_a), int(sort_b), C.byref(p), C.c_int64(int(step)), _dp(o)))
-        return dict(pairs=int(o[0]), skipped=int(o[1]), sigma2_sum=float(o[2]), sigma2_over_1=int(o[3]))
+        o = np.zeros(counters)
+        self._ck(entry(self.h, int(sort_a), int(sort_b), C.byref(p), step, _dp(o)))
+        return dict(pairs=int(o[0]), skipped=int(o[1]), sigma2_sum=float(o[2]), sigma2_over_1=int(o[3])), o
 
     def collide_weighted(self, sort_a, sort_b, strength, step, seed=0, dt=None):
         """Nanbu-Yonemura binary collisions of sort_a with sort_b, whose weights n / Np may differ (include/xpic_hip.h:
@@ -730,11 +734,8 @@ class Context:
         heavier-weighted one with probability w_min / w_max -> Context.collide's dict plus the heavier-side updates made
         (heavy_updates) and rejected (heavy_rejected), summed over the slabs.  Momentum and energy are conserved in
         expectation only.  dt: None for the context's."""
-        p = CollisionParams(float(strength), 0.0 if dt is None else float(dt), int(seed))
-        o = np.zeros(6)
-        self._ck(self.L.xpic_collide_weighted(self.h, int(sort_a), int(sort_b), C.byref(p), int(step), _dp(o)))
-        return dict(pairs=int(o[0]), skipped=int(o[1]), sigma2_sum=float(o[2]), sigma2_over_1=int(o[3]),
-                    heavy_updates=int(o[4]), heavy_rejected=int(o[5]))
+        out, o = self._collide(self.L.xpic_collide_weighted, sort_a, sort_b, strength, int(step), seed, dt, 6)
+        return dict(out, heavy_updates=int(o[4]), heavy_rejected=int(o[5]))
 
     def collide_info(self):
         """dict of the kernel's LDS-path limit (XPIC_COLLIDE_LDS_CELL as the library was built) and the local cells of

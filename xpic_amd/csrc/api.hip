@@ -982,15 +982,15 @@ int xpic_collide(xpic_ctx* ctx, int sort_a, int sort_b, const xpic_collision_par
   CTX_CHECK(ctx);
   SORT_CHECK(sort_a); SORT_CHECK(sort_b);
   XPIC_CHECK(p && out4, "null argument");
-  return collide(ctx, sort_a, sort_b, *p, step, out4);
+  return collide(ctx, sort_a, sort_b, *p, step, false, out4);
 }
 
 int xpic_collide_weighted(xpic_ctx* ctx, int sort_a, int sort_b, const xpic_collision_params* p, int64_t step, double out6[6])
-{ // Nanbu-Yonemura collisions between sorts of unequal weight (collide_weighted.hip): an extension, as xpic_collide
+{ // Nanbu-Yonemura collisions between sorts of unequal weight (collide.hip): an extension, as xpic_collide
   CTX_CHECK(ctx);
   SORT_CHECK(sort_a); SORT_CHECK(sort_b);
   XPIC_CHECK(p && out6, "null argument");
-  return collide_weighted(ctx, sort_a, sort_b, *p, step, out6);
+  return collide(ctx, sort_a, sort_b, *p, step, true, out6);
 }
 
 int xpic_collide_info(xpic_ctx* ctx, int64_t out2[2])

@@ -1,12 +1,13 @@
 // collide_pair.h -- one Takizuka-Abe collision (J. Comput. Phys. 25, 205, 1977) as a device function, and the streams its
-// draws come from: shared by collide.hip (the records of a cell against each other, include/xpic_hip.h: xpic_collide) and
-// collide_trace.hip (a test particle against a partner drawn from a Maxwellian background, xpic_trace_collisions).  AN
-// EXTENSION: the reference has no collision operator.  tests/collisions_ref.py and tests/collisional_trace_ref.py state
-// the same text and the same constants a second time in numpy float64.
+// draws come from: shared by collide.hip (the records of a cell against each other, include/xpic_hip.h: xpic_collide and
+// xpic_collide_weighted) and collide_trace.hip (a test particle against a partner drawn from a Maxwellian background,
+// xpic_trace_collisions).  AN EXTENSION: the reference has no collision operator.  tests/collisions_ref.py and
+// tests/collisional_trace_ref.py state the same text and the same constants a second time in numpy float64.
 //
 // The including files differ in their floating-point contraction (collide.hip: off, the tracers: on), so every function
 // here that rounds carries `#pragma clang fp contract(off)` in its body: the collision is rounded operation by operation,
-// as numpy rounds it, wherever it is included.  Included after device_common.h.  Device code only.
+// as numpy rounds it, wherever it is included.  Included after device_common.h.  Device code, but for the keys the host
+// forms (trace_step_key, call_key).
 #pragma once
 
 #include <cmath>
@@ -44,6 +45,14 @@ __host__ __device__ inline uint64_t trace_step_key(uint64_t seed, long long k)
   uint64_t key = seed;
   (void)splitmix(key);
   key ^= (uint64_t)k * 0xD1342543DE82EF95ull;
+  return splitmix(key);
+}
+// xpic_collide's call key, the stream of (seed, step, sort_a, sort_b): the step key, xor the packed sort pair * constant,
+// splitmix
+__host__ inline uint64_t call_key(uint64_t seed, int64_t step, int ia, int ib)
+{
+  uint64_t key = trace_step_key(seed, step);
+  key ^= (((uint64_t)(uint32_t)ia << 32) | (uint64_t)(uint32_t)ib) * 0x9FB21C651E98DF25ull;
   return splitmix(key);
 }
 __device__ inline uint64_t trace_stream(uint64_t step_key, long long particle, int b)

@@ -253,7 +253,7 @@ struct xpic_ctx {
   int* cmd_add = nullptr;
   int* cmd_rank = nullptr;
   int64_t cmd_rank_n = 0;
-  int64_t collide_large_cells = 0; // collide.hip, collide_weighted.hip: local cells of the last call that took the second path
+  int64_t collide_large_cells = 0; // collide.hip: local cells of the last call that took the second path
   double rtol = 1e-7, atol = 1e-7;
   int maxit = 100;
   xpic::Comm comm;
@@ -383,10 +383,9 @@ int inject_particles(xpic_ctx* c, Sort& si, Sort& se, const xpic_inject_params& 
 int set_coils_field(xpic_ctx* c, double* F, int ncoils, const double* coils3);
 int set_mirror_field(xpic_ctx* c, double* F, double D, double R, double I);
 
-// collide.hip (an extension: the reference has no collision operator)
-int collide(xpic_ctx* c, int sort_a, int sort_b, const xpic_collision_params& p, int64_t step, double* out4);
-// collide_weighted.hip (Nanbu-Yonemura: sorts of unequal weight; sort_a == sort_b forwards to collide)
-int collide_weighted(xpic_ctx* c, int sort_a, int sort_b, const xpic_collision_params& p, int64_t step, double* out6);
+// collide.hip (an extension: the reference has no collision operator): xpic_collide (weighted false, out[4]) and
+// xpic_collide_weighted (Nanbu-Yonemura: sorts of unequal weight; out[6]; sort_a == sort_b takes the unweighted path)
+int collide(xpic_ctx* c, int sort_a, int sort_b, const xpic_collision_params& p, int64_t step, bool weighted, double* out);
 
 // ecsim.hip
 int ecsim_fill_sort(xpic_ctx* c, Sort& s, const double* B, double* currI_sort, double* matL, bool first_sort, bool post_ghost_rows);
