@@ -719,8 +719,8 @@ int xpic_envelope_factors(xpic_ctx* ctx, const xpic_field_envelope* envelope, do
  * test particles off Maxwellian background species, by xpic_collide's pair collision (Takizuka and Abe).  AN EXTENSION, as
  * xpic_collide is: the reference has no collision operator, so no file:line of it is cited.  Everything that is not said
  * here is the model traces': region semantics with XPIC_GEOM_NONE, samples, counters, checks, launches of at most
- * XPIC_MODEL_LAUNCH_STEPS steps, any context.  The envelope traces, the grid traces and the paired and triplet traces have
- * no collisional form.
+ * XPIC_MODEL_LAUNCH_STEPS steps, any context.  The grid traces' collisional form follows below
+ * (xpic_full_orbit_trace_collisional); the envelope traces and the paired and triplet traces have none.
  * When: after the push of step k and before that step's sample is stored, where k = region->step0 + the steps this call
  * has completed + 1 is the step's global index; the step collides iff k % every == 0, with dt_c = every * dt (dt is
  * params->dt), against the backgrounds b = 0 .. nbg - 1 in this order.  A removed particle collides no more.
@@ -772,6 +772,63 @@ int xpic_model_drift_kinetic_trace_collisional(xpic_ctx* ctx, int64_t n, const x
   const xpic_field_model* model, int64_t steps, int64_t sample_every, double* state_6, double* samples,
   int64_t* iterations_total, int* iterations_max, const xpic_trace_region* region, int64_t* exit_step, int64_t* alive,
   int64_t* removed, const xpic_trace_collisions* collisions, double* coll_4);
+
+/* ---- background profiles: a spatially resolved background species for the collisional grid traces below.  AN EXTENSION,
+ * as the collision operator is.  A profile holds five doubles per local cell, in the cell order of the cell-sorted sorts
+ * (x fastest, then y, then z): a density n, a thermal speed per component vth, a drift u[3].  The context owns
+ * XPIC_TRACE_BG_MAX slots.  Single z-slab contexts only, as the grid tracers; other contexts are refused.
+ * xpic_background_set uploads host arrays n_zyx [nz][ny][nx], vth_zyx [nz][ny][nx] and drift_zyx3 [nz][ny][nx][3] (NULL:
+ * no drift).  Refused, the slot left as it was: a slot outside 0 .. XPIC_TRACE_BG_MAX - 1, a NULL n or vth, a negative or
+ * non-finite n or vth, a non-finite drift.  xpic_background_get downloads a slot (any output may be NULL; an empty slot
+ * is refused), xpic_background_clear empties one.
+ * xpic_background_from_sort fills the slot on the device from the records of a sort, cell by cell; N = the cell's records:
+ *   n   = (sort.n / sort.Np) N          xpic_collide's n_L: a tracer sees the density the sort's own collisions see
+ *   u   = (sum v) / N
+ *   vth = sqrt(sum |v - u|^2 / (3 N))   two passes, |d|^2 = (dx dx + dy dy) + dz dz
+ * An empty cell gives zeros, a cell of one record vth = 0.  Every sum is taken in a fixed order (lane l of a wave adds the
+ * records l, l + 64, ... of the cell in cell order, the 64 partial sums are folded by halves), rounded operation by
+ * operation: two calls give the same bits.  The records are not changed: the sort and a following xpic_collide are
+ * what they would have been.  (A deferred re-binning of the sort is completed first, as xpic_sort_get_particles and
+ * xpic_collide complete it.) */
+int xpic_background_set(xpic_ctx* ctx, int slot, const double* n_zyx, const double* vth_zyx, const double* drift_zyx3);
+int xpic_background_get(xpic_ctx* ctx, int slot, double* n_zyx, double* vth_zyx, double* drift_zyx3);
+int xpic_background_clear(xpic_ctx* ctx, int slot);
+int xpic_background_from_sort(xpic_ctx* ctx, int slot, int sort);
+
+/* ---- collisional grid traces: xpic_full_orbit_trace_open and xpic_drift_kinetic_trace_open with the collisions of the
+ * collisional traces above, off uniform backgrounds or off the context's background profiles: test particles traced
+ * through the fields of a run while they scatter off the plasma of that run.  AN EXTENSION.  The argument lists are the
+ * open grid traces' with three more: collisions, profile, coll_4.  Everything xpic_trace_collisions says above holds --
+ * when a step collides, every, seed, particle0, the streams and their seven draws, the partner, the guiding centre's
+ * gyrophase and basis, the tallies -- and everything else is the open grid traces': samples, counters, exit_step, alive,
+ * removed, launches of at most XPIC_FO_LAUNCH_STEPS / XPIC_DK_LAUNCH_STEPS steps, `compact`.  region->geometry may be
+ * XPIC_GEOM_NONE as in the model traces: the closed trace; exit_step, alive and removed may then be NULL.
+ * profile: NULL, or collisions->nbg entries.  Entry -1 (and NULL): background b is the uniform one of the struct.  Entry
+ * s >= 0: background b takes n, vth and drift from slot s at the cell of the particle's pushed position, floor(r / d) per
+ * axis folded onto the grid by the true modulus (positions are not folded in the traces); piecewise constant, nothing is
+ * interpolated.  The struct's q and m are used, its n, vth and drift ignored.  sigma^2's factor is formed on the device as
+ * defined above, ((S (q_a q_a) (q_b q_b) / (m_ab m_ab)) n_L) dt_c, rounded operation by operation.  A cell with n == 0
+ * makes no collision for that background: nothing is drawn, the record keeps its bits and neither tally moves.  A position
+ * that is not a number, or further than 1e9 cells out, has no cell and meets no profile.
+ * Guiding centre: B is what xpic_drift_kinetic_interpolate returns for the segment (r, r) at the pushed position r; with
+ * |B| == 0 the skipped tally counts the backgrounds that have somebody to meet there.
+ * Refused before anything changes: what the open grid traces and the collisional traces refuse, a profile entry outside
+ * -1 .. XPIC_TRACE_BG_MAX - 1, a named slot that is empty, a context that is not a single slab.
+ * Guarantees, bit for bit: (a) collisions == NULL, nbg == 0 or strength == 0 is the grid trace, open or (XPIC_GEOM_NONE)
+ * closed -- state, samples, counters, exit_step, alive, removed -- and coll_4 is zeros; (b) a call of s1 + s2 steps equals
+ * a call of s1 steps followed by one of s2 steps with step0 advanced by s1 and the first call's exit_step; (c) a batch
+ * split in two, the second part with particle0 advanced by the first part's size, gives the bits of the whole batch (the
+ * float tally coll_4[2] to rounding); (d) the three values of `compact` give the same bits; (e) a profile that holds the
+ * struct's n (> 0), vth and drift in every cell gives the bits of profile == NULL; (f) xpic_background_from_sort leaves the
+ * sort's records and xpic_collide's results unchanged. */
+int xpic_full_orbit_trace_collisional(xpic_ctx* ctx, int64_t n, const xpic_fo_params* params, int64_t steps,
+  int64_t sample_every, double* p_6, double* samples, int64_t* iterations_sum, int* iterations_max,
+  const xpic_trace_region* region, int64_t* exit_step, int64_t* alive, int64_t* removed,
+  const xpic_trace_collisions* collisions, const int32_t* profile, double* coll_4);
+int xpic_drift_kinetic_trace_collisional(xpic_ctx* ctx, int64_t n, const xpic_dk_params* params, int gradB_field,
+  int64_t steps, int64_t sample_every, double* state_6, double* samples, int64_t* iterations_total, int* iterations_max,
+  const xpic_trace_region* region, int64_t* exit_step, int64_t* alive, int64_t* removed,
+  const xpic_trace_collisions* collisions, const int32_t* profile, double* coll_4);
 
 /* ---- triplet trace: the whole time loop of the reference's grid tests
  * (tests/drift_kinetic_push/drift_kinetic_grid_boris_ex1..4.cpp, ex1.cpp:79-98) for n triplets, with all seven maxima of

@@ -36,7 +36,8 @@ SYMBOLS = [
     "xpic_drift_kinetic_trace_open", "xpic_paired_trace", "xpic_model_fields", "xpic_set_model_field",
     "xpic_model_full_orbit_trace", "xpic_model_drift_kinetic_trace", "xpic_model_full_orbit_trace_timed",
     "xpic_model_drift_kinetic_trace_timed", "xpic_envelope_factors", "xpic_model_full_orbit_trace_collisional",
-    "xpic_model_drift_kinetic_trace_collisional", "xpic_triplet_trace", "xpic_charge_collect", "xpic_charge_columns", "xpic_comm_rccl_unique_id", "xpic_comm_init_rccl", "xpic_comm_init_callbacks", "xpic_comm_size", "xpic_comm_peer_export", "xpic_comm_peer_import",
+    "xpic_model_drift_kinetic_trace_collisional", "xpic_background_set", "xpic_background_get", "xpic_background_clear",
+    "xpic_background_from_sort", "xpic_full_orbit_trace_collisional", "xpic_drift_kinetic_trace_collisional", "xpic_triplet_trace", "xpic_charge_collect", "xpic_charge_columns", "xpic_comm_rccl_unique_id", "xpic_comm_init_rccl", "xpic_comm_init_callbacks", "xpic_comm_size", "xpic_comm_peer_export", "xpic_comm_peer_import",
     "xpic_profile_enable", "xpic_profile_reset", "xpic_profile_get", "xpic_probe_copy_bandwidth",
 ]
 
@@ -1021,6 +1022,72 @@ class Context:
         return CollisionalTrace(*self._model_trace(
             self.L.xpic_model_drift_kinetic_trace_collisional, self._dk_params(qm, mp, dt, eps, delta, maxit), state, steps,
             model, region, sample_every, exit_step, step0, keep_samples, collisions=collisions))
+
+    # ---- background profiles and the collisional grid traces (include/xpic_hip.h: xpic_background_set,
+    # xpic_full_orbit_trace_collisional): the open grid traces with the collisions of the collisional traces, off uniform
+    # backgrounds or off the context's profiles.  A profile is n [nz][ny][nx], vth [nz][ny][nx], drift [nz][ny][nx][3]
+    def _cells(self):
+        return tuple(int(v) for v in self.fshape()[:3])
+
+    def background_set(self, slot, n, vth, drift=None):
+        """uploads a profile into `slot`; drift None: at rest"""
+        shape = self._cells()
+        n = np.ascontiguousarray(np.broadcast_to(np.asarray(n, dtype=np.float64), shape))
+        vth = np.ascontiguousarray(np.broadcast_to(np.asarray(vth, dtype=np.float64), shape))
+        if drift is not None:
+            drift = np.ascontiguousarray(np.broadcast_to(np.asarray(drift, dtype=np.float64), shape + (3,)))
+        self._ck(self.L.xpic_background_set(self.h, int(slot), _dp(n), _dp(vth), None if drift is None else _dp(drift)))
+
+    def background_get(self, slot):
+        """-> (n, vth, drift) of a slot; an empty slot raises"""
+        shape = self._cells()
+        n, vth, drift = np.zeros(shape), np.zeros(shape), np.zeros(shape + (3,))
+        self._ck(self.L.xpic_background_get(self.h, int(slot), _dp(n), _dp(vth), _dp(drift)))
+        return n, vth, drift
+
+    def background_clear(self, slot):
+        self._ck(self.L.xpic_background_clear(self.h, int(slot)))
+
+    def background_from_sort(self, slot, sort):
+        """fills `slot` on the device from the sort's records, cell by cell: n = (n / Np) N, u = <v>,
+        vth = sqrt(<|v - u|^2> / 3); the records are not changed"""
+        self._ck(self.L.xpic_background_from_sort(self.h, int(slot), int(sort)))
+
+    def _grid_trace_collisional(self, fn, P, middle, state, steps, collisions, profile, region, sample_every, exit_step,
+                                step0, compact, keep_samples):
+        """the ctypes call of the collisional grid traces -> the fields of CollisionalTrace.  middle: fn's arguments
+        between params and steps; profile: a list of slots (-1: the uniform background of `collisions`) or None"""
+        state, samples, alive, ex, reg, tot, mx = self._open_args(state, steps, sample_every, region, exit_step, step0, compact,
+                                                                      keep_samples)
+        removed, i64 = C.c_int64(), C.POINTER(C.c_int64)
+        bare = region is None and exit_step is None  # the closed trace: the library gets no exit_step and no removed
+        prof = None if profile is None else (C.c_int32 * len(profile))(*[int(s) for s in profile])
+        if prof is not None and collisions is not None and len(profile) != collisions.nbg:
+            raise XpicError("profile: one entry per background")
+        coll = np.zeros(4)
+        self._ck(fn(self.h, C.c_int64(state.shape[0]), C.byref(P), *middle, C.c_int64(int(steps)),
+                    C.c_int64(int(sample_every)), _dp(state), None if samples is None else _dp(samples),
+                    tot.ctypes.data_as(i64), mx.ctypes.data_as(C.POINTER(C.c_int)), C.byref(reg),
+                    None if bare else ex.ctypes.data_as(i64), alive.ctypes.data_as(i64) if sample_every else None,
+                    None if bare else C.byref(removed), None if collisions is None else C.byref(collisions), prof, _dp(coll)))
+        return CollisionalTrace(state, samples, ex, alive, removed.value, tot, mx, coll)
+
+    def full_orbit_trace_collisional(self, state, steps, scheme, qm, dt, collisions, profile=None, region=None,
+                                     sample_every=0, exit_step=None, step0=0, compact="never", keep_samples=True, atol=1e-7,
+                                     rtol=1e-7, maxit=30):
+        """full_orbit_trace_open (region None: full_orbit_trace) with collisions -> CollisionalTrace"""
+        return self._grid_trace_collisional(
+            self.L.xpic_full_orbit_trace_collisional, self._fo_params(scheme, qm, dt, atol, rtol, maxit), [], state, steps,
+            collisions, profile, region, sample_every, exit_step, step0, compact, keep_samples)
+
+    def drift_kinetic_trace_collisional(self, state, steps, qm, mp, dt, collisions, profile=None, region=None,
+                                        gradB_field=None, sample_every=0, exit_step=None, step0=0, compact="never",
+                                        keep_samples=True, eps=1e-12, delta=1e-12, maxit=30):
+        """drift_kinetic_trace_open (region None: drift_kinetic_trace) with collisions -> CollisionalTrace"""
+        return self._grid_trace_collisional(
+            self.L.xpic_drift_kinetic_trace_collisional, self._dk_params(qm, mp, dt, eps, delta, maxit),
+            [-1 if gradB_field is None else int(gradB_field)], state, steps, collisions, profile, region, sample_every,
+            exit_step, step0, compact, keep_samples)
 
     def envelope_factors(self, envelope, dt, step0, nsteps):
         """-> the factors of steps step0 .. step0 + nsteps - 1, evaluated on the device as the traces evaluate them"""

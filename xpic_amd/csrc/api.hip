@@ -408,6 +408,7 @@ int xpic_destroy(xpic_ctx* ctx)
   (void)hipFree(ctx->red_partial); (void)hipFree(ctx->red_out); (void)hipHostFree(ctx->red_host);
   (void)hipFree(ctx->scan_tmp);
   (void)hipFree(ctx->cmd_start); (void)hipFree(ctx->cmd_add); (void)hipFree(ctx->cmd_rank);
+  background_free(ctx);
   (void)hipFree(ctx->abar32); (void)hipFree(ctx->abar_work); (void)hipFree(ctx->abar_r);
   (void)hipFree(ctx->lrow_buf[0]); (void)hipFree(ctx->lrow_buf[1]);
   for (int i = 0; i < 4; ++i) (void)hipFree(ctx->halo_buf[i]);

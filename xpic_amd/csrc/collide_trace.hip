@@ -14,6 +14,12 @@
 // XPIC_TRACE_BG_MAX; every global index is formed under q < n.  The four tallies travel per lane in tally [4][n] from
 // launch to launch and leave through block_reduce_store / reduce_to_host in a fixed order.  The host side is trace_call.h's
 // with the "never" policy, as the model traces'.
+//
+// The same kernel text serves the collisional grid traces (xpic_full_orbit_trace_collisional,
+// xpic_drift_kinetic_trace_collisional): it is written over the field source (the model, or the context's grid through
+// FOGrid / DKGrid), the background source (the struct's uniform backgrounds, or the context's per-cell profiles of
+// background.hip) and the lanes (all particles, or the list of live ones, so the grid traces' compaction is honoured).
+// tests/collisional_grid_trace_ref.py states that form a second time.
 #include <cmath>
 #include <string>
 
@@ -65,15 +71,112 @@ __device__ inline void coll_partner(const CollBg& b, uint64_t& st, double* w)
   w[2] = b.drift[2] + b.vth * g3;
 }
 
-// the collisions of one full-orbit step: v is the record's p
-__device__ inline void coll_fo(const CollDev& C, uint64_t step_key, long long particle, double* v, double* t)
+// ---- the three things a kernel is written over: the field source, the background source, the lanes' particles.
+//
+// A field source is a kernel argument with src(g), the source the step functions take (full_orbit_step.h,
+// drift_kinetic_step.h): the analytic model, or the context's grid.
+struct ModelField {
+  xpic_field_model M;
+  __device__ inline ModelSource src(const GridDev&) const { return ModelSource{M}; }
+};
+struct FOGridField {
+  const double *E, *B;
+  __device__ inline FOGrid src(const GridDev& g) const { return FOGrid{g, E, B}; }
+};
+template <bool GRAD>
+struct DKGridField {
+  const double *E, *B, *gB;
+  __device__ inline DKGrid<GRAD> src(const GridDev& g) const { return DKGrid<GRAD>{g, E, B, gB}; }
+};
+
+// A background source says what a particle at r meets of background b: cell(g, r) once per colliding step, then
+// get(C, b, cell, own) per background fills what coll_partner and collide_pair read; false: no collision for that
+// background, nothing is drawn and neither tally moves.  UniformBg: the struct's own backgrounds, as the host formed them
+// (kUniform: the callers read C.bg[b] where it lies, the kernel argument, and get is never called).
+struct UniformBg {
+  static constexpr bool kUniform = true;
+  __device__ inline long cell(const GridDev&, const double*) const { return 0; }
+  __device__ inline bool get(const CollDev&, int, long, CollBg&) const { return true; }
+};
+// ProfileBg: background b reads n, vth and the drift of slot[b] ([5][ncell], background.hip) at the cell of r --
+// floor(r / d) per axis, folded onto the grid by the true modulus (positions are not folded in the traces), piecewise
+// constant -- and forms sigma^2's factor ((c0 n) dt_c) here, rounded operation by operation as the host rounds the
+// uniform one's: a constant profile gives the uniform background's bits.  slot[b] null: the uniform one of the struct.
+// A position that is not a number, or further out than an int counts cells, has no cell (fo_in_range): no index is
+// formed from it and it meets nobody.  n == 0: nobody to meet.
+struct ProfileBg {
+  static constexpr bool kUniform = false;
+  const double* slot[XPIC_TRACE_BG_MAX];
+  double c0[XPIC_TRACE_BG_MAX]; // S q_a^2 q_b^2 / m_ab^2
+  double dtc;                   // every * dt
+  long ncell;
+  __device__ inline long cell(const GridDev& g, const double* r) const
+  {
+#pragma clang fp contract(off)
+    if (!fo_in_range(g, r)) return -1;
+    const int x = GridDev::wrap((int)floor(r[0] / g.dx), g.nx), y = GridDev::wrap((int)floor(r[1] / g.dy), g.ny),
+              z = GridDev::wrap((int)floor(r[2] / g.dz), g.nzl);
+    return ((long)z * g.ny + y) * g.nx + x;
+  }
+  __device__ inline bool get(const CollDev& C, int b, long cell, CollBg& own) const
+  {
+#pragma clang fp contract(off)
+    own = C.bg[b]; // (by value: a pointer that may lead to the kernel argument or to `own` would put both in scratch)
+    const double* p = slot[b];
+    if (!p) return true;
+    if (cell < 0 || cell >= ncell) return false;
+    const double n = p[cell];
+    if (!(n > 0.0)) return false;
+    own.cdt = (c0[b] * n) * dtc;
+    own.vth = p[ncell + cell];
+    own.drift[0] = p[2 * ncell + cell];
+    own.drift[1] = p[3 * ncell + cell];
+    own.drift[2] = p[4 * ncell + cell];
+    return true;
+  }
+};
+
+// The particle *q of lane j of a launch; false: none.  AllLanes: particle j (the model traces: every launch covers all n);
+// ListedLanes: entry j of the list of live particles (trace_open.hip; null: the particles 0 .. m - 1), the grid traces'.
+struct AllLanes {
+  __device__ inline bool pick(long j, long n, long* q) const
+  {
+    *q = j;
+    return j < n;
+  }
+};
+struct ListedLanes {
+  const long long* list;
+  long m;
+  __device__ inline bool pick(long j, long n, long* q) const
+  {
+    *q = j < m ? (list ? (long)list[j] : j) : -1;
+    return *q >= 0 && *q < n;
+  }
+};
+
+// one full-orbit collision with background b
+__device__ inline void coll_fo_one(const CollBg& bg, uint64_t step_key, long long particle, int b, double* v, double* t)
 {
+  uint64_t st = trace_stream(step_key, particle, b);
+  double w[3];
+  coll_partner(bg, st, w);
+  (void)u01(st); // a5: the gyrophase a guiding centre draws here
+  collide_pair(bg.fa, 0.0, bg.cdt, st, v, w, t);
+}
+
+// the collisions of one full-orbit step at r: v is the record's p
+template <class BG>
+__device__ inline void coll_fo(const BG& bgs, const GridDev& g, const CollDev& C, uint64_t step_key, long long particle,
+  const double* r, double* v, double* t)
+{
+  const long cell = bgs.cell(g, r);
   for (int b = 0; b < C.nbg && b < XPIC_TRACE_BG_MAX; ++b) {
-    uint64_t st = trace_stream(step_key, particle, b);
-    double w[3];
-    coll_partner(C.bg[b], st, w);
-    (void)u01(st); // a5: the gyrophase a guiding centre draws here
-    collide_pair(C.bg[b].fa, 0.0, C.bg[b].cdt, st, v, w, t);
+    if constexpr (BG::kUniform) coll_fo_one(C.bg[b], step_key, particle, b, v, t);
+    else {
+      CollBg own;
+      if (bgs.get(C, b, cell, own)) coll_fo_one(own, step_key, particle, b, v, t);
+    }
   }
 }
 
@@ -101,48 +204,69 @@ __device__ inline double coll_basis(const double* B, double* b, double* e1, doub
   return lenB;
 }
 
-// the collisions of one guiding-centre step; B: the model at pn.r.  |B| == 0: the step's collisions are skipped and counted
-__device__ inline void coll_dk(const CollDev& C, uint64_t step_key, long long particle, const double* B, double mp, DKPoint& pn,
-  double* t)
+// one guiding-centre collision with background k, in the basis b, e1, e2 across B
+__device__ inline void coll_dk_one(const CollBg& bg, uint64_t step_key, long long particle, int k, const double* b,
+  const double* e1, const double* e2, double lenB, double mp, DKPoint& pn, double* t)
+{
+#pragma clang fp contract(off)
+  uint64_t st = trace_stream(step_key, particle, k);
+  double w[3], v[3];
+  coll_partner(bg, st, w);
+  const double psi = 2.0 * M_PI * u01(st);
+  const double cs = cos(psi), sn = sin(psi);
+#pragma unroll
+  for (int c = 0; c < 3; ++c) v[c] = pn.ppar * b[c] + pn.pperp * (cs * e1[c] + sn * e2[c]);
+  const double made = t[0];
+  collide_pair(bg.fa, 0.0, bg.cdt, st, v, w, t);
+  if (t[0] == made) return; // (|u| == 0: skipped, the record keeps its bits)
+  const double par = v[0] * b[0] + v[1] * b[1] + v[2] * b[2];
+  const double x = v[0] - par * b[0], y = v[1] - par * b[1], z = v[2] - par * b[2];
+  const double perp = sqrt(x * x + y * y + z * z);
+  pn.ppar = par;
+  pn.pperp = perp;
+  pn.mu = mp * perp * perp / (2.0 * lenB);
+}
+
+// the collisions of one guiding-centre step; B: the field source at pn.r.  |B| == 0: the step's collisions are skipped and
+// counted (on a profile: those of the backgrounds that have somebody to meet in the cell)
+template <class BG>
+__device__ inline void coll_dk(const BG& bgs, const GridDev& g, const CollDev& C, uint64_t step_key, long long particle,
+  const double* B, double mp, DKPoint& pn, double* t)
 {
 #pragma clang fp contract(off)
   double b[3], e1[3], e2[3];
   const double lenB = coll_basis(B, b, e1, e2);
-  if (lenB == 0.0) {
+  if (BG::kUniform && lenB == 0.0) {
     t[1] += (double)C.nbg;
     return;
   }
+  const long cell = bgs.cell(g, pn.r);
   for (int k = 0; k < C.nbg && k < XPIC_TRACE_BG_MAX; ++k) {
-    uint64_t st = trace_stream(step_key, particle, k);
-    double w[3], v[3];
-    coll_partner(C.bg[k], st, w);
-    const double psi = 2.0 * M_PI * u01(st);
-    const double cs = cos(psi), sn = sin(psi);
-#pragma unroll
-    for (int c = 0; c < 3; ++c) v[c] = pn.ppar * b[c] + pn.pperp * (cs * e1[c] + sn * e2[c]);
-    const double made = t[0];
-    collide_pair(C.bg[k].fa, 0.0, C.bg[k].cdt, st, v, w, t);
-    if (t[0] == made) continue; // (|u| == 0: skipped, the record keeps its bits)
-    const double par = v[0] * b[0] + v[1] * b[1] + v[2] * b[2];
-    const double x = v[0] - par * b[0], y = v[1] - par * b[1], z = v[2] - par * b[2];
-    const double perp = sqrt(x * x + y * y + z * z);
-    pn.ppar = par;
-    pn.pperp = perp;
-    pn.mu = mp * perp * perp / (2.0 * lenB);
+    if constexpr (BG::kUniform) coll_dk_one(C.bg[k], step_key, particle, k, b, e1, e2, lenB, mp, pn, t);
+    else {
+      CollBg own;
+      if (!bgs.get(C, k, cell, own)) continue;
+      if (lenB == 0.0) t[1] += 1.0;
+      else coll_dk_one(own, step_key, particle, k, b, e1, e2, lenB, mp, pn, t);
+    }
   }
 }
 
-// k_model_fo_trace (model_trace.hip) with the collisions of step R.step0 + first + done + 1 after its push
-template <bool CN>
-__global__ void __launch_bounds__(kBlock) k_coll_fo_trace(GridDev g, xpic_field_model M, xpic_fo_params P, OpenRegion R,
+// k_model_fo_trace (model_trace.hip) with the collisions of step R.step0 + first + done + 1 after its push, written once
+// over the field source, the background source and the lanes: <ModelField, UniformBg, AllLanes> is the model trace's
+// kernel, <FOGridField, ProfileBg, ListedLanes> k_fo_trace_open's (full_orbit.hip) with the collisions, R.kind < 0 its
+// closed form.  The per-lane tallies are the particle's, tally[k * n + q]: a list of live particles changes the lane, not
+// the slot.  The policies come last in the argument list, so what the model instance read before them lies where it lay.
+template <bool CN, class FIELD, class BG, class LANES>
+__global__ void __launch_bounds__(kBlock) k_coll_fo_trace(GridDev g, FIELD F, xpic_fo_params P, OpenRegion R,
   CollDev C, long n, double* __restrict__ s, long first, int nsteps, long sample_every, long nsamp, double* __restrict__ samples,
   long long* __restrict__ it_sum, int* __restrict__ it_max, long long* __restrict__ exit_step, unsigned long long* alive,
-  unsigned long long* removed, double* __restrict__ tally)
+  unsigned long long* removed, double* __restrict__ tally, BG bgs, LANES lanes)
 {
-  const long q = (long)blockIdx.x * kBlock + threadIdx.x;
-  const bool live = q < n && exit_step[q] < 0;
+  long q;
+  const bool live = lanes.pick((long)blockIdx.x * kBlock + threadIdx.x, n, &q) && exit_step[q] < 0;
   const int ns = nsteps < kLaunchSteps ? nsteps : kLaunchSteps;
-  const ModelSource src{M};
+  const auto src = F.src(g);
   int done = 0;
   bool gone = false;
   if (live) {
@@ -165,7 +289,7 @@ __global__ void __launch_bounds__(kBlock) k_coll_fo_trace(GridDev g, xpic_field_
       most = it > most ? it : most;
       const long step = first + done + 1;
       const long long k = R.step0 + step;
-      if (k % C.every == 0) coll_fo(C, trace_step_key(C.seed, k), C.particle0 + q, pn.p, t);
+      if (k % C.every == 0) coll_fo(bgs, g, C, trace_step_key(C.seed, k), C.particle0 + q, pn.r, pn.p, t);
       if (samples && step % sample_every == 0) {
         const long row = step / sample_every - 1;
         if (row < nsamp) fo_store(samples + row * 6 * n, n, q, pn);
@@ -180,16 +304,19 @@ __global__ void __launch_bounds__(kBlock) k_coll_fo_trace(GridDev g, xpic_field_
   open_tally<kBlock>(live, gone, first + done, first, ns, sample_every, nsamp, alive, removed);
 }
 
-// k_model_dk_trace<StaticClock> (model_trace.hip) with the collisions after the push, on the model at pn.r
-__global__ void __launch_bounds__(kBlock) k_coll_dk_trace(GridDev g, xpic_field_model M, xpic_dk_params P, OpenRegion R,
+// k_model_dk_trace<StaticClock> (model_trace.hip) with the collisions after the push, in the field the source gives for
+// the segment (pn.r, pn.r): the model at pn.r, or what xpic_drift_kinetic_interpolate returns there on the grid.
+// <DKGridField<GRAD>, ProfileBg, ListedLanes> is k_dk_trace_open's (drift_kinetic.hip) with the collisions.
+template <class FIELD, class BG, class LANES>
+__global__ void __launch_bounds__(kBlock) k_coll_dk_trace(GridDev g, FIELD F, xpic_dk_params P, OpenRegion R,
   CollDev C, long n, double* __restrict__ s, long first, int nsteps, long sample_every, long nsamp, double* __restrict__ samples,
   long long* __restrict__ it_total, int* __restrict__ it_max, long long* __restrict__ exit_step, unsigned long long* alive,
-  unsigned long long* removed, double* __restrict__ tally)
+  unsigned long long* removed, double* __restrict__ tally, BG bgs, LANES lanes)
 {
-  const long q = (long)blockIdx.x * kBlock + threadIdx.x;
-  const bool live = q < n && exit_step[q] < 0;
+  long q;
+  const bool live = lanes.pick((long)blockIdx.x * kBlock + threadIdx.x, n, &q) && exit_step[q] < 0;
   const int ns = nsteps < kLaunchSteps ? nsteps : kLaunchSteps;
-  const ModelSource src{M};
+  const auto src = F.src(g);
   int done = 0;
   bool gone = false;
   if (live) {
@@ -211,7 +338,7 @@ __global__ void __launch_bounds__(kBlock) k_coll_dk_trace(GridDev g, xpic_field_
       if (k % C.every == 0) {
         double Ep[3], Bp[3], gBp[3];
         src.dk(pn.r, pn.r, Ep, Bp, gBp);
-        coll_dk(C, trace_step_key(C.seed, k), C.particle0 + q, Bp, P.mp, pn, t);
+        coll_dk(bgs, g, C, trace_step_key(C.seed, k), C.particle0 + q, Bp, P.mp, pn, t);
       }
       if (samples && step % sample_every == 0) {
         const long row = step / sample_every - 1;
@@ -304,6 +431,89 @@ TraceEntry coll_entry(const std::string& who)
   return {who.c_str(), "the particle array", "an iteration counter", "an iteration counter", false};
 }
 
+// what the four colliding entry points do around trace_call: the tallies before the first launch, coll_4 after the last.
+// launch: trace_call's, with the tallies in place of the sums
+template <class Launch>
+int coll_trace(xpic_ctx* ctx, const std::string& who, const char* label, const char* compact_label, int64_t n, bool counters,
+  int64_t steps, int64_t sample_every, double* state_6, double* samples, int64_t* it_sum, int* it_max, const OpenRegion& R,
+  int policy, int64_t* exit_step, int64_t* alive, int64_t* removed, double* coll_4, Launch launch)
+{
+  const bool runs = n > 0 && steps > 0;
+  Tally tally;
+  if (runs) XPIC_CALL(tally.begin(ctx, n));
+  XPIC_CALL(trace_call(ctx, coll_entry(who), label, compact_label, kLaunchSteps, n, counters, steps, sample_every, state_6,
+    samples, it_sum, it_max, R, policy, exit_step, alive, removed, nullptr,
+    [&](double* s, const long long* list, long m, long first, int ns, long nsamp, double* sm, long long* sum, int* mx,
+      long long* ex, unsigned long long* al, unsigned long long* rm, double*) {
+      launch(s, list, m, first, ns, nsamp, sm, sum, mx, ex, al, rm, tally.d.p);
+    }));
+  if (coll_4)
+    for (int k = 0; k < kTally; ++k) coll_4[k] = 0.0;
+  if (runs) XPIC_CALL(tally.end(ctx, n, coll_4));
+  return 0;
+}
+
+// ---- the collisional grid traces
+static_assert(XPIC_FO_LAUNCH_STEPS == kLaunchSteps && XPIC_DK_LAUNCH_STEPS == kLaunchSteps,
+  "the grid instances of the kernels take the grid traces' launches");
+
+// the grid tracers' checks of the context, under the entry point's name
+int grid_check(xpic_ctx* ctx, const std::string& who, int64_t n)
+{
+  XPIC_CHECK(ctx != nullptr, "null context");
+  XPIC_CHECK(n >= 0, who + ": n is negative");
+  XPIC_CHECK(ctx->geom.nranks == 1 && ctx->g.G == 0,
+    who + ": a context of several z-slabs (or a self_ring one) is not supported: the gathers wrap z in the kernel");
+  XPIC_CHECK(ctx->field[XPIC_E] && ctx->field[XPIC_B], who + ": the context has no E or B");
+  return 0;
+}
+
+// the region of a collisional grid trace: XPIC_GEOM_NONE is the closed trace, and `compact` is read
+int grid_region(const std::string& who, const xpic_trace_region* region, OpenRegion* R, int* policy)
+{
+  XPIC_CALL(trace_region(who, region, true, true, R));
+  *policy = R->kind < 0 ? (int)XPIC_COMPACT_NEVER : region->compact;
+  return 0;
+}
+
+// the checks of `profile` (null: every background is the struct's uniform one) -> what the kernels get.  Called after
+// coll_setup has accepted `in`
+int profile_setup(xpic_ctx* ctx, const std::string& who, const xpic_trace_collisions* in, const int32_t* profile, double qm,
+  double dt, ProfileBg* B)
+{
+  *B = ProfileBg{};
+  B->ncell = ctx->ncell;
+  if (!in) return 0;
+  const double qa = qm * in->mass;
+  B->dtc = (double)in->every * dt;
+  for (int b = 0; b < in->nbg; ++b) {
+    const int s = profile ? profile[b] : -1;
+    XPIC_CHECK(s >= -1 && s < XPIC_TRACE_BG_MAX, who + ": a profile entry must be within -1 .. XPIC_TRACE_BG_MAX - 1");
+    XPIC_CHECK(s < 0 || ctx->bg_profile[s], who + ": a profile entry names an empty slot");
+    const xpic_trace_background& g = in->bg[b];
+    const double mab = in->mass * g.m / (in->mass + g.m);
+    B->c0[b] = in->strength * (qa * qa) * (g.q * g.q) / (mab * mab); // (as coll_setup forms it)
+    B->slot[b] = s < 0 ? nullptr : ctx->bg_profile[s];
+  }
+  return 0;
+}
+
+// a refusal of the grid trace that (a) hands the call to, under the collisional entry point's name as well
+int handed(const std::string& who, int rc)
+{
+  if (rc != 0) set_error(who + ": " + xpic_last_error());
+  return rc;
+}
+
+// the closed trace of (a) for a call that neither collides nor has a region: alive and removed as a model trace under
+// XPIC_GEOM_NONE reports them
+void closed_counts(int64_t n, int64_t steps, int64_t sample_every, int64_t* alive, int64_t* removed)
+{
+  if (alive && sample_every >= 1)
+    for (int64_t k = 0; k < steps / sample_every; ++k) alive[k] = n;
+  if (removed) *removed = 0;
+}
+
 }  // namespace
 
 }  // namespace xpic
@@ -336,20 +546,15 @@ int xpic_model_full_orbit_trace_collisional(xpic_ctx* ctx, int64_t n, const xpic
   OpenRegion R;
   XPIC_CALL(trace_region(who, region, true, false, &R));
   const bool cn = params->scheme == XPIC_FO_CN;
-  const bool runs = n > 0 && steps > 0;
-  Tally tally;
-  if (runs) XPIC_CALL(tally.begin(ctx, n));
-  XPIC_CALL(trace_call(ctx, coll_entry(who), "coll_fo_trace", "coll_fo_trace", kLaunchSteps, n, cn, steps, sample_every, p_6,
-    samples, iterations_sum, iterations_max, R, XPIC_COMPACT_NEVER, exit_step, alive, removed, nullptr,
+  return coll_trace(ctx, who, "coll_fo_trace", "coll_fo_trace", n, cn, steps, sample_every, p_6, samples, iterations_sum,
+    iterations_max, R, XPIC_COMPACT_NEVER, exit_step, alive, removed, coll_4,
     [&](double* s, const long long*, long, long first, int ns, long nsamp, double* sm, long long* sum, int* mx, long long* ex,
-      unsigned long long* al, unsigned long long* rm, double*) {
-      hipLaunchKernelGGL(cn ? k_coll_fo_trace<true> : k_coll_fo_trace<false>, lane_grid(n), dim3(kBlock), 0, ctx->stream,
-        ctx->g, *model, *params, R, Cd, (long)n, s, first, ns, (long)sample_every, nsamp, sm, sum, mx, ex, al, rm, tally.d.p);
-    }));
-  if (coll_4)
-    for (int k = 0; k < kTally; ++k) coll_4[k] = 0.0;
-  if (runs) XPIC_CALL(tally.end(ctx, n, coll_4));
-  return 0;
+      unsigned long long* al, unsigned long long* rm, double* tally) {
+      hipLaunchKernelGGL((cn ? k_coll_fo_trace<true, ModelField, UniformBg, AllLanes>
+                             : k_coll_fo_trace<false, ModelField, UniformBg, AllLanes>),
+        lane_grid(n), dim3(kBlock), 0, ctx->stream, ctx->g, ModelField{*model}, *params, R, Cd, (long)n, s, first, ns,
+        (long)sample_every, nsamp, sm, sum, mx, ex, al, rm, tally, UniformBg{}, AllLanes{});
+    });
 }
 
 int xpic_model_drift_kinetic_trace_collisional(xpic_ctx* ctx, int64_t n, const xpic_dk_params* params,
@@ -375,20 +580,104 @@ int xpic_model_drift_kinetic_trace_collisional(xpic_ctx* ctx, int64_t n, const x
   }
   OpenRegion R;
   XPIC_CALL(trace_region(who, region, true, false, &R));
-  const bool runs = n > 0 && steps > 0;
-  Tally tally;
-  if (runs) XPIC_CALL(tally.begin(ctx, n));
-  XPIC_CALL(trace_call(ctx, coll_entry(who), "coll_dk_trace", "coll_dk_trace", kLaunchSteps, n, true, steps, sample_every,
-    state_6, samples, iterations_total, iterations_max, R, XPIC_COMPACT_NEVER, exit_step, alive, removed, nullptr,
+  return coll_trace(ctx, who, "coll_dk_trace", "coll_dk_trace", n, true, steps, sample_every, state_6, samples,
+    iterations_total, iterations_max, R, XPIC_COMPACT_NEVER, exit_step, alive, removed, coll_4,
     [&](double* s, const long long*, long, long first, int ns, long nsamp, double* sm, long long* sum, int* mx, long long* ex,
-      unsigned long long* al, unsigned long long* rm, double*) {
-      hipLaunchKernelGGL(k_coll_dk_trace, lane_grid(n), dim3(kBlock), 0, ctx->stream, ctx->g, *model, *params, R, Cd, (long)n,
-        s, first, ns, (long)sample_every, nsamp, sm, sum, mx, ex, al, rm, tally.d.p);
-    }));
-  if (coll_4)
-    for (int k = 0; k < kTally; ++k) coll_4[k] = 0.0;
-  if (runs) XPIC_CALL(tally.end(ctx, n, coll_4));
-  return 0;
+      unsigned long long* al, unsigned long long* rm, double* tally) {
+      hipLaunchKernelGGL((k_coll_dk_trace<ModelField, UniformBg, AllLanes>), lane_grid(n), dim3(kBlock), 0, ctx->stream, ctx->g,
+        ModelField{*model}, *params, R, Cd, (long)n, s, first, ns, (long)sample_every, nsamp, sm, sum, mx, ex, al, rm, tally,
+        UniformBg{}, AllLanes{});
+    });
+}
+
+int xpic_full_orbit_trace_collisional(xpic_ctx* ctx, int64_t n, const xpic_fo_params* params, int64_t steps,
+  int64_t sample_every, double* p_6, double* samples, int64_t* iterations_sum, int* iterations_max,
+  const xpic_trace_region* region, int64_t* exit_step, int64_t* alive, int64_t* removed,
+  const xpic_trace_collisions* collisions, const int32_t* profile, double* coll_4)
+{
+  const std::string who = "full_orbit_trace_collisional";
+  XPIC_CALL(grid_check(ctx, who, n));
+  XPIC_CALL(fo_check_params(who, params));
+  bool on;
+  CollDev Cd;
+  ProfileBg Bg;
+  OpenRegion R;
+  int policy;
+  XPIC_CALL(coll_setup(who, collisions, params->qm, params->dt, &on, &Cd));
+  XPIC_CALL(profile_setup(ctx, who, collisions, profile, params->qm, params->dt, &Bg));
+  XPIC_CALL(grid_region(who, region, &R, &policy));
+  if (!on && (R.kind >= 0 || !exit_step)) { // the grid trace itself, bit for bit
+    if (R.kind >= 0)
+      XPIC_CALL(handed(who, xpic_full_orbit_trace_open(ctx, n, params, steps, sample_every, p_6, samples, iterations_sum, iterations_max,
+        region, exit_step, alive, removed)));
+    else {
+      XPIC_CALL(handed(who, xpic_full_orbit_trace(ctx, n, params, steps, sample_every, p_6, samples, iterations_sum, iterations_max)));
+      closed_counts(n, steps, sample_every, alive, removed);
+    }
+    if (coll_4)
+      for (int k = 0; k < kTally; ++k) coll_4[k] = 0.0;
+    return 0;
+  }
+  if (!on) Cd.every = 1; // (no region, but an exit_step to honour: the kernel with no background)
+  const bool cn = params->scheme == XPIC_FO_CN;
+  const FOGridField F{ctx->field[XPIC_E], ctx->field[XPIC_B]};
+  return coll_trace(ctx, who, "coll_fo_grid_trace", "coll_fo_grid_trace_compact", n, cn, steps, sample_every, p_6, samples,
+    iterations_sum, iterations_max, R, policy, exit_step, alive, removed, coll_4,
+    [&](double* s, const long long* list, long m, long first, int ns, long nsamp, double* sm, long long* sum, int* mx,
+      long long* ex, unsigned long long* al, unsigned long long* rm, double* tally) {
+      hipLaunchKernelGGL((cn ? k_coll_fo_trace<true, FOGridField, ProfileBg, ListedLanes>
+                             : k_coll_fo_trace<false, FOGridField, ProfileBg, ListedLanes>),
+        lane_grid(m), dim3(kBlock), 0, ctx->stream, ctx->g, F, *params, R, Cd, (long)n, s, first, ns, (long)sample_every, nsamp,
+        sm, sum, mx, ex, al, rm, tally, Bg, ListedLanes{list, m});
+    });
+}
+
+int xpic_drift_kinetic_trace_collisional(xpic_ctx* ctx, int64_t n, const xpic_dk_params* params, int gradB_field,
+  int64_t steps, int64_t sample_every, double* state_6, double* samples, int64_t* iterations_total, int* iterations_max,
+  const xpic_trace_region* region, int64_t* exit_step, int64_t* alive, int64_t* removed,
+  const xpic_trace_collisions* collisions, const int32_t* profile, double* coll_4)
+{
+  const std::string who = "drift_kinetic_trace_collisional";
+  XPIC_CALL(grid_check(ctx, who, n));
+  XPIC_CHECK(gradB_field == -1 || (gradB_field >= 0 && gradB_field < XPIC_NFIELDS && ctx->field[gradB_field]),
+    who + ": gradB_field is neither -1 nor an allocated field id");
+  XPIC_CALL(dk_check_params(who, params, 0));
+  bool on;
+  CollDev Cd;
+  ProfileBg Bg;
+  OpenRegion R;
+  int policy;
+  XPIC_CALL(coll_setup(who, collisions, params->qm, params->dt, &on, &Cd));
+  XPIC_CALL(profile_setup(ctx, who, collisions, profile, params->qm, params->dt, &Bg));
+  XPIC_CALL(grid_region(who, region, &R, &policy));
+  if (!on && (R.kind >= 0 || !exit_step)) { // the grid trace itself, bit for bit
+    if (R.kind >= 0)
+      XPIC_CALL(handed(who, xpic_drift_kinetic_trace_open(ctx, n, params, gradB_field, steps, sample_every, state_6, samples,
+        iterations_total, iterations_max, region, exit_step, alive, removed)));
+    else {
+      XPIC_CALL(handed(who, xpic_drift_kinetic_trace(ctx, n, params, gradB_field, steps, sample_every, state_6, samples, iterations_total,
+        iterations_max)));
+      closed_counts(n, steps, sample_every, alive, removed);
+    }
+    if (coll_4)
+      for (int k = 0; k < kTally; ++k) coll_4[k] = 0.0;
+    return 0;
+  }
+  if (!on) Cd.every = 1; // (no region, but an exit_step to honour: the kernel with no background)
+  const double* gB = gradB_field == -1 ? nullptr : ctx->field[gradB_field];
+  return coll_trace(ctx, who, "coll_dk_grid_trace", "coll_dk_grid_trace_compact", n, true, steps, sample_every, state_6,
+    samples, iterations_total, iterations_max, R, policy, exit_step, alive, removed, coll_4,
+    [&](double* s, const long long* list, long m, long first, int ns, long nsamp, double* sm, long long* sum, int* mx,
+      long long* ex, unsigned long long* al, unsigned long long* rm, double* tally) {
+      if (gB)
+        hipLaunchKernelGGL((k_coll_dk_trace<DKGridField<true>, ProfileBg, ListedLanes>), lane_grid(m), dim3(kBlock), 0,
+          ctx->stream, ctx->g, DKGridField<true>{ctx->field[XPIC_E], ctx->field[XPIC_B], gB}, *params, R, Cd, (long)n, s,
+          first, ns, (long)sample_every, nsamp, sm, sum, mx, ex, al, rm, tally, Bg, ListedLanes{list, m});
+      else
+        hipLaunchKernelGGL((k_coll_dk_trace<DKGridField<false>, ProfileBg, ListedLanes>), lane_grid(m), dim3(kBlock), 0,
+          ctx->stream, ctx->g, DKGridField<false>{ctx->field[XPIC_E], ctx->field[XPIC_B], gB}, *params, R, Cd, (long)n, s,
+          first, ns, (long)sample_every, nsamp, sm, sum, mx, ex, al, rm, tally, Bg, ListedLanes{list, m});
+    });
 }
 
 }  // extern "C"

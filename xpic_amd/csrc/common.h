@@ -254,6 +254,7 @@ struct xpic_ctx {
   int* cmd_rank = nullptr;
   int64_t cmd_rank_n = 0;
   int64_t collide_large_cells = 0; // collide.hip: local cells of the last call that took the second path
+  double* bg_profile[XPIC_TRACE_BG_MAX] = {}; // background.hip: the background profiles, [5][ncell] each; null: an empty slot
   double rtol = 1e-7, atol = 1e-7;
   int maxit = 100;
   xpic::Comm comm;
@@ -386,6 +387,9 @@ int set_mirror_field(xpic_ctx* c, double* F, double D, double R, double I);
 // collide.hip (an extension: the reference has no collision operator): xpic_collide (weighted false, out[4]) and
 // xpic_collide_weighted (Nanbu-Yonemura: sorts of unequal weight; out[6]; sort_a == sort_b takes the unweighted path)
 int collide(xpic_ctx* c, int sort_a, int sort_b, const xpic_collision_params& p, int64_t step, bool weighted, double* out);
+
+// background.hip: frees the background profiles (xpic_destroy)
+void background_free(xpic_ctx* c);
 
 // ecsim.hip
 int ecsim_fill_sort(xpic_ctx* c, Sort& s, const double* B, double* currI_sort, double* matL, bool first_sort, bool post_ghost_rows);
