@@ -10,36 +10,10 @@ import os
 
 import numpy as np
 
+from ._abi import *  # noqa: F401,F403 (the mirrors of include/xpic_hip.h; every name stays importable from here)
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libxpic_hip.so")
-
-E, B, B0, J, EP, EC, CURRI, CURRJE, W0, W1, W2 = range(11)
-BASIC, ECSIM, ECSIMCORR = 0, 1, 2
-OP_MATA_GMRES, OP_MATM_GMRES, OP_MATM_CG = 0, 1, 2
-LSTENCIL = 123
-SCHEMES = {"basic": BASIC, "ecsim": ECSIM, "ecsimcorr": ECSIMCORR}
-
-# every symbol include/xpic_hip.h declares (tests check that the library exports all of them)
-SYMBOLS = [
-    "xpic_last_error", "xpic_version", "xpic_create", "xpic_destroy", "xpic_synchronize", "xpic_add_sort",
-    "xpic_sort_add_particles", "xpic_sort_count", "xpic_sort_get_particles", "xpic_sort_clear",
-    "xpic_sort_fill_synthetic", "xpic_sort_load_synthetic", "xpic_sort_occupancy", "xpic_field_set", "xpic_field_get", "xpic_sort_current_get", "xpic_vec_set",
-    "xpic_vec_axpy", "xpic_vec_axpby", "xpic_vec_dot", "xpic_vec_norm2", "xpic_rot_apply", "xpic_matM_apply",
-    "xpic_matL_apply", "xpic_matA_apply", "xpic_matL_get", "xpic_lstencil_decode", "xpic_ecsim_first_push",
-    "xpic_update_cells", "xpic_ecsim_fill_current", "xpic_ecsim_second_push", "xpic_basic_push",
-    "xpic_ecsimcorr_first_push", "xpic_ecsimcorr_second_push", "xpic_ecsimcorr_final_update",
-    "xpic_calculate_energy", "xpic_ecsimcorr_scalars", "xpic_solve", "xpic_set_tolerances", "xpic_set_preconditioner", "xpic_precond_apply", "xpic_precond_get", "xpic_set_overlap", "xpic_comm_stats", "xpic_set_fill_kernel", "xpic_set_fused_rebin", "xpic_get_fill_variant", "xpic_debug_set", "xpic_step",
-    "xpic_energy", "xpic_momentum", "xpic_charge_density", "xpic_moment_density", "xpic_moment", "xpic_velocity_distribution", "xpic_remove_particles", "xpic_fields_damping",
-    "xpic_inject_particles", "xpic_collide", "xpic_collide_info", "xpic_collide_weighted", "xpic_set_coils_field", "xpic_set_mirror_field", "xpic_cell_traversal", "xpic_implicit_esirkepov_interpolate",
-    "xpic_implicit_esirkepov_decompose", "xpic_drift_kinetic_interpolate", "xpic_drift_kinetic_push",
-    "xpic_drift_kinetic_trace", "xpic_full_orbit_push", "xpic_full_orbit_trace", "xpic_full_orbit_trace_open",
-    "xpic_drift_kinetic_trace_open", "xpic_paired_trace", "xpic_model_fields", "xpic_set_model_field",
-    "xpic_model_full_orbit_trace", "xpic_model_drift_kinetic_trace", "xpic_model_full_orbit_trace_timed",
-    "xpic_model_drift_kinetic_trace_timed", "xpic_envelope_factors", "xpic_model_full_orbit_trace_collisional",
-    "xpic_model_drift_kinetic_trace_collisional", "xpic_background_set", "xpic_background_get", "xpic_background_clear",
-    "xpic_background_from_sort", "xpic_full_orbit_trace_collisional", "xpic_drift_kinetic_trace_collisional", "xpic_triplet_trace", "xpic_charge_collect", "xpic_charge_columns", "xpic_comm_rccl_unique_id", "xpic_comm_init_rccl", "xpic_comm_init_callbacks", "xpic_comm_size", "xpic_comm_peer_export", "xpic_comm_peer_import",
-    "xpic_profile_enable", "xpic_profile_reset", "xpic_profile_get", "xpic_probe_copy_bandwidth",
-]
 
 
 def csrc_hash():
@@ -60,39 +34,6 @@ class XpicError(RuntimeError):
     pass
 
 
-class Geometry(C.Structure):
-    _fields_ = [("n", C.c_int32 * 3), ("d", C.c_double * 3), ("dt", C.c_double), ("periodic", C.c_int32 * 3),
-                ("rank", C.c_int32), ("nranks", C.c_int32), ("device", C.c_int32), ("self_ring", C.c_int32)]
-
-
-# include/xpic_hip.h: enum xpic_moment_kind (the reference's order) and the components of each moment
-MOMENTS = {"density": 0, "current": 1, "momentum_flux": 2, "momentum_flux_diag": 3, "momentum_flux_cyl": 4,
-           "momentum_flux_diag_cyl": 5}
-MOMENT_DOF = {"density": 1, "current": 3, "momentum_flux": 6, "momentum_flux_diag": 3, "momentum_flux_cyl": 6,
-              "momentum_flux_diag_cyl": 3}
-PROJECTORS = {"vx_vy": 0, "vz_vxy": 1, "vr_vphi": 2}  # enum xpic_projector
-GEOMETRIES = {"box": 0, "BoxGeometry": 0, "cylinder": 1, "CylinderGeometry": 1}  # enum xpic_vgeometry
-
-COORDINATES = {"PreciseCoordinate": 0, "CoordinateInBox": 1, "CoordinateInCylinder": 2}  # enum xpic_coordinate_kind
-MOMENTA = {"PreciseMomentum": 0, "MaxwellianMomentum": 1}  # enum xpic_momentum_kind
-
-
-class MomentumParams(C.Structure):
-    _fields_ = [("kind", C.c_int32), ("tov", C.c_int32), ("value", C.c_double * 3), ("T", C.c_double * 3)]
-
-
-class InjectParams(C.Structure):
-    _fields_ = [("coordinate", C.c_int32), ("reserved", C.c_int32), ("geom", C.c_double * 7),
-                ("momentum", MomentumParams * 2), ("seed", C.c_uint64)]
-
-
-class CollisionParams(C.Structure):  # include/xpic_hip.h: xpic_collision_params
-    _fields_ = [("strength", C.c_double), ("dt", C.c_double), ("seed", C.c_uint64)]
-
-
-COLLIDE_LDS_CELL = 256  # include/xpic_hip.h: XPIC_COLLIDE_LDS_CELL (Context.collide_info reads the library's own)
-
-
 def _geom7(geometry):
     """(kind, double[7]) of a geometry dict: {"name": "box", "min": xyz, "max": xyz} or {"name": "cylinder", "center": xyz,
     "radius": r, "height": h} ("BoxGeometry" / "CylinderGeometry" as well)"""
@@ -102,91 +43,6 @@ def _geom7(geometry):
     else:
         gp = list(geometry["center"]) + [geometry["radius"], geometry["height"], 0.0, 0.0]
     return kind, np.array(gp, dtype=np.float64)
-
-
-DEBUG_GATHER_WINDOW, DEBUG_PENCIL_LIMIT, DEBUG_SURROGATE_SCALE = 0, 1, 2  # include/xpic_hip.h: xpic_debug_set
-PEER_BLOB_BYTES = 256  # include/xpic_hip.h: XPIC_PEER_BLOB_BYTES
-VERSION_EXPERIMENT_BIT = 0x40000000  # include/xpic_hip.h: XPIC_VERSION_EXPERIMENT_BIT
-
-
-class LoadParams(C.Structure):
-    _fields_ = [("ppc", C.c_int32), ("profile", C.c_int32), ("vth", C.c_double), ("drift", C.c_double * 3),
-                ("profile_param", C.c_double * 4), ("seed", C.c_uint64)]
-
-
-LOAD_PROFILES = {"poisson": 0, "uniform": 0, "regular": 1, "gradient": 2, "blob": 3}  # include/xpic_hip.h: XPIC_LOAD_*
-
-
-class SortParams(C.Structure):
-    _fields_ = [("Np", C.c_int32), ("n", C.c_double), ("q", C.c_double), ("m", C.c_double)]
-
-
-class DkParams(C.Structure):  # include/xpic_hip.h: xpic_dk_params
-    _fields_ = [("qm", C.c_double), ("mp", C.c_double), ("dt", C.c_double), ("eps", C.c_double), ("delta", C.c_double),
-                ("maxit", C.c_int32)]
-
-
-DK_LAUNCH_STEPS = 64  # include/xpic_hip.h: XPIC_DK_LAUNCH_STEPS
-
-
-class FoParams(C.Structure):  # include/xpic_hip.h: xpic_fo_params
-    _fields_ = [("qm", C.c_double), ("dt", C.c_double), ("atol", C.c_double), ("rtol", C.c_double), ("scheme", C.c_int32),
-                ("maxit", C.c_int32)]
-
-
-# include/xpic_hip.h: enum xpic_fo_scheme -- the 17 Chin ids of tests/boris_push/boris_push.h, then Crank-Nicolson
-FO_SCHEMES = {name: i for i, name in enumerate(
-    ["M1A", "M1B", "MLF", "B1A", "B1B", "BLF", "C1A", "C1B", "CLF", "M2A", "M2B", "C2A", "B2B", "EB1A", "EB1B", "EBLF",
-     "EB2B", "CN"])}
-FO_LAUNCH_STEPS = 64  # include/xpic_hip.h: XPIC_FO_LAUNCH_STEPS
-FO_MAXIT = 64         # include/xpic_hip.h: XPIC_FO_MAXIT
-
-
-class TraceRegion(C.Structure):  # include/xpic_hip.h: xpic_trace_region
-    _fields_ = [("geometry", C.c_int32), ("compact", C.c_int32), ("geom", C.c_double * 7), ("step0", C.c_int64)]
-
-
-COMPACT = {"auto": 0, "never": 1, "always": 2}  # include/xpic_hip.h: enum xpic_trace_compact
-PAIR_LAUNCH_STEPS = 64  # include/xpic_hip.h: XPIC_PAIR_LAUNCH_STEPS
-PAIR_DK_MAXIT = 1024    # include/xpic_hip.h: XPIC_PAIR_DK_MAXIT
-PAIR_STATS = ("z", "p_parallel", "mu", "energy")  # the columns of stats_4 and curve_4 (xpic_paired_trace)
-
-
-class FieldModel(C.Structure):  # include/xpic_hip.h: xpic_field_model
-    _fields_ = [("kind", C.c_int32), ("reserved", C.c_int32), ("E0", C.c_double * 3), ("B0", C.c_double * 3),
-                ("r0", C.c_double * 3), ("g", C.c_double * 3), ("B_min", C.c_double), ("B_max", C.c_double), ("W", C.c_double),
-                ("D", C.c_double), ("L", C.c_double), ("E_phi", C.c_double), ("phi", C.c_double)]
-
-
-MODEL_KINDS = {"uniform": 0, "linear": 1, "quadratic_mirror": 2, "gaussian_mirror": 3}  # include/xpic_hip.h: enum xpic_model_kind
-GEOM_NONE = -1             # include/xpic_hip.h: XPIC_GEOM_NONE
-MODEL_LAUNCH_STEPS = 64    # include/xpic_hip.h: XPIC_MODEL_LAUNCH_STEPS
-MODEL_DK_MAXIT = 1024      # include/xpic_hip.h: XPIC_MODEL_DK_MAXIT
-TRIPLET_LAUNCH_STEPS = 64  # include/xpic_hip.h: XPIC_TRIPLET_LAUNCH_STEPS
-TRIPLET_DK_MAXIT = 1024    # include/xpic_hip.h: XPIC_TRIPLET_DK_MAXIT
-# the columns of stats_7 and curve_7 (xpic_triplet_trace), XPIC_TRIPLET_NSTATS of them: ComparisonStats' order
-TRIPLET_STATS = ("B", "gradB", "pos", "z", "p_parallel", "mu", "energy")
-
-
-class FieldEnvelope(C.Structure):  # include/xpic_hip.h: xpic_field_envelope
-    _fields_ = [("kind", C.c_int32), ("reserved", C.c_int32), ("a", C.c_double), ("b", C.c_double), ("omega", C.c_double),
-                ("phase", C.c_double)]
-
-
-# include/xpic_hip.h: enum xpic_envelope_kind; "harmonic" is an extension, the reference has no such callback
-ENVELOPE_KINDS = {"constant": 0, "ramp": 1, "harmonic": 2}
-
-
-TRACE_BG_MAX = 4  # include/xpic_hip.h: XPIC_TRACE_BG_MAX
-
-
-class TraceBackground(C.Structure):  # include/xpic_hip.h: xpic_trace_background
-    _fields_ = [("q", C.c_double), ("m", C.c_double), ("n", C.c_double), ("vth", C.c_double), ("drift", C.c_double * 3)]
-
-
-class TraceCollisions(C.Structure):  # include/xpic_hip.h: xpic_trace_collisions
-    _fields_ = [("nbg", C.c_int32), ("every", C.c_int32), ("seed", C.c_uint64), ("particle0", C.c_int64),
-                ("strength", C.c_double), ("mass", C.c_double), ("bg", TraceBackground * TRACE_BG_MAX)]
 
 
 def trace_collisions(backgrounds, strength, mass, every=1, seed=0, particle0=0):
@@ -307,13 +163,11 @@ def guiding_centre(points6, B3, mp, qm, *, orbit_centre=False):
 
 
 _lib = None
-c_dp = C.POINTER(C.c_double)
-# include/xpic_hip.h: int xpic_collide_weighted(xpic_ctx*, int, int, const xpic_collision_params*, int64_t, double[6])
-COLLIDE_WEIGHTED_ARGTYPES = [C.c_void_p, C.c_int, C.c_int, C.POINTER(CollisionParams), C.c_int64, c_dp]
 
 
 def load_library():
-    """Loads libxpic_hip.so; raises if it has not been built (no fallback path exists)."""
+    """Loads libxpic_hip.so and types every entry point from PROTOTYPES; raises if it has not been built (no fallback
+    path exists).  The xpic_debug_*_stamps symbols of experiment builds are not in the header and stay untyped."""
     global _lib
     if _lib is not None:
         return _lib
@@ -321,9 +175,9 @@ def load_library():
         raise XpicError(f"{LIB_PATH} is missing: run `make` (or __graft_entry__.build()) first; "
                         "xpic_amd has no CPU fallback")
     L = C.CDLL(LIB_PATH)
-    L.xpic_last_error.restype = C.c_char_p
-    L.xpic_collide_weighted.restype = C.c_int
-    L.xpic_collide_weighted.argtypes = COLLIDE_WEIGHTED_ARGTYPES
+    for name, (ret, args) in PROTOTYPES.items():
+        f = getattr(L, name)
+        f.restype, f.argtypes = CTYPES[ret], [CTYPES[a] for a in args]
     if L.xpic_version() & VERSION_EXPERIMENT_BIT and os.environ.get("XPIC_ALLOW_EXPERIMENT") != "1":
         raise XpicError(f"{LIB_PATH} was built with -DXPIC_EXPERIMENT (ablation switches / in-kernel timers: its results "
                         "may be wrong by design); rebuild with `make clean all`, or set XPIC_ALLOW_EXPERIMENT=1 for a "
@@ -332,9 +186,19 @@ def load_library():
     return L
 
 
-def _dp(a):
-    assert a.dtype == np.float64 and a.flags["C_CONTIGUOUS"]
-    return a.ctypes.data_as(c_dp)
+def _array_pointer(dtype, word):
+    def pointer(a):
+        """a contiguous array of the dtype as the header's pointer type; None stays None, the null pointer"""
+        if a is None:
+            return None
+        assert a.dtype == dtype and a.flags["C_CONTIGUOUS"]
+        return a.ctypes.data_as(CTYPES[word])
+    return pointer
+
+
+_dp = _array_pointer(np.float64, "double*")
+_i64p = _array_pointer(np.int64, "int64_t*")
+_i32p = _array_pointer(np.int32, "int32_t*")  # (and the header's `int*`: the same ctypes type)
 
 
 class Context:
@@ -369,10 +233,6 @@ class Context:
     def comm_init_callbacks(self, sendrecv, allreduce_sum):
         """sendrecv(down: bytes, up: bytes, n_from_up, n_from_down) -> (from_up: bytes, from_down: bytes);
         allreduce_sum(np.ndarray[float64]) -> reduces in place.  Used by tests (torch.distributed / gloo)."""
-        SR = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
-                         C.c_void_p, C.c_size_t)
-        AR = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_double), C.c_int)
-
         def _sr(user, down, nd, up, nu, fu, nfu, fd, nfd):
             try:
                 a, b = sendrecv(C.string_at(down, nd) if nd else b"", C.string_at(up, nu) if nu else b"", nfu, nfd)
@@ -394,10 +254,8 @@ class Context:
                 print("xpic comm callback failed:", e, flush=True)
                 return 1
 
-        class CB(C.Structure):
-            _fields_ = [("user", C.c_void_p), ("sendrecv", SR), ("allreduce_sum", AR)]
-
-        self._cb = CB(None, SR(_sr), AR(_ar))
+        _, (_, SR), (_, AR) = CommCallbacks._fields_
+        self._cb = CommCallbacks(None, SR(_sr), AR(_ar))
         self._ck(self.L.xpic_comm_init_callbacks(self.h, C.byref(self._cb)))
 
     def comm_peer_export(self):
@@ -435,14 +293,14 @@ class Context:
     def add_sort(self, Np, n, q, m, capacity):
         p = SortParams(int(Np), float(n), float(q), float(m))
         out = C.c_int()
-        self._ck(self.L.xpic_add_sort(self.h, C.byref(p), C.c_int64(int(capacity)), C.byref(out)))
+        self._ck(self.L.xpic_add_sort(self.h, C.byref(p), int(capacity), C.byref(out)))
         self.nsorts += 1
         return out.value
 
     def add_particles(self, sort, pts):
         pts = np.ascontiguousarray(pts, dtype=np.float64)
         added = C.c_int64()
-        self._ck(self.L.xpic_sort_add_particles(self.h, sort, C.c_int64(pts.shape[0]), _dp(pts), C.byref(added)))
+        self._ck(self.L.xpic_sort_add_particles(self.h, sort, pts.shape[0], _dp(pts), C.byref(added)))
         return added.value
 
     def count(self, sort):
@@ -454,14 +312,14 @@ class Context:
         n = self.count(sort)
         pts = np.zeros((n, 6))
         cells = np.zeros(n, dtype=np.int32)
-        self._ck(self.L.xpic_sort_get_particles(self.h, sort, _dp(pts), cells.ctypes.data_as(C.POINTER(C.c_int32))))
+        self._ck(self.L.xpic_sort_get_particles(self.h, sort, _dp(pts), _i32p(cells)))
         return pts, cells
 
     def clear(self, sort):
         self._ck(self.L.xpic_sort_clear(self.h, sort))
 
     def fill_synthetic(self, sort, ppc, vth, seed=1, regular=False):
-        self._ck(self.L.xpic_sort_fill_synthetic(self.h, sort, int(ppc), C.c_double(vth), C.c_uint64(seed), int(regular)))
+        self._ck(self.L.xpic_sort_fill_synthetic(self.h, sort, int(ppc), vth, seed, int(regular)))
 
     def load_synthetic(self, sort, ppc, vth, seed=1, profile="poisson", drift=(0.0, 0.0, 0.0), param=(0.0, 0.0)):
         """fill_synthetic with a drift (MaxwellianMomentum's px, py, pz: an extension of the reference's JSON surface) and
@@ -499,13 +357,13 @@ class Context:
         return v
 
     def vec_set(self, y, a):
-        self._ck(self.L.xpic_vec_set(self.h, y, C.c_double(a)))
+        self._ck(self.L.xpic_vec_set(self.h, y, a))
 
     def vec_axpy(self, y, a, x):
-        self._ck(self.L.xpic_vec_axpy(self.h, y, C.c_double(a), x))
+        self._ck(self.L.xpic_vec_axpy(self.h, y, a, x))
 
     def vec_axpby(self, y, a, b, x):
-        self._ck(self.L.xpic_vec_axpby(self.h, y, C.c_double(a), C.c_double(b), x))
+        self._ck(self.L.xpic_vec_axpby(self.h, y, a, b, x))
 
     def vec_dot(self, x, y):
         o = C.c_double()
@@ -519,7 +377,7 @@ class Context:
 
     # ---- operators
     def rot_apply(self, sign, alpha, x, y, add=False):
-        self._ck(self.L.xpic_rot_apply(self.h, sign, C.c_double(alpha), x, y, int(add)))
+        self._ck(self.L.xpic_rot_apply(self.h, sign, alpha, x, y, int(add)))
 
     def matM_apply(self, x, y, add=False):
         self._ck(self.L.xpic_matM_apply(self.h, x, y, int(add)))
@@ -574,12 +432,11 @@ class Context:
 
     def solve(self, op, rhs, x, rtol=1e-7, atol=1e-7, maxit=100):
         its, reason, rn = C.c_int(), C.c_int(), C.c_double()
-        self._ck(self.L.xpic_solve(self.h, op, rhs, x, C.c_double(rtol), C.c_double(atol), maxit, C.byref(its),
-                                   C.byref(reason), C.byref(rn)))
+        self._ck(self.L.xpic_solve(self.h, op, rhs, x, rtol, atol, maxit, C.byref(its), C.byref(reason), C.byref(rn)))
         return its.value, reason.value, rn.value
 
     def set_tolerances(self, rtol, atol, maxit):
-        self._ck(self.L.xpic_set_tolerances(self.h, C.c_double(rtol), C.c_double(atol), maxit))
+        self._ck(self.L.xpic_set_tolerances(self.h, rtol, atol, maxit))
 
     def set_preconditioner(self, kind, degree=0):
         self._ck(self.L.xpic_set_preconditioner(self.h, int(kind), int(degree)))
@@ -618,7 +475,7 @@ class Context:
 
     def debug_set(self, what, value):
         """test hooks (include/xpic_hip.h): DEBUG_GATHER_WINDOW, DEBUG_PENCIL_LIMIT"""
-        self._ck(self.L.xpic_debug_set(self.h, int(what), C.c_int64(int(value))))
+        self._ck(self.L.xpic_debug_set(self.h, int(what), int(value)))
 
     def set_overlap(self, on):
         self._ck(self.L.xpic_set_overlap(self.h, int(on)))  # bit 0: operator halos, bit 1: matL ghost rows
@@ -663,12 +520,7 @@ class Context:
         """VelocityDistribution of one sort (include/xpic_hip.h: xpic_velocity_distribution) -> (array [vsize_y][vsize_x],
         vstart (x, y)), the whole histogram on every slab.  geometry: {"name": "box", "min": xyz, "max": xyz} or
         {"name": "cylinder", "center": xyz, "radius": r, "height": h} ("BoxGeometry" / "CylinderGeometry" as well)."""
-        kind = GEOMETRIES[geometry["name"]]
-        if kind == 0:
-            gp = list(geometry["min"]) + list(geometry["max"]) + [0.0]
-        else:
-            gp = list(geometry["center"]) + [geometry["radius"], geometry["height"], 0.0]
-        gp = np.array(gp, dtype=np.float64)
+        kind, gp = _geom7(geometry)  # (the header's `const double geom[7]`, of which this entry point reads six at most)
         vreg = np.array([vmin[0], vmin[1], vmax[0], vmax[1], dv[0], dv[1]], dtype=np.float64)
         vg = (C.c_int * 4)()  # vsize_x, vsize_y, vstart_x, vstart_y (include/xpic_hip.h)
         self._ck(self.L.xpic_velocity_distribution(self.h, sort, PROJECTORS[projector], kind, _dp(gp), _dp(vreg), vg, None))
@@ -689,7 +541,7 @@ class Context:
         """FieldsDamping of E and B - B0 outside `geometry` -> the damped energy, summed over the slabs"""
         kind, gp = _geom7(geometry)
         e = C.c_double()
-        self._ck(self.L.xpic_fields_damping(self.h, E, B, B0, kind, _dp(gp), C.c_double(coefficient), C.byref(e)))
+        self._ck(self.L.xpic_fields_damping(self.h, E, B, B0, kind, _dp(gp), coefficient, C.byref(e)))
         return e.value
 
     def inject_particles(self, ionized, ejected, pairs, step, coordinate, momentum_i, momentum_e, seed=1):
@@ -711,8 +563,8 @@ class Context:
             mp.T[:] = [float(v) for v in m.get("T", (0.0, 0.0, 0.0))]
         p.seed = int(seed)
         added, e2 = C.c_int64(), np.zeros(2)
-        self._ck(self.L.xpic_inject_particles(self.h, ionized, ejected, C.byref(p), C.c_int64(int(pairs)),
-                                              C.c_int64(int(step)), C.byref(added), _dp(e2)))
+        self._ck(self.L.xpic_inject_particles(self.h, ionized, ejected, C.byref(p), int(pairs), int(step),
+                                              C.byref(added), _dp(e2)))
         return added.value, (float(e2[0]), float(e2[1]))
 
     def collide(self, sort_a, sort_b, strength, step, seed=0, dt=None):
@@ -720,13 +572,13 @@ class Context:
         (include/xpic_hip.h: xpic_collide; an extension, the reference has no collision operator) -> dict of the pairs
         collided, the pairs skipped (|u| == 0), the sum of sigma^2 over the collided pairs and the pairs with
         sigma^2 > 1, summed over the slabs.  dt: None for the context's."""
-        return self._collide(self.L.xpic_collide, sort_a, sort_b, strength, C.c_int64(int(step)), seed, dt, 4)[0]
+        return self._collide(self.L.xpic_collide, sort_a, sort_b, strength, step, seed, dt, 4)[0]
 
     def _collide(self, entry, sort_a, sort_b, strength, step, seed, dt, counters):
         """xpic_collide or xpic_collide_weighted -> (Context.collide's dict, the entry point's counters)"""
         p = CollisionParams(float(strength), 0.0 if dt is None else float(dt), int(seed))
         o = np.zeros(counters)
-        self._ck(entry(self.h, int(sort_a), int(sort_b), C.byref(p), step, _dp(o)))
+        self._ck(entry(self.h, int(sort_a), int(sort_b), C.byref(p), int(step), _dp(o)))
         return dict(pairs=int(o[0]), skipped=int(o[1]), sigma2_sum=float(o[2]), sigma2_over_1=int(o[3])), o
 
     def collide_weighted(self, sort_a, sort_b, strength, step, seed=0, dt=None):
@@ -735,7 +587,7 @@ class Context:
         heavier-weighted one with probability w_min / w_max -> Context.collide's dict plus the heavier-side updates made
         (heavy_updates) and rejected (heavy_rejected), summed over the slabs.  Momentum and energy are conserved in
         expectation only.  dt: None for the context's."""
-        out, o = self._collide(self.L.xpic_collide_weighted, sort_a, sort_b, strength, int(step), seed, dt, 6)
+        out, o = self._collide(self.L.xpic_collide_weighted, sort_a, sort_b, strength, step, seed, dt, 6)
         return dict(out, heavy_updates=int(o[4]), heavy_rejected=int(o[5]))
 
     def collide_info(self):
@@ -753,27 +605,26 @@ class Context:
     def set_mirror_field(self, D, R, I, field=B0):
         """SetApproximateMirrorField: field += the paraxial field of two coils of radius R and current I at z = -D / 2 and
         z = +D / 2, as the reference writes it (both transverse terms into the X component)"""
-        self._ck(self.L.xpic_set_mirror_field(self.h, field, C.c_double(D), C.c_double(R), C.c_double(I)))
+        self._ck(self.L.xpic_set_mirror_field(self.h, field, D, R, I))
 
     def cell_traversal(self, end, start, max_pts=8):
         end, start = np.ascontiguousarray(end, dtype=np.float64), np.ascontiguousarray(start, dtype=np.float64)
         n = end.shape[0]
         pts = np.zeros((n, max_pts, 3))
         counts = np.zeros(n, dtype=np.int32)
-        self._ck(self.L.xpic_cell_traversal(self.h, C.c_int64(n), _dp(end), _dp(start), max_pts, _dp(pts),
-                                            counts.ctypes.data_as(C.POINTER(C.c_int))))
+        self._ck(self.L.xpic_cell_traversal(self.h, n, _dp(end), _dp(start), max_pts, _dp(pts), _i32p(counts)))
         return pts, counts
 
     def implicit_esirkepov_interpolate(self, rn, r0):
         rn, r0 = np.ascontiguousarray(rn, dtype=np.float64), np.ascontiguousarray(r0, dtype=np.float64)
         Ep, Bp = np.zeros_like(rn), np.zeros_like(rn)
-        self._ck(self.L.xpic_implicit_esirkepov_interpolate(self.h, C.c_int64(rn.shape[0]), _dp(rn), _dp(r0), _dp(Ep), _dp(Bp)))
+        self._ck(self.L.xpic_implicit_esirkepov_interpolate(self.h, rn.shape[0], _dp(rn), _dp(r0), _dp(Ep), _dp(Bp)))
         return Ep, Bp
 
     def implicit_esirkepov_decompose(self, alpha, v, rn, r0, field):
         alpha, v = np.ascontiguousarray(alpha, dtype=np.float64), np.ascontiguousarray(v, dtype=np.float64)
         rn, r0 = np.ascontiguousarray(rn, dtype=np.float64), np.ascontiguousarray(r0, dtype=np.float64)
-        self._ck(self.L.xpic_implicit_esirkepov_decompose(self.h, C.c_int64(rn.shape[0]), _dp(alpha), _dp(v), _dp(rn), _dp(r0), field))
+        self._ck(self.L.xpic_implicit_esirkepov_decompose(self.h, rn.shape[0], _dp(alpha), _dp(v), _dp(rn), _dp(r0), field))
 
     # ---- drift-kinetic pusher (include/xpic_hip.h: xpic_drift_kinetic_*); particles are records {x, y, z, p_parallel,
     # p_perp, mu_p} (guiding_centre), gradB_field a field id filled with grad |B| or None
@@ -785,7 +636,7 @@ class Context:
         """DriftKineticEsirkepov::interpolate -> (E_p, B_p, gradB_p): E over the segment r0 -> rn, B and grad B at rn"""
         rn, r0 = np.ascontiguousarray(rn, dtype=np.float64), np.ascontiguousarray(r0, dtype=np.float64)
         Ep, Bp, gBp = np.zeros_like(rn), np.zeros_like(rn), np.zeros_like(rn)
-        self._ck(self.L.xpic_drift_kinetic_interpolate(self.h, C.c_int64(rn.shape[0]), _dp(rn), _dp(r0),
+        self._ck(self.L.xpic_drift_kinetic_interpolate(self.h, rn.shape[0], _dp(rn), _dp(r0),
                                                        -1 if gradB_field is None else int(gradB_field), _dp(Ep), _dp(Bp), _dp(gBp)))
         return Ep, Bp, gBp
 
@@ -795,9 +646,8 @@ class Context:
         pn = np.zeros_like(p0)
         its = np.zeros(p0.shape[0], dtype=np.int32)
         P = self._dk_params(qm, mp, dt, eps, delta, maxit)
-        self._ck(self.L.xpic_drift_kinetic_push(self.h, C.c_int64(p0.shape[0]), C.byref(P),
-                                                -1 if gradB_field is None else int(gradB_field), _dp(p0), _dp(pn),
-                                                its.ctypes.data_as(C.POINTER(C.c_int))))
+        self._ck(self.L.xpic_drift_kinetic_push(self.h, p0.shape[0], C.byref(P), -1 if gradB_field is None else int(gradB_field),
+                                                _dp(p0), _dp(pn), _i32p(its)))
         return pn, its
 
     def drift_kinetic_trace(self, state, steps, qm, mp, dt, gradB_field=None, sample_every=0, eps=1e-12, delta=1e-12, maxit=30):
@@ -806,10 +656,8 @@ class Context:
         state, samples, _, _, _, tot, mx = self._open_args(state, steps, sample_every, None, None, 0, "never", True)
         n = state.shape[0]
         P = self._dk_params(qm, mp, dt, eps, delta, maxit)
-        self._ck(self.L.xpic_drift_kinetic_trace(self.h, C.c_int64(n), C.byref(P), -1 if gradB_field is None else int(gradB_field),
-                                                 C.c_int64(int(steps)), C.c_int64(int(sample_every)), _dp(state),
-                                                 _dp(samples) if sample_every else None, tot.ctypes.data_as(C.POINTER(C.c_int64)),
-                                                 mx.ctypes.data_as(C.POINTER(C.c_int))))
+        self._ck(self.L.xpic_drift_kinetic_trace(self.h, n, C.byref(P), -1 if gradB_field is None else int(gradB_field),
+                                                 int(steps), int(sample_every), _dp(state), _dp(samples), _i64p(tot), _i32p(mx)))
         return state, samples, tot, mx
 
     # ---- full-orbit pusher (include/xpic_hip.h: xpic_full_orbit_*); particles are Point records {x, y, z, px, py, pz},
@@ -825,8 +673,7 @@ class Context:
         pn = np.zeros_like(p0)
         its = np.zeros(p0.shape[0], dtype=np.int32)
         P = self._fo_params(scheme, qm, dt, atol, rtol, maxit)
-        self._ck(self.L.xpic_full_orbit_push(self.h, C.c_int64(p0.shape[0]), C.byref(P), _dp(p0), _dp(pn),
-                                             its.ctypes.data_as(C.POINTER(C.c_int))))
+        self._ck(self.L.xpic_full_orbit_push(self.h, p0.shape[0], C.byref(P), _dp(p0), _dp(pn), _i32p(its)))
         return pn, its
 
     def full_orbit_trace(self, state, steps, scheme, qm, dt, sample_every=0, atol=1e-7, rtol=1e-7, maxit=30):
@@ -835,9 +682,8 @@ class Context:
         state, samples, _, _, _, tot, mx = self._open_args(state, steps, sample_every, None, None, 0, "never", True)
         n = state.shape[0]
         P = self._fo_params(scheme, qm, dt, atol, rtol, maxit)
-        self._ck(self.L.xpic_full_orbit_trace(self.h, C.c_int64(n), C.byref(P), C.c_int64(int(steps)),
-                                              C.c_int64(int(sample_every)), _dp(state), _dp(samples) if sample_every else None,
-                                              tot.ctypes.data_as(C.POINTER(C.c_int64)), mx.ctypes.data_as(C.POINTER(C.c_int))))
+        self._ck(self.L.xpic_full_orbit_trace(self.h, n, C.byref(P), int(steps), int(sample_every), _dp(state), _dp(samples),
+                                              _i64p(tot), _i32p(mx)))
         return state, samples, tot, mx
 
     # ---- open-trap traces (include/xpic_hip.h: xpic_trace_region): the traces above with RemoveParticles' corner rule at
@@ -854,9 +700,17 @@ class Context:
         samples = np.zeros((nsamp, n, 6)) if sample_every and keep_samples else None
         alive = np.zeros(nsamp, dtype=np.int64) if sample_every else None
         ex = np.full(n, -1, dtype=np.int64) if exit_step is None else np.array(exit_step, dtype=np.int64).reshape(n)
+        # (samples and alive are None exactly where the library is to get a null pointer: _dp and _i64p pass None through)
         kind, gp = (GEOM_NONE, [0.0] * 7) if region is None else _geom7(region)
         reg = TraceRegion(kind, int(COMPACT.get(compact, compact)), (C.c_double * 7)(*gp[:7]), int(step0))
         return state, samples, alive, ex, reg, np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int32)
+
+    @staticmethod
+    def _trace_tail(steps, sample_every, state, samples, tot, mx, reg, ex, alive, removed):
+        """the ten arguments from steps to removed that every trace with a region takes, from _open_args' arrays.  ex None:
+        the closed trace, the library gets no exit_step and no removed"""
+        return [int(steps), int(sample_every), _dp(state), _dp(samples), _i64p(tot), _i32p(mx), C.byref(reg), _i64p(ex),
+                _i64p(alive), None if ex is None else C.byref(removed)]
 
     def full_orbit_trace_open(self, state, steps, scheme, qm, dt, region, sample_every=0, exit_step=None, step0=0,
                               compact="never", keep_samples=True, atol=1e-7, rtol=1e-7, maxit=30):
@@ -864,11 +718,10 @@ class Context:
         state, samples, alive, ex, reg, tot, mx = self._open_args(state, steps, sample_every, region, exit_step, step0, compact,
                                                                       keep_samples)
         P = self._fo_params(scheme, qm, dt, atol, rtol, maxit)
-        removed, i64 = C.c_int64(), C.POINTER(C.c_int64)
+        removed = C.c_int64()
         self._ck(self.L.xpic_full_orbit_trace_open(
-            self.h, C.c_int64(state.shape[0]), C.byref(P), C.c_int64(int(steps)), C.c_int64(int(sample_every)), _dp(state),
-            None if samples is None else _dp(samples), tot.ctypes.data_as(i64), mx.ctypes.data_as(C.POINTER(C.c_int)),
-            C.byref(reg), ex.ctypes.data_as(i64), alive.ctypes.data_as(i64) if sample_every else None, C.byref(removed)))
+            self.h, state.shape[0], C.byref(P),
+            *self._trace_tail(steps, sample_every, state, samples, tot, mx, reg, ex, alive, removed)))
         return OpenTrace(state, samples, ex, alive, removed.value, tot, mx)
 
     def drift_kinetic_trace_open(self, state, steps, qm, mp, dt, region, gradB_field=None, sample_every=0, exit_step=None,
@@ -877,12 +730,10 @@ class Context:
         state, samples, alive, ex, reg, tot, mx = self._open_args(state, steps, sample_every, region, exit_step, step0, compact,
                                                                       keep_samples)
         P = self._dk_params(qm, mp, dt, eps, delta, maxit)
-        removed, i64 = C.c_int64(), C.POINTER(C.c_int64)
+        removed = C.c_int64()
         self._ck(self.L.xpic_drift_kinetic_trace_open(
-            self.h, C.c_int64(state.shape[0]), C.byref(P), -1 if gradB_field is None else int(gradB_field),
-            C.c_int64(int(steps)), C.c_int64(int(sample_every)), _dp(state), None if samples is None else _dp(samples),
-            tot.ctypes.data_as(i64), mx.ctypes.data_as(C.POINTER(C.c_int)), C.byref(reg), ex.ctypes.data_as(i64),
-            alive.ctypes.data_as(i64) if sample_every else None, C.byref(removed)))
+            self.h, state.shape[0], C.byref(P), -1 if gradB_field is None else int(gradB_field),
+            *self._trace_tail(steps, sample_every, state, samples, tot, mx, reg, ex, alive, removed)))
         return OpenTrace(state, samples, ex, alive, removed.value, tot, mx)
 
     def _compare_trace(self, fn, mismatch, p, centres, width, middle, steps, scheme, qm, mp, dt, sample_every, stats, atol,
@@ -903,11 +754,8 @@ class Context:
                     for m in members]
         F = self._fo_params(scheme, qm, dt, atol, rtol, maxit)
         D = self._dk_params(qm, mp, dt, eps, delta, dk_maxit)
-        types = (C.POINTER(C.c_int64), C.POINTER(C.c_int))
-        self._ck(fn(
-            self.h, C.c_int64(n), C.byref(F), C.byref(D), *middle, C.c_int64(int(steps)), C.c_int64(int(sample_every)),
-            *[None if m is None else _dp(m) for m in members], _dp(stats), _dp(curve) if sample_every else None,
-            *[None if a is None else a.ctypes.data_as(t) for pair in counters for a, t in zip(pair, types)]))
+        self._ck(fn(self.h, n, C.byref(F), C.byref(D), *middle, int(steps), int(sample_every), *[_dp(m) for m in members],
+                    _dp(stats), _dp(curve), *[a for tot, mx in counters for a in (_i64p(tot), _i32p(mx))]))
         return members[0], members[1:], stats, curve, counters
 
     # ---- paired trace (include/xpic_hip.h: xpic_paired_trace): full_orbit_trace of p and drift_kinetic_trace of state
@@ -930,14 +778,13 @@ class Context:
         """-> (E, B, gradB) of the model at the positions r [n][3]"""
         r = np.ascontiguousarray(r, dtype=np.float64).reshape(-1, 3)
         E, B, gB = np.zeros_like(r), np.zeros_like(r), np.zeros_like(r)
-        self._ck(self.L.xpic_model_fields(self.h, None if model is None else C.byref(model), C.c_int64(r.shape[0]), _dp(r),
-                                          _dp(E), _dp(B), _dp(gB)))
+        self._ck(self.L.xpic_model_fields(self.h, model, r.shape[0], _dp(r), _dp(E), _dp(B), _dp(gB)))
         return E, B, gB
 
     def set_model_field(self, model, E_field=E, B_field=B, gradB_field=None):
         """fills the grid vectors from the model, every component of node (i, j, k) at (i dx, j dy, k dz); None: skipped"""
         ids = [-1 if f is None else int(f) for f in (E_field, B_field, gradB_field)]
-        self._ck(self.L.xpic_set_model_field(self.h, None if model is None else C.byref(model), *ids))
+        self._ck(self.L.xpic_set_model_field(self.h, model, *ids))
 
     _ABSENT = object()  # _model_trace: the library function has no such argument
 
@@ -953,20 +800,17 @@ class Context:
         absent = self._ABSENT
         if sums is not absent and sums is not None:
             sums = np.zeros((n, 4)) if sums is True else np.array(sums, dtype=np.float64).reshape(n, 4)
-        removed, i64 = C.c_int64(), C.POINTER(C.c_int64)
-        bare = region is None and exit_step is None  # the closed trace: the library gets no exit_step and no removed
-        args = [self.h, C.c_int64(n), C.byref(P), None if model is None else C.byref(model)]
+        removed = C.c_int64()
+        bare = region is None and exit_step is None  # the closed trace
+        args = [self.h, n, C.byref(P), model]
         if envelope is not absent:
-            args.append(None if envelope is None else C.byref(envelope))
-        args += [C.c_int64(int(steps)), C.c_int64(int(sample_every)), _dp(state), None if samples is None else _dp(samples),
-                 tot.ctypes.data_as(i64), mx.ctypes.data_as(C.POINTER(C.c_int)), C.byref(reg),
-                 None if bare else ex.ctypes.data_as(i64), alive.ctypes.data_as(i64) if sample_every else None,
-                 None if bare else C.byref(removed)]
+            args.append(envelope)
+        args += self._trace_tail(steps, sample_every, state, samples, tot, mx, reg, None if bare else ex, alive, removed)
         if sums is not absent:
-            args.append(None if sums is None else _dp(sums))
+            args.append(_dp(sums))
         if collisions is not absent:
             coll = np.zeros(4)
-            args += [None if collisions is None else C.byref(collisions), _dp(coll)]
+            args += [collisions, _dp(coll)]
         self._ck(fn(*args))
         if collisions is not absent:
             return state, samples, ex, alive, removed.value, tot, mx, coll
@@ -1036,7 +880,7 @@ class Context:
         vth = np.ascontiguousarray(np.broadcast_to(np.asarray(vth, dtype=np.float64), shape))
         if drift is not None:
             drift = np.ascontiguousarray(np.broadcast_to(np.asarray(drift, dtype=np.float64), shape + (3,)))
-        self._ck(self.L.xpic_background_set(self.h, int(slot), _dp(n), _dp(vth), None if drift is None else _dp(drift)))
+        self._ck(self.L.xpic_background_set(self.h, int(slot), _dp(n), _dp(vth), _dp(drift)))
 
     def background_get(self, slot):
         """-> (n, vth, drift) of a slot; an empty slot raises"""
@@ -1059,17 +903,15 @@ class Context:
         between params and steps; profile: a list of slots (-1: the uniform background of `collisions`) or None"""
         state, samples, alive, ex, reg, tot, mx = self._open_args(state, steps, sample_every, region, exit_step, step0, compact,
                                                                       keep_samples)
-        removed, i64 = C.c_int64(), C.POINTER(C.c_int64)
-        bare = region is None and exit_step is None  # the closed trace: the library gets no exit_step and no removed
+        removed = C.c_int64()
+        bare = region is None and exit_step is None  # the closed trace
         prof = None if profile is None else (C.c_int32 * len(profile))(*[int(s) for s in profile])
         if prof is not None and collisions is not None and len(profile) != collisions.nbg:
             raise XpicError("profile: one entry per background")
         coll = np.zeros(4)
-        self._ck(fn(self.h, C.c_int64(state.shape[0]), C.byref(P), *middle, C.c_int64(int(steps)),
-                    C.c_int64(int(sample_every)), _dp(state), None if samples is None else _dp(samples),
-                    tot.ctypes.data_as(i64), mx.ctypes.data_as(C.POINTER(C.c_int)), C.byref(reg),
-                    None if bare else ex.ctypes.data_as(i64), alive.ctypes.data_as(i64) if sample_every else None,
-                    None if bare else C.byref(removed), None if collisions is None else C.byref(collisions), prof, _dp(coll)))
+        self._ck(fn(self.h, state.shape[0], C.byref(P), *middle,
+                    *self._trace_tail(steps, sample_every, state, samples, tot, mx, reg, None if bare else ex, alive, removed),
+                    collisions, prof, _dp(coll)))
         return CollisionalTrace(state, samples, ex, alive, removed.value, tot, mx, coll)
 
     def full_orbit_trace_collisional(self, state, steps, scheme, qm, dt, collisions, profile=None, region=None,
@@ -1092,8 +934,7 @@ class Context:
     def envelope_factors(self, envelope, dt, step0, nsteps):
         """-> the factors of steps step0 .. step0 + nsteps - 1, evaluated on the device as the traces evaluate them"""
         out = np.zeros(max(int(nsteps), 0))
-        self._ck(self.L.xpic_envelope_factors(self.h, None if envelope is None else C.byref(envelope), C.c_double(float(dt)),
-                                              C.c_int64(int(step0)), C.c_int64(int(nsteps)), _dp(out)))
+        self._ck(self.L.xpic_envelope_factors(self.h, envelope, float(dt), int(step0), int(nsteps), _dp(out)))
         return out
 
     # ---- triplet trace (include/xpic_hip.h: xpic_triplet_trace): model_drift_kinetic_trace of state_model,
@@ -1108,7 +949,7 @@ class Context:
         p, (sm, sg), stats, curve, (fo, dkm, dkg) = self._compare_trace(
             self.L.xpic_triplet_trace, "triplet_trace: p, state_model and state_grid hold different numbers of particles", p,
             [state_model, state_grid], 7,
-            [None if model is None else C.byref(model), int(grid), -1 if gradB_field is None or not grid else int(gradB_field)],
+            [model, int(grid), -1 if gradB_field is None or not grid else int(gradB_field)],
             steps, scheme, qm, mp, dt, sample_every, stats, atol, rtol, maxit, eps, delta, dk_maxit)
         return TripletTrace(p, sm, sg, stats, curve, *fo, *dkm, *dkg)
 
@@ -1137,7 +978,7 @@ class Context:
 
     def probe_copy_bandwidth(self, nbytes=1 << 30, reps=10):
         o = C.c_double()
-        self._ck(self.L.xpic_probe_copy_bandwidth(self.h, C.c_int64(nbytes), reps, C.byref(o)))
+        self._ck(self.L.xpic_probe_copy_bandwidth(self.h, nbytes, reps, C.byref(o)))
         return o.value
 
 
