@@ -1,6 +1,6 @@
 // batch_host.cpp -- the host half of xpic_amd/csrc/batch.h (the part above its __HIPCC__ line: transposition,
-// trace_sample_bytes, trace_compacts, fill_frozen_samples) in a stand-alone program, so that a plain host compiler and its
-// sanitizers can run it without a GPU, on the shapes of tests/test_gpu_open_trace.py: 775 particles, 21 sample rows,
+// trace_sample_bytes and the record of a call's arrays it reads, trace_compacts, fill_frozen_samples) in a stand-alone
+// program, so that a plain host compiler and its sanitizers can run it without a GPU, on the shapes of tests/test_gpu_open_trace.py: 775 particles, 21 sample rows,
 // particles removed before their first step, after the 7th, the 146th and the 149th, and one that entered removed; and the
 // windowed transposition of a comparison trace's statistics: 775 records of width 7 with the window 3 .. 6 (columns 0 .. 2
 // keep their sentinels), width 4 with the full window, and no record at all.
@@ -19,6 +19,32 @@ int main()
   int64_t nsamp;
   assert(trace_sample_bytes(n, steps, every, true, &nsamp) == 48 * n * 21 && nsamp == 21);
   std::vector<double> state(6 * n), soa, back(6 * n), samples(6 * n * nsamp, -1.0);
+  // the record of a call's arrays gives the same rows; only a call with samples counts particles into the bytes
+  std::vector<int64_t> rows(21);
+  TraceArrays A{n, steps, every, state.data(), samples.data(), nullptr, nullptr, nullptr, nullptr, nullptr, false, nullptr};
+  nsamp = -1;
+  assert(trace_sample_bytes(A, &nsamp) == 48 * n * 21 && nsamp == 21);
+  A.samples = nullptr; // neither samples nor alive: no row, and sample_every is not read
+  A.sample_every = 0;
+  assert(trace_sample_bytes(A, &nsamp) == 0 && nsamp == 0);
+  A.alive = rows.data(); // alive alone: the rows are counted, no particle is
+  A.sample_every = every;
+  assert(trace_sample_bytes(A, &nsamp) == 0 && nsamp == 21);
+  A.samples = samples.data();
+  A.n = 0; // zero particles
+  assert(trace_sample_bytes(A, &nsamp) == 0 && nsamp == 21);
+  A.n = n;
+  A.sample_every = steps + 1; // sample_every larger than steps: no row
+  assert(trace_sample_bytes(A, &nsamp) == 0 && nsamp == 0);
+  A.sample_every = 1; // the refusal above 2^46 bytes: a row of 2^36 particles is 3 * 2^40 bytes
+  A.n = (int64_t)1 << 36;
+  A.steps = 21; // 63 * 2^40 bytes
+  assert(trace_sample_bytes(A, &nsamp) == 48 * A.n * 21 && nsamp == 21);
+  A.steps = 22; // 66 * 2^40 bytes: refused
+  assert(trace_sample_bytes(A, &nsamp) == -1);
+  A.steps = INT64_MAX; // the product overflows: refused
+  assert(trace_sample_bytes(A, &nsamp) == -1);
+  nsamp = 21;
   for (size_t i = 0; i < state.size(); ++i) state[i] = (double)i;
   to_soa(state.data(), n, soa);
   to_aos(soa.data(), n, back.data());

@@ -45,6 +45,28 @@ inline int64_t trace_sample_bytes(int64_t n, int64_t steps, int64_t sample_every
   return fits ? bytes : -1;
 }
 
+// What a trace call of one batch was given by its caller (trace_call.h, batch_trace): host pointers and counts as the C
+// entry points take them.
+struct TraceArrays {
+  int64_t n;            // particles
+  int64_t steps;        // steps of this call
+  int64_t sample_every; // a sample row after every sample_every-th step; >= 1 when samples or alive is given
+  double* state_6;      // [n][6], in and out
+  double* samples;      // [nsamp][n][6], or null
+  int64_t* it_sum;      // [n] the sum and
+  int* it_max;          // [n] the maximum of each particle's iteration counts; either may be null without `counters`
+  int64_t* exit_step;   // [n] in and out as the open entry points document it; null (a closed trace): all enter alive
+  int64_t* alive;       // [nsamp], or null
+  int64_t* removed;     // one count; null (a closed trace): nothing can leave, nothing is read back between launches
+  bool counters;        // the launches count iterations: it_sum and it_max are staged, zeroed, and come back
+  double* sums_4;       // [n][4] in and out, staged as [4][n] around the launches (the timed full orbit's), or null
+};
+// the sample buffer of such a call: its rows hold particles only when samples are asked for
+inline int64_t trace_sample_bytes(const TraceArrays& A, int64_t* nsamp)
+{
+  return trace_sample_bytes(A.samples ? A.n : 0, A.steps, A.sample_every, A.samples || A.alive, nsamp);
+}
+
 // An open trace (batch_trace): whether the list of `listed` entries, `live` of them alive, is rebuilt before the next
 // launch.  policy: enum xpic_trace_compact (0: when fewer than half are alive, 1: never, 2: whenever one is not).
 inline bool trace_compacts(int policy, int64_t live, int64_t listed)
@@ -159,6 +181,24 @@ struct CompareDev {
   unsigned long long* curve;
 };
 
+// what one launch of a trace of one batch gets (batch_trace), typed as the kernels take it: the launch runs the steps
+// first + 1 .. first + ns over the m entries of list
+struct TraceDev {
+  double* s;                   // the state [6][n]
+  const long long* list;       // the particles the launch covers; null: the particles 0 .. m - 1
+  long m;                      // its entries
+  long first;                  // steps of the call before this launch
+  int ns;                      // steps of this launch
+  long nsamp;                  // rows of samples and of alive
+  double* samples;             // [nsamp][6][n]; null: the call has none
+  long long* it_sum;           // [n] and
+  int* it_max;                 // [n]; null in a call without counters
+  long long* exit_step;        // [n]; a closed trace's is a stand-in, which its kernels do not take
+  unsigned long long* alive;   // [nsamp], zeroed before the first launch, the kernel adds to its rows; null: none
+  unsigned long long* removed; // one count, zeroed before the first launch, the kernel adds to it
+  double* extra;               // [4][n] of the caller: the timed trace's sums, the collisional traces' tallies, or null
+};
+
 // `steps` steps of n > 0 lanes in place.  The running maxima stats [n][stats_width] are in and out: the stats_w columns
 // from stats_first on travel, staged as [stats_w][n], and the other columns of the caller's array are neither read nor
 // written (a pair: 4 / 0 / 4; a triplet: 7 / 0 / 7; its grid-less pair: 7 / 3 / 4).  curve [nsamp][curve_width] (null with
@@ -226,28 +266,24 @@ int batch_compare_trace(xpic_ctx* c, const char* label, int launch_steps, int64_
 int live_compact(xpic_ctx* c, const char* label, const int64_t* exit_step, const int64_t* list, int64_t m, int64_t cap,
   int64_t* out, double* blk, int64_t* off);
 
-// `steps` steps of n > 0 particles in place in state_6, the particles kept on the device, with the region rule of an open
-// trace (include/xpic_hip.h: xpic_trace_region) when the kernel applies one.  nsamp (trace_sample_bytes)
-// counts the rows of samples [nsamp][n][6] and of alive [nsamp], either of which may be null; with `counters` the sum and
-// the maximum of each particle's iteration counts.  exit_step [n] in and out and *removed as the open entry points
-// document them.  A closed trace passes a null exit_step (everybody enters alive: a stand-in of -1 is staged) and a null
-// removed (nothing can leave: see below).  launch(s, list, m, first, nsteps, samples, it_sum, it_max, exit_step, alive,
-// removed) starts the kernel for steps first + 1 .. first + nsteps over the m entries of list (null: the particles
-// 0 .. m - 1); samples, it_sum / it_max and alive are null where the call has none; the kernel adds to alive[row] and to
-// *removed (device, zeroed here); each launch is timed under `label`.  With `removed`, the count removed so far comes back
-// after every launch (8 bytes), so the host knows how many entries are alive: when none is, the remaining launches are
-// skipped, and by `policy` (trace_compacts) the list is rebuilt for the next launch, timed under `compact_label`.  Without
-// it nothing is read back and nothing synchronises between the launches.  The sample rows behind a removed particle's last
-// step are filled here, on the host, from the final state (fill_frozen_samples): a launch no longer covers a particle that
-// compaction has dropped.
+// The steps of A (TraceArrays, A.n > 0) in place in A.state_6, the particles kept on the device, with the region rule of
+// an open trace (include/xpic_hip.h: xpic_trace_region) when the kernel applies one.  `d` (TraceDev) comes
+// with nsamp (trace_sample_bytes) and extra set by the caller; its other members are filled here, and launch(d) starts
+// the kernel, each launch timed under `label`.  A.sums_4 is the caller's to stage (trace_call.h).  With A.removed, the
+// count removed so far comes back after every launch (8 bytes), so the host knows how many entries are alive: when none
+// is, the remaining launches are skipped, and by `policy` (trace_compacts) the list is rebuilt for the next launch, timed
+// under `compact_label`.  Without it nothing is read back and nothing synchronises between the launches.  The sample rows
+// behind a removed particle's last step are filled here, on the host, from the final state (fill_frozen_samples): a launch
+// no longer covers a particle that compaction has dropped.
 template <class Launch>
-int batch_trace(xpic_ctx* c, const char* label, const char* compact_label, int launch_steps, int64_t n, int64_t steps,
-  int64_t sample_every, int64_t nsamp, bool counters, int policy, int64_t step0, double* state_6, double* samples,
-  int64_t* it_sum, int* it_max, int64_t* exit_step, int64_t* alive, int64_t* removed, Launch launch)
+int batch_trace(xpic_ctx* c, const char* label, const char* compact_label, int launch_steps, const TraceArrays& A, int policy,
+  int64_t step0, TraceDev d, Launch launch)
 {
+  const int64_t n = A.n, steps = A.steps, nsamp = d.nsamp;
+  int64_t* exit_step = A.exit_step;
   const size_t row = (size_t)6 * n; // doubles of one state
   std::vector<double> h, hs;
-  to_soa(state_6, n, h);
+  to_soa(A.state_6, n, h);
   std::vector<int64_t> exit_in(n, -1), exit_own(exit_step ? 0 : n); // the closed trace's stand-ins
   if (exit_step) exit_in.assign(exit_step, exit_step + n);
   else exit_step = exit_own.data();
@@ -258,29 +294,32 @@ int batch_trace(xpic_ctx* c, const char* label, const char* compact_label, int l
   DevScratch<int> mx;
   XPIC_CALL(s.alloc(row)); XPIC_CALL(ex.alloc(n)); XPIC_CALL(rm.alloc(1));
   XPIC_CALL(zero(rm, 1, c->stream));
-  if (counters) {
+  if (A.counters) {
     XPIC_CALL(tot.alloc(n)); XPIC_CALL(mx.alloc(n));
     XPIC_CALL(zero(tot, n, c->stream)); XPIC_CALL(zero(mx, n, c->stream));
   }
-  if (samples && nsamp > 0) XPIC_CALL(sm.alloc(row * nsamp));
-  if (alive && nsamp > 0) {
+  if (A.samples && nsamp > 0) XPIC_CALL(sm.alloc(row * nsamp));
+  if (A.alive && nsamp > 0) {
     XPIC_CALL(al.alloc(nsamp));
     XPIC_CALL(zero(al, nsamp, c->stream));
   }
   XPIC_CALL(upload(s, h.data(), row, c->stream));
   XPIC_CALL(upload(ex, exit_in.data(), n, c->stream));
+  d.s = s.p; d.samples = sm.p; d.exit_step = (long long*)ex.p;
+  d.it_sum = (long long*)tot.p; d.it_max = mx.p;
+  d.alive = (unsigned long long*)al.p; d.removed = (unsigned long long*)rm.p;
   const int64_t* list = nullptr; // the entries the next launch covers: null = every particle
   int64_t listed = n, gone = 0;
   int next = 0;                  // the buffer the next compaction writes
   for (int64_t first = 0; first < steps && live > 0; first += launch_steps) {
-    const int ns = (int)std::min<int64_t>(launch_steps, steps - first);
+    d.list = (const long long*)list; d.m = (long)listed;
+    d.first = (long)first; d.ns = (int)std::min<int64_t>(launch_steps, steps - first);
     {
       Timed t(c, label);
-      launch(s.p, list, (long)listed, (long)first, ns, sm.p, (long long*)tot.p, mx.p, (long long*)ex.p,
-        (unsigned long long*)al.p, (unsigned long long*)rm.p);
+      launch(d);
       XPIC_HIP(hipGetLastError());
     }
-    if (!removed) continue;
+    if (!A.removed) continue;
     int64_t g = 0;
     XPIC_CALL(download(&g, rm, 1, c->stream));
     XPIC_HIP(hipStreamSynchronize(c->stream));
@@ -301,22 +340,22 @@ int batch_trace(xpic_ctx* c, const char* label, const char* compact_label, int l
   }
   XPIC_CALL(download(h.data(), s, row, c->stream));
   XPIC_CALL(download(exit_step, ex, n, c->stream));
-  if (counters) {
-    XPIC_CALL(download(it_sum, tot, n, c->stream));
-    XPIC_CALL(download(it_max, mx, n, c->stream));
+  if (A.counters) {
+    XPIC_CALL(download(A.it_sum, tot, n, c->stream));
+    XPIC_CALL(download(A.it_max, mx, n, c->stream));
   }
   if (sm.p) {
     hs.resize(row * nsamp);
     XPIC_CALL(download(hs.data(), sm, row * nsamp, c->stream)); // the samples, once
   }
-  if (al.p) XPIC_CALL(download(alive, al, nsamp, c->stream));
+  if (al.p) XPIC_CALL(download(A.alive, al, nsamp, c->stream));
   XPIC_HIP(hipStreamSynchronize(c->stream));
-  to_aos(h.data(), n, state_6);
+  to_aos(h.data(), n, A.state_6);
   if (sm.p) {
-    for (int64_t k = 0; k < nsamp; ++k) to_aos(hs.data() + row * k, n, samples + row * k);
-    fill_frozen_samples(n, nsamp, sample_every, step0, exit_in.data(), exit_step, state_6, samples);
+    for (int64_t k = 0; k < nsamp; ++k) to_aos(hs.data() + row * k, n, A.samples + row * k);
+    fill_frozen_samples(n, nsamp, A.sample_every, step0, exit_in.data(), exit_step, A.state_6, A.samples);
   }
-  if (removed) *removed = gone;
+  if (A.removed) *A.removed = gone;
   return 0;
 }
 

@@ -367,6 +367,14 @@ __global__ void __launch_bounds__(kBlock) k_coll_tally(long n, const double* __r
   block_reduce_store<kTally, kBlock>(t, partial, gridDim.x, blockIdx.x);
 }
 
+// the test particle of `in` (charge qm * mass) against background g -> S q_a^2 q_b^2 / m_ab^2; *mab: the reduced mass
+double coll_c0(const xpic_trace_collisions* in, const xpic_trace_background& g, double qm, double* mab)
+{
+  const double qa = qm * in->mass;
+  *mab = in->mass * g.m / (in->mass + g.m);
+  return in->strength * (qa * qa) * (g.q * g.q) / (*mab * *mab);
+}
+
 // the checks of an xpic_trace_collisions (null: no collisions) -> on: the call collides; C: what the kernels get
 int coll_setup(const std::string& who, const xpic_trace_collisions* in, double qm, double dt, bool* on, CollDev* C)
 {
@@ -390,11 +398,11 @@ int coll_setup(const std::string& who, const xpic_trace_collisions* in, double q
   C->every = in->every;
   C->seed = in->seed;
   C->particle0 = in->particle0;
-  const double qa = qm * in->mass, dtc = (double)in->every * dt;
+  const double dtc = (double)in->every * dt;
   for (int b = 0; b < in->nbg; ++b) {
     const xpic_trace_background& g = in->bg[b];
-    const double mab = in->mass * g.m / (in->mass + g.m);
-    const double c0 = in->strength * (qa * qa) * (g.q * g.q) / (mab * mab);
+    double mab;
+    const double c0 = coll_c0(in, g, qm, &mab);
     C->bg[b].cdt = c0 * g.n * dtc;
     C->bg[b].fa = mab / in->mass;
     C->bg[b].vth = g.vth;
@@ -426,30 +434,25 @@ struct Tally {
   }
 };
 
-TraceEntry coll_entry(const std::string& who)
+// no tally has moved: a call that did not collide (rc: what the trace it was handed to returned), or one yet to be summed
+int coll_none(int rc, double* coll_4)
 {
-  return {who.c_str(), "the particle array", "an iteration counter", "an iteration counter", false};
+  if (rc == 0 && coll_4)
+    for (int k = 0; k < kTally; ++k) coll_4[k] = 0.0;
+  return rc;
 }
 
 // what the four colliding entry points do around trace_call: the tallies before the first launch, coll_4 after the last.
-// launch: trace_call's, with the tallies in place of the sums
+// launch: trace_call's, with the tallies as TraceDev's extra
 template <class Launch>
-int coll_trace(xpic_ctx* ctx, const std::string& who, const char* label, const char* compact_label, int64_t n, bool counters,
-  int64_t steps, int64_t sample_every, double* state_6, double* samples, int64_t* it_sum, int* it_max, const OpenRegion& R,
-  int policy, int64_t* exit_step, int64_t* alive, int64_t* removed, double* coll_4, Launch launch)
+int coll_trace(xpic_ctx* ctx, const TraceEntry& E, const TraceArrays& A, const OpenRegion& R, int policy, double* coll_4,
+  Launch launch)
 {
-  const bool runs = n > 0 && steps > 0;
+  const bool runs = A.n > 0 && A.steps > 0;
   Tally tally;
-  if (runs) XPIC_CALL(tally.begin(ctx, n));
-  XPIC_CALL(trace_call(ctx, coll_entry(who), label, compact_label, kLaunchSteps, n, counters, steps, sample_every, state_6,
-    samples, it_sum, it_max, R, policy, exit_step, alive, removed, nullptr,
-    [&](double* s, const long long* list, long m, long first, int ns, long nsamp, double* sm, long long* sum, int* mx,
-      long long* ex, unsigned long long* al, unsigned long long* rm, double*) {
-      launch(s, list, m, first, ns, nsamp, sm, sum, mx, ex, al, rm, tally.d.p);
-    }));
-  if (coll_4)
-    for (int k = 0; k < kTally; ++k) coll_4[k] = 0.0;
-  if (runs) XPIC_CALL(tally.end(ctx, n, coll_4));
+  if (runs) XPIC_CALL(tally.begin(ctx, A.n));
+  XPIC_CALL(coll_none(trace_call(ctx, E, kLaunchSteps, A, R, policy, tally.d.p, launch), coll_4));
+  if (runs) XPIC_CALL(tally.end(ctx, A.n, coll_4));
   return 0;
 }
 
@@ -468,14 +471,6 @@ int grid_check(xpic_ctx* ctx, const std::string& who, int64_t n)
   return 0;
 }
 
-// the region of a collisional grid trace: XPIC_GEOM_NONE is the closed trace, and `compact` is read
-int grid_region(const std::string& who, const xpic_trace_region* region, OpenRegion* R, int* policy)
-{
-  XPIC_CALL(trace_region(who, region, true, true, R));
-  *policy = R->kind < 0 ? (int)XPIC_COMPACT_NEVER : region->compact;
-  return 0;
-}
-
 // the checks of `profile` (null: every background is the struct's uniform one) -> what the kernels get.  Called after
 // coll_setup has accepted `in`
 int profile_setup(xpic_ctx* ctx, const std::string& who, const xpic_trace_collisions* in, const int32_t* profile, double qm,
@@ -484,34 +479,64 @@ int profile_setup(xpic_ctx* ctx, const std::string& who, const xpic_trace_collis
   *B = ProfileBg{};
   B->ncell = ctx->ncell;
   if (!in) return 0;
-  const double qa = qm * in->mass;
   B->dtc = (double)in->every * dt;
   for (int b = 0; b < in->nbg; ++b) {
     const int s = profile ? profile[b] : -1;
     XPIC_CHECK(s >= -1 && s < XPIC_TRACE_BG_MAX, who + ": a profile entry must be within -1 .. XPIC_TRACE_BG_MAX - 1");
     XPIC_CHECK(s < 0 || ctx->bg_profile[s], who + ": a profile entry names an empty slot");
-    const xpic_trace_background& g = in->bg[b];
-    const double mab = in->mass * g.m / (in->mass + g.m);
-    B->c0[b] = in->strength * (qa * qa) * (g.q * g.q) / (mab * mab); // (as coll_setup forms it)
+    double mab;
+    B->c0[b] = coll_c0(in, in->bg[b], qm, &mab);
     B->slot[b] = s < 0 ? nullptr : ctx->bg_profile[s];
   }
   return 0;
 }
 
-// a refusal of the grid trace that (a) hands the call to, under the collisional entry point's name as well
-int handed(const std::string& who, int rc)
+// The two entry points on a model, either pusher's, after model_checks.  plain: the entry point of the model trace
+// itself, which a call that does not collide is handed to, bit for bit; launch(d, R, C) starts the kernel.
+template <class Params, class Plain, class Launch>
+int coll_model_trace(xpic_ctx* ctx, const TraceEntry& E, const Params* params, const xpic_field_model* model,
+  const TraceArrays& A, const xpic_trace_region* region, const xpic_trace_collisions* collisions, double* coll_4, Plain plain,
+  Launch launch)
 {
-  if (rc != 0) set_error(who + ": " + xpic_last_error());
-  return rc;
+  bool on;
+  CollDev Cd;
+  XPIC_CALL(coll_setup(E.who, collisions, params->qm, params->dt, &on, &Cd));
+  if (!on)
+    return coll_none(plain(ctx, A.n, params, model, A.steps, A.sample_every, A.state_6, A.samples, A.it_sum, A.it_max, region,
+      A.exit_step, A.alive, A.removed), coll_4);
+  OpenRegion R;
+  XPIC_CALL(trace_region(E.who, region, true, false, &R));
+  return coll_trace(ctx, E, A, R, XPIC_COMPACT_NEVER, coll_4, [&](const TraceDev& d) { launch(d, R, Cd); });
 }
 
-// the closed trace of (a) for a call that neither collides nor has a region: alive and removed as a model trace under
-// XPIC_GEOM_NONE reports them
-void closed_counts(int64_t n, int64_t steps, int64_t sample_every, int64_t* alive, int64_t* removed)
+// The two entry points on the grid, either pusher's, after grid_check and the pusher's checks.  XPIC_GEOM_NONE is the
+// closed trace, and `compact` is read.  plain(open): the open or the closed entry point of the grid trace itself, which a
+// call that does not collide is handed to, bit for bit; launch(d, R, C, B) starts the kernel.
+template <class Params, class Plain, class Launch>
+int coll_grid_trace(xpic_ctx* ctx, const TraceEntry& E, const Params& P, const TraceArrays& A, const xpic_trace_region* region,
+  const xpic_trace_collisions* collisions, const int32_t* profile, double* coll_4, Plain plain, Launch launch)
 {
-  if (alive && sample_every >= 1)
-    for (int64_t k = 0; k < steps / sample_every; ++k) alive[k] = n;
-  if (removed) *removed = 0;
+  const std::string who = E.who;
+  bool on;
+  CollDev Cd;
+  ProfileBg Bg;
+  OpenRegion R;
+  XPIC_CALL(coll_setup(who, collisions, P.qm, P.dt, &on, &Cd));
+  XPIC_CALL(profile_setup(ctx, who, collisions, profile, P.qm, P.dt, &Bg));
+  XPIC_CALL(trace_region(who, region, true, true, &R));
+  const int policy = R.kind < 0 ? (int)XPIC_COMPACT_NEVER : region->compact;
+  if (!on && (R.kind >= 0 || !A.exit_step)) {
+    const int rc = plain(R.kind >= 0);
+    if (rc != 0) set_error(who + ": " + xpic_last_error()); // the grid trace's refusal, under this entry point's name too
+    else if (R.kind < 0) { // the closed trace: alive and removed as a model trace under XPIC_GEOM_NONE reports them
+      if (A.alive && A.sample_every >= 1)
+        for (int64_t k = 0; k < A.steps / A.sample_every; ++k) A.alive[k] = A.n;
+      if (A.removed) *A.removed = 0;
+    }
+    return coll_none(rc, coll_4);
+  }
+  if (!on) Cd.every = 1; // (no region, but an exit_step to honour: the kernel with no background)
+  return coll_trace(ctx, E, A, R, policy, coll_4, [&](const TraceDev& d) { launch(d, R, Cd, Bg); });
 }
 
 }  // namespace
@@ -528,32 +553,16 @@ int xpic_model_full_orbit_trace_collisional(xpic_ctx* ctx, int64_t n, const xpic
   const xpic_trace_collisions* collisions, double* coll_4)
 {
   const std::string who = "model_full_orbit_trace_collisional";
-  XPIC_CHECK(ctx != nullptr, "null context");
-  XPIC_CHECK(n >= 0, who + ": n is negative");
-  XPIC_CALL(fo_check_params(who, params));
-  const char* bad = model_check(model);
-  XPIC_CHECK(!bad, who + ": " + (bad ? bad : ""));
-  bool on;
-  CollDev Cd;
-  XPIC_CALL(coll_setup(who, collisions, params->qm, params->dt, &on, &Cd));
-  if (!on) { // the model trace itself, bit for bit
-    XPIC_CALL(xpic_model_full_orbit_trace(ctx, n, params, model, steps, sample_every, p_6, samples, iterations_sum,
-      iterations_max, region, exit_step, alive, removed));
-    if (coll_4)
-      for (int k = 0; k < kTally; ++k) coll_4[k] = 0.0;
-    return 0;
-  }
-  OpenRegion R;
-  XPIC_CALL(trace_region(who, region, true, false, &R));
+  XPIC_CALL(model_checks(who, ctx, n, params, model));
   const bool cn = params->scheme == XPIC_FO_CN;
-  return coll_trace(ctx, who, "coll_fo_trace", "coll_fo_trace", n, cn, steps, sample_every, p_6, samples, iterations_sum,
-    iterations_max, R, XPIC_COMPACT_NEVER, exit_step, alive, removed, coll_4,
-    [&](double* s, const long long*, long, long first, int ns, long nsamp, double* sm, long long* sum, int* mx, long long* ex,
-      unsigned long long* al, unsigned long long* rm, double* tally) {
+  return coll_model_trace(ctx, model_entry(who, "coll_fo_trace"), params, model,
+    {n, steps, sample_every, p_6, samples, iterations_sum, iterations_max, exit_step, alive, removed, cn, nullptr}, region,
+    collisions, coll_4, xpic_model_full_orbit_trace, [&](const TraceDev& d, const OpenRegion& R, const CollDev& Cd) {
       hipLaunchKernelGGL((cn ? k_coll_fo_trace<true, ModelField, UniformBg, AllLanes>
                              : k_coll_fo_trace<false, ModelField, UniformBg, AllLanes>),
-        lane_grid(n), dim3(kBlock), 0, ctx->stream, ctx->g, ModelField{*model}, *params, R, Cd, (long)n, s, first, ns,
-        (long)sample_every, nsamp, sm, sum, mx, ex, al, rm, tally, UniformBg{}, AllLanes{});
+        lane_grid(n), dim3(kBlock), 0, ctx->stream, ctx->g, ModelField{*model}, *params, R, Cd, (long)n, d.s, d.first, d.ns,
+        (long)sample_every, d.nsamp, d.samples, d.it_sum, d.it_max, d.exit_step, d.alive, d.removed, d.extra, UniformBg{},
+        AllLanes{});
     });
 }
 
@@ -563,30 +572,13 @@ int xpic_model_drift_kinetic_trace_collisional(xpic_ctx* ctx, int64_t n, const x
   int64_t* removed, const xpic_trace_collisions* collisions, double* coll_4)
 {
   const std::string who = "model_drift_kinetic_trace_collisional";
-  XPIC_CHECK(ctx != nullptr, "null context");
-  XPIC_CHECK(n >= 0, who + ": n is negative");
-  XPIC_CALL(dk_check_params(who, params, XPIC_MODEL_DK_MAXIT));
-  const char* bad = model_check(model);
-  XPIC_CHECK(!bad, who + ": " + (bad ? bad : ""));
-  bool on;
-  CollDev Cd;
-  XPIC_CALL(coll_setup(who, collisions, params->qm, params->dt, &on, &Cd));
-  if (!on) { // the model trace itself, bit for bit
-    XPIC_CALL(xpic_model_drift_kinetic_trace(ctx, n, params, model, steps, sample_every, state_6, samples, iterations_total,
-      iterations_max, region, exit_step, alive, removed));
-    if (coll_4)
-      for (int k = 0; k < kTally; ++k) coll_4[k] = 0.0;
-    return 0;
-  }
-  OpenRegion R;
-  XPIC_CALL(trace_region(who, region, true, false, &R));
-  return coll_trace(ctx, who, "coll_dk_trace", "coll_dk_trace", n, true, steps, sample_every, state_6, samples,
-    iterations_total, iterations_max, R, XPIC_COMPACT_NEVER, exit_step, alive, removed, coll_4,
-    [&](double* s, const long long*, long, long first, int ns, long nsamp, double* sm, long long* sum, int* mx, long long* ex,
-      unsigned long long* al, unsigned long long* rm, double* tally) {
+  XPIC_CALL(model_checks(who, ctx, n, params, model));
+  return coll_model_trace(ctx, model_entry(who, "coll_dk_trace"), params, model,
+    {n, steps, sample_every, state_6, samples, iterations_total, iterations_max, exit_step, alive, removed, true, nullptr},
+    region, collisions, coll_4, xpic_model_drift_kinetic_trace, [&](const TraceDev& d, const OpenRegion& R, const CollDev& Cd) {
       hipLaunchKernelGGL((k_coll_dk_trace<ModelField, UniformBg, AllLanes>), lane_grid(n), dim3(kBlock), 0, ctx->stream, ctx->g,
-        ModelField{*model}, *params, R, Cd, (long)n, s, first, ns, (long)sample_every, nsamp, sm, sum, mx, ex, al, rm, tally,
-        UniformBg{}, AllLanes{});
+        ModelField{*model}, *params, R, Cd, (long)n, d.s, d.first, d.ns, (long)sample_every, d.nsamp, d.samples, d.it_sum,
+        d.it_max, d.exit_step, d.alive, d.removed, d.extra, UniformBg{}, AllLanes{});
     });
 }
 
@@ -598,37 +590,22 @@ int xpic_full_orbit_trace_collisional(xpic_ctx* ctx, int64_t n, const xpic_fo_pa
   const std::string who = "full_orbit_trace_collisional";
   XPIC_CALL(grid_check(ctx, who, n));
   XPIC_CALL(fo_check_params(who, params));
-  bool on;
-  CollDev Cd;
-  ProfileBg Bg;
-  OpenRegion R;
-  int policy;
-  XPIC_CALL(coll_setup(who, collisions, params->qm, params->dt, &on, &Cd));
-  XPIC_CALL(profile_setup(ctx, who, collisions, profile, params->qm, params->dt, &Bg));
-  XPIC_CALL(grid_region(who, region, &R, &policy));
-  if (!on && (R.kind >= 0 || !exit_step)) { // the grid trace itself, bit for bit
-    if (R.kind >= 0)
-      XPIC_CALL(handed(who, xpic_full_orbit_trace_open(ctx, n, params, steps, sample_every, p_6, samples, iterations_sum, iterations_max,
-        region, exit_step, alive, removed)));
-    else {
-      XPIC_CALL(handed(who, xpic_full_orbit_trace(ctx, n, params, steps, sample_every, p_6, samples, iterations_sum, iterations_max)));
-      closed_counts(n, steps, sample_every, alive, removed);
-    }
-    if (coll_4)
-      for (int k = 0; k < kTally; ++k) coll_4[k] = 0.0;
-    return 0;
-  }
-  if (!on) Cd.every = 1; // (no region, but an exit_step to honour: the kernel with no background)
   const bool cn = params->scheme == XPIC_FO_CN;
   const FOGridField F{ctx->field[XPIC_E], ctx->field[XPIC_B]};
-  return coll_trace(ctx, who, "coll_fo_grid_trace", "coll_fo_grid_trace_compact", n, cn, steps, sample_every, p_6, samples,
-    iterations_sum, iterations_max, R, policy, exit_step, alive, removed, coll_4,
-    [&](double* s, const long long* list, long m, long first, int ns, long nsamp, double* sm, long long* sum, int* mx,
-      long long* ex, unsigned long long* al, unsigned long long* rm, double* tally) {
+  return coll_grid_trace(ctx, model_entry(who, "coll_fo_grid_trace", "coll_fo_grid_trace_compact"), *params,
+    {n, steps, sample_every, p_6, samples, iterations_sum, iterations_max, exit_step, alive, removed, cn, nullptr}, region,
+    collisions, profile, coll_4,
+    [&](bool open) {
+      return open ? xpic_full_orbit_trace_open(ctx, n, params, steps, sample_every, p_6, samples, iterations_sum,
+                      iterations_max, region, exit_step, alive, removed)
+                  : xpic_full_orbit_trace(ctx, n, params, steps, sample_every, p_6, samples, iterations_sum, iterations_max);
+    },
+    [&](const TraceDev& d, const OpenRegion& R, const CollDev& Cd, const ProfileBg& Bg) {
       hipLaunchKernelGGL((cn ? k_coll_fo_trace<true, FOGridField, ProfileBg, ListedLanes>
                              : k_coll_fo_trace<false, FOGridField, ProfileBg, ListedLanes>),
-        lane_grid(m), dim3(kBlock), 0, ctx->stream, ctx->g, F, *params, R, Cd, (long)n, s, first, ns, (long)sample_every, nsamp,
-        sm, sum, mx, ex, al, rm, tally, Bg, ListedLanes{list, m});
+        lane_grid(d.m), dim3(kBlock), 0, ctx->stream, ctx->g, F, *params, R, Cd, (long)n, d.s, d.first, d.ns,
+        (long)sample_every, d.nsamp, d.samples, d.it_sum, d.it_max, d.exit_step, d.alive, d.removed, d.extra, Bg,
+        ListedLanes{d.list, d.m});
     });
 }
 
@@ -642,41 +619,24 @@ int xpic_drift_kinetic_trace_collisional(xpic_ctx* ctx, int64_t n, const xpic_dk
   XPIC_CHECK(gradB_field == -1 || (gradB_field >= 0 && gradB_field < XPIC_NFIELDS && ctx->field[gradB_field]),
     who + ": gradB_field is neither -1 nor an allocated field id");
   XPIC_CALL(dk_check_params(who, params, 0));
-  bool on;
-  CollDev Cd;
-  ProfileBg Bg;
-  OpenRegion R;
-  int policy;
-  XPIC_CALL(coll_setup(who, collisions, params->qm, params->dt, &on, &Cd));
-  XPIC_CALL(profile_setup(ctx, who, collisions, profile, params->qm, params->dt, &Bg));
-  XPIC_CALL(grid_region(who, region, &R, &policy));
-  if (!on && (R.kind >= 0 || !exit_step)) { // the grid trace itself, bit for bit
-    if (R.kind >= 0)
-      XPIC_CALL(handed(who, xpic_drift_kinetic_trace_open(ctx, n, params, gradB_field, steps, sample_every, state_6, samples,
-        iterations_total, iterations_max, region, exit_step, alive, removed)));
-    else {
-      XPIC_CALL(handed(who, xpic_drift_kinetic_trace(ctx, n, params, gradB_field, steps, sample_every, state_6, samples, iterations_total,
-        iterations_max)));
-      closed_counts(n, steps, sample_every, alive, removed);
-    }
-    if (coll_4)
-      for (int k = 0; k < kTally; ++k) coll_4[k] = 0.0;
-    return 0;
-  }
-  if (!on) Cd.every = 1; // (no region, but an exit_step to honour: the kernel with no background)
   const double* gB = gradB_field == -1 ? nullptr : ctx->field[gradB_field];
-  return coll_trace(ctx, who, "coll_dk_grid_trace", "coll_dk_grid_trace_compact", n, true, steps, sample_every, state_6,
-    samples, iterations_total, iterations_max, R, policy, exit_step, alive, removed, coll_4,
-    [&](double* s, const long long* list, long m, long first, int ns, long nsamp, double* sm, long long* sum, int* mx,
-      long long* ex, unsigned long long* al, unsigned long long* rm, double* tally) {
-      if (gB)
-        hipLaunchKernelGGL((k_coll_dk_trace<DKGridField<true>, ProfileBg, ListedLanes>), lane_grid(m), dim3(kBlock), 0,
-          ctx->stream, ctx->g, DKGridField<true>{ctx->field[XPIC_E], ctx->field[XPIC_B], gB}, *params, R, Cd, (long)n, s,
-          first, ns, (long)sample_every, nsamp, sm, sum, mx, ex, al, rm, tally, Bg, ListedLanes{list, m});
-      else
-        hipLaunchKernelGGL((k_coll_dk_trace<DKGridField<false>, ProfileBg, ListedLanes>), lane_grid(m), dim3(kBlock), 0,
-          ctx->stream, ctx->g, DKGridField<false>{ctx->field[XPIC_E], ctx->field[XPIC_B], gB}, *params, R, Cd, (long)n, s,
-          first, ns, (long)sample_every, nsamp, sm, sum, mx, ex, al, rm, tally, Bg, ListedLanes{list, m});
+  return coll_grid_trace(ctx, model_entry(who, "coll_dk_grid_trace", "coll_dk_grid_trace_compact"), *params,
+    {n, steps, sample_every, state_6, samples, iterations_total, iterations_max, exit_step, alive, removed, true, nullptr},
+    region, collisions, profile, coll_4,
+    [&](bool open) {
+      return open ? xpic_drift_kinetic_trace_open(ctx, n, params, gradB_field, steps, sample_every, state_6, samples,
+                      iterations_total, iterations_max, region, exit_step, alive, removed)
+                  : xpic_drift_kinetic_trace(ctx, n, params, gradB_field, steps, sample_every, state_6, samples,
+                      iterations_total, iterations_max);
+    },
+    [&](const TraceDev& d, const OpenRegion& R, const CollDev& Cd, const ProfileBg& Bg) {
+      auto go = [&](auto F) {
+        hipLaunchKernelGGL((k_coll_dk_trace<decltype(F), ProfileBg, ListedLanes>), lane_grid(d.m), dim3(kBlock), 0,
+          ctx->stream, ctx->g, F, *params, R, Cd, (long)n, d.s, d.first, d.ns, (long)sample_every, d.nsamp, d.samples, d.it_sum,
+          d.it_max, d.exit_step, d.alive, d.removed, d.extra, Bg, ListedLanes{d.list, d.m});
+      };
+      if (gB) go(DKGridField<true>{ctx->field[XPIC_E], ctx->field[XPIC_B], gB});
+      else go(DKGridField<false>{ctx->field[XPIC_E], ctx->field[XPIC_B], gB});
     });
 }
 

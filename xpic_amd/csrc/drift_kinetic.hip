@@ -140,25 +140,22 @@ int dk_check(xpic_ctx* ctx, int64_t n, int gradB_field, const double** gradB)
 }
 
 // both traces, after dk_check; region: null for the closed trace
-int dk_trace(xpic_ctx* ctx, const TraceEntry& E, const char* label, const char* compact_label, int64_t n,
-  const xpic_dk_params* params, const double* gradB, int64_t steps, int64_t sample_every, double* state_6, double* samples,
-  int64_t* iterations_total, int* iterations_max, const xpic_trace_region* region, int64_t* exit_step, int64_t* alive,
-  int64_t* removed)
+int dk_trace(xpic_ctx* ctx, const TraceEntry& E, const xpic_dk_params* params, const double* gradB, const TraceArrays& A,
+  const xpic_trace_region* region)
 {
   XPIC_CALL(dk_check_params("drift_kinetic", params, 0));
+  const long n = (long)A.n, every = (long)A.sample_every;
   OpenRegion R{XPIC_GEOM_NONE, {}, 0};
   if (!E.closed) XPIC_CALL(trace_region(E.who, region, false, true, &R));
-  return trace_call(ctx, E, label, compact_label, XPIC_DK_LAUNCH_STEPS, n, true, steps, sample_every, state_6, samples,
-    iterations_total, iterations_max, R, E.closed ? XPIC_COMPACT_NEVER : region->compact, exit_step, alive, removed, nullptr,
-    [&](double* s, const long long* list, long m, long first, int ns, long nsamp, double* sm, long long* it_sum, int* it_max,
-      long long* ex, unsigned long long* al, unsigned long long* rm, double*) {
+  return trace_call(ctx, E, XPIC_DK_LAUNCH_STEPS, A, R, E.closed ? XPIC_COMPACT_NEVER : region->compact, nullptr,
+    [&](const TraceDev& d) {
       if (E.closed) // its text takes no region: the driver's stand-ins for exit_step and removed stay unused
         hipLaunchKernelGGL(gradB ? k_dk_trace<true> : k_dk_trace<false>, lane_grid(n), dim3(kBlock), 0, ctx->stream, ctx->g,
-          ctx->field[XPIC_E], ctx->field[XPIC_B], gradB, *params, (long)n, s, first, ns, (long)sample_every, sm, it_sum, it_max);
+          ctx->field[XPIC_E], ctx->field[XPIC_B], gradB, *params, n, d.s, d.first, d.ns, every, d.samples, d.it_sum, d.it_max);
       else
-        hipLaunchKernelGGL(gradB ? k_dk_trace_open<true> : k_dk_trace_open<false>, lane_grid(m), dim3(kBlock), 0, ctx->stream,
-          ctx->g, ctx->field[XPIC_E], ctx->field[XPIC_B], gradB, *params, R, (long)n, s, list, m, first, ns, (long)sample_every,
-          nsamp, sm, it_sum, it_max, ex, al, rm);
+        hipLaunchKernelGGL(gradB ? k_dk_trace_open<true> : k_dk_trace_open<false>, lane_grid(d.m), dim3(kBlock), 0,
+          ctx->stream, ctx->g, ctx->field[XPIC_E], ctx->field[XPIC_B], gradB, *params, R, n, d.s, d.list, d.m, d.first, d.ns,
+          every, d.nsamp, d.samples, d.it_sum, d.it_max, d.exit_step, d.alive, d.removed);
     });
 }
 
@@ -220,8 +217,9 @@ int xpic_drift_kinetic_trace(xpic_ctx* ctx, int64_t n, const xpic_dk_params* par
 {
   const double* gradB;
   XPIC_CALL(dk_check(ctx, n, gradB_field, &gradB));
-  return dk_trace(ctx, {"drift_kinetic_trace", "state_6", "iterations_total", "iterations_max", true}, "dk_trace", "dk_trace",
-    n, params, gradB, steps, sample_every, state_6, samples, iterations_total, iterations_max, nullptr, nullptr, nullptr,
+  return dk_trace(ctx, {"drift_kinetic_trace", "state_6", "iterations_total", "iterations_max", true, "dk_trace", "dk_trace"},
+    params, gradB,
+    {n, steps, sample_every, state_6, samples, iterations_total, iterations_max, nullptr, nullptr, nullptr, true, nullptr},
     nullptr);
 }
 
@@ -231,9 +229,11 @@ int xpic_drift_kinetic_trace_open(xpic_ctx* ctx, int64_t n, const xpic_dk_params
 { // xpic_drift_kinetic_trace with RemoveParticles::execute (remove_particles.cpp:22-38) at the top of every step
   const double* gradB;
   XPIC_CALL(dk_check(ctx, n, gradB_field, &gradB));
-  return dk_trace(ctx, {"drift_kinetic_trace_open", "state_6", "iterations_total", "iterations_max", false}, "dk_trace_open",
-    "dk_trace_open_compact", n, params, gradB, steps, sample_every, state_6, samples, iterations_total, iterations_max, region,
-    exit_step, alive, removed);
+  const TraceEntry E{"drift_kinetic_trace_open", "state_6", "iterations_total", "iterations_max", false, "dk_trace_open",
+    "dk_trace_open_compact"};
+  return dk_trace(ctx, E, params, gradB,
+    {n, steps, sample_every, state_6, samples, iterations_total, iterations_max, exit_step, alive, removed, true, nullptr},
+    region);
 }
 
 }  // extern "C"

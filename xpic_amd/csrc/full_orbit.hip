@@ -147,26 +147,23 @@ int fo_check(xpic_ctx* ctx, int64_t n, const xpic_fo_params* P)
   return 0;
 }
 
-// both traces, after fo_check; region: null for the closed trace
-int fo_trace(xpic_ctx* ctx, const TraceEntry& E, const char* label, const char* compact_label, int64_t n,
-  const xpic_fo_params& P, int64_t steps, int64_t sample_every, double* p_6, double* samples, int64_t* iterations_sum,
-  int* iterations_max, const xpic_trace_region* region, int64_t* exit_step, int64_t* alive, int64_t* removed)
+// both traces, after fo_check; region: null for the closed trace.  A Chin id has no iterations: its launches get null
+// counters
+int fo_trace(xpic_ctx* ctx, const TraceEntry& E, const xpic_fo_params& P, const TraceArrays& A, const xpic_trace_region* region)
 {
-  const bool cn = P.scheme == XPIC_FO_CN;
+  const bool cn = A.counters;
+  const long n = (long)A.n, every = (long)A.sample_every;
   OpenRegion R{XPIC_GEOM_NONE, {}, 0};
   if (!E.closed) XPIC_CALL(trace_region(E.who, region, false, true, &R));
-  // a Chin id has no iterations: its launches get null counters
-  return trace_call(ctx, E, label, compact_label, kLaunchSteps, n, cn, steps, sample_every, p_6, samples, iterations_sum,
-    iterations_max, R, E.closed ? XPIC_COMPACT_NEVER : region->compact, exit_step, alive, removed, nullptr,
-    [&](double* s, const long long* list, long m, long first, int ns, long nsamp, double* sm, long long* it_sum, int* it_max,
-      long long* ex, unsigned long long* al, unsigned long long* rm, double*) {
+  return trace_call(ctx, E, kLaunchSteps, A, R, E.closed ? XPIC_COMPACT_NEVER : region->compact, nullptr,
+    [&](const TraceDev& d) {
       if (E.closed) // its text takes no region: the driver's stand-ins for exit_step and removed stay unused
         hipLaunchKernelGGL(cn ? k_fo_trace<true> : k_fo_trace<false>, lane_grid(n), dim3(kBlock), 0, ctx->stream, ctx->g,
-          ctx->field[XPIC_E], ctx->field[XPIC_B], P, (long)n, s, first, ns, (long)sample_every, nsamp, sm, it_sum, it_max);
+          ctx->field[XPIC_E], ctx->field[XPIC_B], P, n, d.s, d.first, d.ns, every, d.nsamp, d.samples, d.it_sum, d.it_max);
       else
-        hipLaunchKernelGGL(cn ? k_fo_trace_open<true> : k_fo_trace_open<false>, lane_grid(m), dim3(kBlock), 0, ctx->stream,
-          ctx->g, ctx->field[XPIC_E], ctx->field[XPIC_B], P, R, (long)n, s, list, m, first, ns, (long)sample_every, nsamp, sm,
-          it_sum, it_max, ex, al, rm);
+        hipLaunchKernelGGL(cn ? k_fo_trace_open<true> : k_fo_trace_open<false>, lane_grid(d.m), dim3(kBlock), 0, ctx->stream,
+          ctx->g, ctx->field[XPIC_E], ctx->field[XPIC_B], P, R, n, d.s, d.list, d.m, d.first, d.ns, every, d.nsamp, d.samples,
+          d.it_sum, d.it_max, d.exit_step, d.alive, d.removed);
     });
 }
 
@@ -199,8 +196,9 @@ int xpic_full_orbit_trace(xpic_ctx* ctx, int64_t n, const xpic_fo_params* params
   double* p_6, double* samples, int64_t* iterations_sum, int* iterations_max)
 { // the time loops of boris_push_ex1.cpp:51-60 and crank_nicolson_push_ex2.cpp:43-56
   XPIC_CALL(fo_check(ctx, n, params));
-  return fo_trace(ctx, {"full_orbit_trace", "p_6", "iterations_sum", "iterations_max", true}, "fo_trace", "fo_trace", n,
-    *params, steps, sample_every, p_6, samples, iterations_sum, iterations_max, nullptr, nullptr, nullptr, nullptr);
+  const bool cn = params->scheme == XPIC_FO_CN;
+  return fo_trace(ctx, {"full_orbit_trace", "p_6", "iterations_sum", "iterations_max", true, "fo_trace", "fo_trace"}, *params,
+    {n, steps, sample_every, p_6, samples, iterations_sum, iterations_max, nullptr, nullptr, nullptr, cn, nullptr}, nullptr);
 }
 
 int xpic_full_orbit_trace_open(xpic_ctx* ctx, int64_t n, const xpic_fo_params* params, int64_t steps, int64_t sample_every,
@@ -208,9 +206,11 @@ int xpic_full_orbit_trace_open(xpic_ctx* ctx, int64_t n, const xpic_fo_params* p
   int64_t* exit_step, int64_t* alive, int64_t* removed)
 { // xpic_full_orbit_trace with RemoveParticles::execute (remove_particles.cpp:22-38) at the top of every step
   XPIC_CALL(fo_check(ctx, n, params));
-  return fo_trace(ctx, {"full_orbit_trace_open", "p_6", "iterations_sum", "iterations_max", false}, "fo_trace_open",
-    "fo_trace_open_compact", n, *params, steps, sample_every, p_6, samples, iterations_sum, iterations_max, region, exit_step,
-    alive, removed);
+  const bool cn = params->scheme == XPIC_FO_CN;
+  return fo_trace(ctx,
+    {"full_orbit_trace_open", "p_6", "iterations_sum", "iterations_max", false, "fo_trace_open", "fo_trace_open_compact"},
+    *params, {n, steps, sample_every, p_6, samples, iterations_sum, iterations_max, exit_step, alive, removed, cn, nullptr},
+    region);
 }
 
 }  // extern "C"

@@ -255,13 +255,6 @@ __global__ void __launch_bounds__(kBlock) k_envelope_factors(xpic_field_envelope
   out[i] = envelope_factor(V, step0 + i, dt);
 }
 
-int model_ok(const std::string& who, const xpic_field_model* model)
-{
-  const char* bad = model_check(model);
-  XPIC_CHECK(!bad, who + ": " + (bad ? bad : ""));
-  return 0;
-}
-
 // the envelope a call runs with: a null one is the constant one
 int timed_envelope(const std::string& who, const xpic_field_envelope* in, xpic_field_envelope* V)
 {
@@ -272,41 +265,15 @@ int timed_envelope(const std::string& who, const xpic_field_envelope* in, xpic_f
   return 0;
 }
 
-// the checks a pusher's timed and untimed entry points make first, up to the model
-int fo_checks(const std::string& who, xpic_ctx* ctx, int64_t n, const xpic_fo_params* params, const xpic_field_model* model)
-{
-  XPIC_CHECK(ctx != nullptr, "null context");
-  XPIC_CHECK(n >= 0, who + ": n is negative");
-  XPIC_CALL(fo_check_params(who, params));
-  return model_ok(who, model);
-}
-int dk_checks(const std::string& who, xpic_ctx* ctx, int64_t n, const xpic_dk_params* params, const xpic_field_model* model)
-{
-  XPIC_CHECK(ctx != nullptr, "null context");
-  XPIC_CHECK(n >= 0, who + ": n is negative");
-  XPIC_CALL(dk_check_params(who, params, XPIC_MODEL_DK_MAXIT));
-  return model_ok(who, model);
-}
-
-// how the four model traces' messages name their arrays (trace_call.h)
-TraceEntry model_entry(const std::string& who)
-{
-  return {who.c_str(), "the particle array", "an iteration counter", "an iteration counter", false};
-}
-
 // the drift-kinetic trace of either clock, after the checks: `label` names the profile entry
 template <class Clock>
-int dk_trace(xpic_ctx* ctx, const std::string& who, const char* label, int64_t n, const xpic_dk_params& P, const Clock& C,
-  int64_t steps, int64_t sample_every, double* state_6, double* samples, int64_t* it_total, int* it_max, const OpenRegion& R,
-  int64_t* exit_step, int64_t* alive, int64_t* removed)
+int dk_trace(xpic_ctx* ctx, const std::string& who, const char* label, const xpic_dk_params& P, const Clock& C,
+  const TraceArrays& A, const OpenRegion& R)
 {
-  return trace_call(ctx, model_entry(who), label, label, kLaunchSteps, n, true, steps, sample_every, state_6, samples,
-    it_total, it_max, R, XPIC_COMPACT_NEVER, exit_step, alive, removed, nullptr,
-    [&](double* s, const long long*, long, long first, int ns, long nsamp, double* sm, long long* sum, int* mx, long long* ex,
-      unsigned long long* al, unsigned long long* rm, double*) {
-      hipLaunchKernelGGL(k_model_dk_trace<Clock>, lane_grid(n), dim3(kBlock), 0, ctx->stream, ctx->g, C, P, R, (long)n, s,
-        first, ns, (long)sample_every, nsamp, sm, sum, mx, ex, al, rm);
-    });
+  return trace_call(ctx, model_entry(who, label), kLaunchSteps, A, R, XPIC_COMPACT_NEVER, nullptr, [&](const TraceDev& d) {
+    hipLaunchKernelGGL(k_model_dk_trace<Clock>, lane_grid(A.n), dim3(kBlock), 0, ctx->stream, ctx->g, C, P, R, (long)A.n, d.s,
+      d.first, d.ns, (long)A.sample_every, d.nsamp, d.samples, d.it_sum, d.it_max, d.exit_step, d.alive, d.removed);
+  });
 }
 
 }  // namespace
@@ -366,16 +333,16 @@ int xpic_model_full_orbit_trace(xpic_ctx* ctx, int64_t n, const xpic_fo_params* 
   const xpic_trace_region* region, int64_t* exit_step, int64_t* alive, int64_t* removed)
 {
   const std::string who = "model_full_orbit_trace";
-  XPIC_CALL(fo_checks(who, ctx, n, params, model));
+  XPIC_CALL(model_checks(who, ctx, n, params, model));
   OpenRegion R;
   XPIC_CALL(trace_region(who, region, true, false, &R));
   const bool cn = params->scheme == XPIC_FO_CN;
-  return trace_call(ctx, model_entry(who), "model_fo_trace", "model_fo_trace", kLaunchSteps, n, cn, steps, sample_every, p_6,
-    samples, iterations_sum, iterations_max, R, XPIC_COMPACT_NEVER, exit_step, alive, removed, nullptr,
-    [&](double* s, const long long*, long, long first, int ns, long nsamp, double* sm, long long* sum, int* mx, long long* ex,
-      unsigned long long* al, unsigned long long* rm, double*) {
+  return trace_call(ctx, model_entry(who, "model_fo_trace"), kLaunchSteps,
+    {n, steps, sample_every, p_6, samples, iterations_sum, iterations_max, exit_step, alive, removed, cn, nullptr}, R,
+    XPIC_COMPACT_NEVER, nullptr, [&](const TraceDev& d) {
       hipLaunchKernelGGL(cn ? k_model_fo_trace<true> : k_model_fo_trace<false>, lane_grid(n), dim3(kBlock), 0, ctx->stream,
-        ctx->g, *model, *params, R, (long)n, s, first, ns, (long)sample_every, nsamp, sm, sum, mx, ex, al, rm);
+        ctx->g, *model, *params, R, (long)n, d.s, d.first, d.ns, (long)sample_every, d.nsamp, d.samples, d.it_sum, d.it_max,
+        d.exit_step, d.alive, d.removed);
     });
 }
 
@@ -384,11 +351,11 @@ int xpic_model_drift_kinetic_trace(xpic_ctx* ctx, int64_t n, const xpic_dk_param
   const xpic_trace_region* region, int64_t* exit_step, int64_t* alive, int64_t* removed)
 {
   const std::string who = "model_drift_kinetic_trace";
-  XPIC_CALL(dk_checks(who, ctx, n, params, model));
+  XPIC_CALL(model_checks(who, ctx, n, params, model));
   OpenRegion R;
   XPIC_CALL(trace_region(who, region, true, false, &R));
-  return dk_trace(ctx, who, "model_dk_trace", n, *params, StaticClock{*model}, steps, sample_every, state_6, samples,
-    iterations_total, iterations_max, R, exit_step, alive, removed);
+  return dk_trace(ctx, who, "model_dk_trace", *params, StaticClock{*model},
+    {n, steps, sample_every, state_6, samples, iterations_total, iterations_max, exit_step, alive, removed, true, nullptr}, R);
 }
 
 int xpic_model_full_orbit_trace_timed(xpic_ctx* ctx, int64_t n, const xpic_fo_params* params, const xpic_field_model* model,
@@ -397,7 +364,7 @@ int xpic_model_full_orbit_trace_timed(xpic_ctx* ctx, int64_t n, const xpic_fo_pa
   int64_t* removed, double* sums_4)
 {
   const std::string who = "model_full_orbit_trace_timed";
-  XPIC_CALL(fo_checks(who, ctx, n, params, model));
+  XPIC_CALL(model_checks(who, ctx, n, params, model));
   xpic_field_envelope V;
   XPIC_CALL(timed_envelope(who, envelope, &V));
   OpenRegion R;
@@ -405,12 +372,11 @@ int xpic_model_full_orbit_trace_timed(xpic_ctx* ctx, int64_t n, const xpic_fo_pa
   const bool cn = params->scheme == XPIC_FO_CN, sums = sums_4 != nullptr;
   auto kernel = cn ? (sums ? k_timed_fo_trace<true, true> : k_timed_fo_trace<true, false>)
                    : (sums ? k_timed_fo_trace<false, true> : k_timed_fo_trace<false, false>);
-  return trace_call(ctx, model_entry(who), "timed_fo_trace", "timed_fo_trace", kLaunchSteps, n, cn, steps, sample_every, p_6,
-    samples, iterations_sum, iterations_max, R, XPIC_COMPACT_NEVER, exit_step, alive, removed, sums_4,
-    [&](double* s, const long long*, long, long first, int ns, long nsamp, double* sm, long long* sum, int* mx, long long* ex,
-      unsigned long long* al, unsigned long long* rm, double* sd) {
-      hipLaunchKernelGGL(kernel, lane_grid(n), dim3(kBlock), 0, ctx->stream, ctx->g, *model, V, *params, R, (long)n, s, first,
-        ns, (long)sample_every, nsamp, sm, sum, mx, ex, al, rm, sd);
+  return trace_call(ctx, model_entry(who, "timed_fo_trace"), kLaunchSteps,
+    {n, steps, sample_every, p_6, samples, iterations_sum, iterations_max, exit_step, alive, removed, cn, sums_4}, R,
+    XPIC_COMPACT_NEVER, nullptr, [&](const TraceDev& d) {
+      hipLaunchKernelGGL(kernel, lane_grid(n), dim3(kBlock), 0, ctx->stream, ctx->g, *model, V, *params, R, (long)n, d.s,
+        d.first, d.ns, (long)sample_every, d.nsamp, d.samples, d.it_sum, d.it_max, d.exit_step, d.alive, d.removed, d.extra);
     });
 }
 
@@ -420,13 +386,13 @@ int xpic_model_drift_kinetic_trace_timed(xpic_ctx* ctx, int64_t n, const xpic_dk
   int64_t* alive, int64_t* removed)
 {
   const std::string who = "model_drift_kinetic_trace_timed";
-  XPIC_CALL(dk_checks(who, ctx, n, params, model));
+  XPIC_CALL(model_checks(who, ctx, n, params, model));
   xpic_field_envelope V;
   XPIC_CALL(timed_envelope(who, envelope, &V));
   OpenRegion R;
   XPIC_CALL(trace_region(who, region, true, false, &R));
-  return dk_trace(ctx, who, "timed_dk_trace", n, *params, EnvelopeClock{*model, V}, steps, sample_every, state_6, samples,
-    iterations_total, iterations_max, R, exit_step, alive, removed);
+  return dk_trace(ctx, who, "timed_dk_trace", *params, EnvelopeClock{*model, V},
+    {n, steps, sample_every, state_6, samples, iterations_total, iterations_max, exit_step, alive, removed, true, nullptr}, R);
 }
 
 int xpic_envelope_factors(xpic_ctx* ctx, const xpic_field_envelope* envelope, double dt, int64_t step0, int64_t nsteps,
