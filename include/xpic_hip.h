@@ -342,8 +342,14 @@ int xpic_fields_damping(xpic_ctx* ctx, int E, int B, int B0, int geometry, const
  * follow the old ones of their cell.  *added = pairs added, energy2 = kinetic energy added to the ionized, the ejected
  * sort.  The two sorts must differ.  More records than a sort's capacity fail with an error on every slab, before any
  * sort is changed. */
-enum xpic_coordinate_kind { XPIC_COORD_PRECISE = 0, XPIC_COORD_IN_BOX = 1, XPIC_COORD_IN_CYLINDER = 2 };
-enum xpic_momentum_kind { XPIC_MOMENTUM_PRECISE = 0, XPIC_MOMENTUM_MAXWELLIAN = 1 };
+enum xpic_coordinate_kind {
+  XPIC_COORD_PRECISE = 0, XPIC_COORD_IN_BOX = 1, XPIC_COORD_IN_CYLINDER = 2,
+  XPIC_COORD_ON_ANNULUS = 3 /* xpic_set_particles only */
+};
+enum xpic_momentum_kind {
+  XPIC_MOMENTUM_PRECISE = 0, XPIC_MOMENTUM_MAXWELLIAN = 1,
+  XPIC_MOMENTUM_COSINE_PERTURBATION = 2, XPIC_MOMENTUM_ANGULAR = 3 /* xpic_set_particles only */
+};
 typedef struct xpic_momentum_params {
   int32_t kind;     /* enum xpic_momentum_kind */
   int32_t tov;      /* MaxwellianMomentum: p /= sqrt(m^2 + p^2) */
@@ -359,6 +365,24 @@ typedef struct xpic_inject_params {
 } xpic_inject_params;
 int xpic_inject_particles(xpic_ctx* ctx, int ionized, int ejected, const xpic_inject_params* params, int64_t pairs,
   int64_t step, int64_t* added, double energy2[2]);
+/* The parameters of xpic_set_particles (include/xpic_set_particles.h, where the command is defined). */
+#define XPIC_SET_PARTICLES_CHUNK 16777216 /* particles per internal chunk when `chunk` is 0 */
+typedef struct xpic_set_particles_params {
+  int32_t coordinate;    /* enum xpic_coordinate_kind */
+  int32_t momentum;      /* enum xpic_momentum_kind */
+  int32_t tov;           /* MaxwellianMomentum: p /= sqrt(m^2 + p^2) */
+  int32_t reserved;
+  double geom[7];        /* the point (precise), {min xyz, max xyz} (box), {center xyz, radius, height} (cylinder),
+                            {center xyz, inner_r, outer_r, height} (annulus) */
+  double value[3];       /* PreciseMomentum: the value; Maxwellian, angular: px, py, pz of SortParameters */
+  double T[3];           /* Tx, Ty, Tz of SortParameters (all generators but the precise one) */
+  double amplitude[3];   /* MaxwellCosinePerturbation: a */
+  double wave_number[3]; /* MaxwellCosinePerturbation: m */
+  double box6[6];        /* MaxwellCosinePerturbation: its box {min xyz, max xyz}; only the extents enter */
+  double center[3];      /* AngularMomentum: the axis (its z is not read) */
+  uint64_t seed;
+  int64_t chunk;         /* particles per internal chunk; 0: XPIC_SET_PARTICLES_CHUNK */
+} xpic_set_particles_params;
 /* Binary Coulomb collisions between the records of one cell (Takizuka and Abe, J. Comput. Phys. 25, 205, 1977),
  * non-relativistic.  AN EXTENSION: the reference has no collision operator, so no file:line of it is cited here.
  * A call collides sort_a with sort_b (the same sort: intra-species) inside every local cell, independently of every other
@@ -928,4 +952,6 @@ int xpic_probe_copy_bandwidth(xpic_ctx* ctx, int64_t bytes, int reps, double* by
 #ifdef __cplusplus
 }
 #endif
+/* ---- SetParticles on the device and the builder's particle count: their entry points and their definition */
+#include "xpic_set_particles.h"
 #endif

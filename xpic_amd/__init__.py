@@ -166,7 +166,7 @@ _lib = None
 
 
 def load_library():
-    """Loads libxpic_hip.so and types every entry point from PROTOTYPES; raises if it has not been built (no fallback
+    """Loads libxpic_hip.so and types every entry point from PROTOTYPES and LOAD_PROTOTYPES; raises if it has not been built (no fallback
     path exists).  The xpic_debug_*_stamps symbols of experiment builds are not in the header and stay untyped."""
     global _lib
     if _lib is not None:
@@ -175,7 +175,7 @@ def load_library():
         raise XpicError(f"{LIB_PATH} is missing: run `make` (or __graft_entry__.build()) first; "
                         "xpic_amd has no CPU fallback")
     L = C.CDLL(LIB_PATH)
-    for name, (ret, args) in PROTOTYPES.items():
+    for name, (ret, args) in dict(PROTOTYPES, **LOAD_PROTOTYPES).items():
         f = getattr(L, name)
         f.restype, f.argtypes = CTYPES[ret], [CTYPES[a] for a in args]
     if L.xpic_version() & VERSION_EXPERIMENT_BIT and os.environ.get("XPIC_ALLOW_EXPERIMENT") != "1":
@@ -201,7 +201,55 @@ _i64p = _array_pointer(np.int64, "int64_t*")
 _i32p = _array_pointer(np.int32, "int32_t*")  # (and the header's `int*`: the same ctypes type)
 
 
-class Context:
+def _coordinate7(coordinate):
+    """(enum xpic_coordinate_kind, double[7]) of a coordinate generator's dict"""
+    kind = COORDINATES[coordinate["name"]]
+    if kind == 0:
+        g = list(coordinate["value"]) + [0.0] * 4
+    elif kind == 3:
+        g = list(coordinate["center"]) + [coordinate["inner_r"], coordinate["outer_r"], coordinate["height"], 0.0]
+    else:
+        g = list(_geom7(dict(coordinate, name="box" if kind == 1 else "cylinder"))[1])
+    return kind, np.array([float(v) for v in g], dtype=np.float64)
+
+
+class LoadCommands:
+    """SetParticles on the device and the builder's particle count (include/xpic_set_particles.h), as methods of Context"""
+
+    def set_particles(self, sort, n, coordinate, momentum, step=0, seed=0, particle0=0, chunk=0):
+        """SetParticles for the particles particle0 .. particle0 + n - 1 of one command -> (particles added, their energy),
+        summed over the slabs.  coordinate: as inject_particles', or {"name": "CoordinateOnAnnulus", "center": xyz,
+        "inner_r": r, "outer_r": r, "height": h}; momentum: as inject_particles', or {"name":
+        "MaxwellCosinePerturbation", "T": (Tx, Ty, Tz), "amplitude": xyz, "wave_number": xyz, "min": xyz, "max": xyz},
+        or {"name": "AngularMomentum", "T": (Tx, Ty, Tz), "drift": (px, py, pz), "center": xyz}.  chunk: particles per
+        launch, 0 for the library's default."""
+        p = SetParticlesParams()
+        p.coordinate, g = _coordinate7(coordinate)
+        p.geom[:] = list(g)
+        p.momentum = MOMENTA[momentum["name"]]
+        p.tov = int(bool(momentum.get("tov", False)))
+        p.value[:] = [float(v) for v in (momentum["value"] if p.momentum == 0 else momentum.get("drift", (0.0, 0.0, 0.0)))]
+        p.T[:] = [float(v) for v in momentum.get("T", (0.0, 0.0, 0.0))]
+        p.amplitude[:] = [float(v) for v in momentum.get("amplitude", (0.0, 0.0, 0.0))]
+        p.wave_number[:] = [float(v) for v in momentum.get("wave_number", (0.0, 0.0, 0.0))]
+        if p.momentum == 2:
+            p.box6[:] = [float(v) for v in list(momentum["min"]) + list(momentum["max"])]
+        p.center[:] = [float(v) for v in momentum.get("center", (0.0, 0.0, 0.0))]
+        p.seed, p.chunk = int(seed), int(chunk)
+        added, energy = C.c_int64(), C.c_double()
+        self._ck(self.L.xpic_set_particles(self.h, int(sort), C.byref(p), int(n), int(particle0), int(step),
+                                           C.byref(added), C.byref(energy)))
+        return added.value, energy.value
+
+    def particles_number(self, sort, coordinate):
+        """the number of particles the reference's builder gives a SetParticles command with this coordinate generator"""
+        kind, g = _coordinate7(coordinate)
+        out = C.c_int64()
+        self._ck(self.L.xpic_particles_number(self.h, int(sort), kind, _dp(g), C.byref(out)))
+        return out.value
+
+
+class Context(LoadCommands):
     """One z-slab context = one `interfaces::Simulation` backend instance."""
 
     def __init__(self, scheme, n, d, dt, device=0, rank=0, nranks=1, self_ring=False):

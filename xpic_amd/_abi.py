@@ -22,8 +22,9 @@ MOMENT_DOF = {"density": 1, "current": 3, "momentum_flux": 6, "momentum_flux_dia
 PROJECTORS = {"vx_vy": 0, "vz_vxy": 1, "vr_vphi": 2}  # enum xpic_projector
 GEOMETRIES = {"box": 0, "BoxGeometry": 0, "cylinder": 1, "CylinderGeometry": 1}  # enum xpic_vgeometry
 
-COORDINATES = {"PreciseCoordinate": 0, "CoordinateInBox": 1, "CoordinateInCylinder": 2}  # enum xpic_coordinate_kind
-MOMENTA = {"PreciseMomentum": 0, "MaxwellianMomentum": 1}  # enum xpic_momentum_kind
+# enum xpic_coordinate_kind, enum xpic_momentum_kind; inject_particles takes the first three and the first two
+COORDINATES = {"PreciseCoordinate": 0, "CoordinateInBox": 1, "CoordinateInCylinder": 2, "CoordinateOnAnnulus": 3}
+MOMENTA = {"PreciseMomentum": 0, "MaxwellianMomentum": 1, "MaxwellCosinePerturbation": 2, "AngularMomentum": 3}
 
 
 class MomentumParams(C.Structure):
@@ -33,6 +34,16 @@ class MomentumParams(C.Structure):
 class InjectParams(C.Structure):
     _fields_ = [("coordinate", C.c_int32), ("reserved", C.c_int32), ("geom", C.c_double * 7),
                 ("momentum", MomentumParams * 2), ("seed", C.c_uint64)]
+
+
+class SetParticlesParams(C.Structure):
+    _fields_ = [("coordinate", C.c_int32), ("momentum", C.c_int32), ("tov", C.c_int32), ("reserved", C.c_int32),
+                ("geom", C.c_double * 7), ("value", C.c_double * 3), ("T", C.c_double * 3), ("amplitude", C.c_double * 3),
+                ("wave_number", C.c_double * 3), ("box6", C.c_double * 6), ("center", C.c_double * 3), ("seed", C.c_uint64),
+                ("chunk", C.c_int64)]
+
+
+SET_PARTICLES_CHUNK = 1 << 24  # XPIC_SET_PARTICLES_CHUNK
 
 
 class CollisionParams(C.Structure):
@@ -133,6 +144,7 @@ class CommCallbacks(C.Structure):
 # every struct the header defines (all typedefs but the opaque xpic_ctx) and its mirror
 MIRRORS = {"xpic_geometry": Geometry, "xpic_sort_params": SortParams, "xpic_load_params": LoadParams,
            "xpic_momentum_params": MomentumParams, "xpic_inject_params": InjectParams,
+           "xpic_set_particles_params": SetParticlesParams,
            "xpic_collision_params": CollisionParams, "xpic_dk_params": DkParams, "xpic_fo_params": FoParams,
            "xpic_trace_region": TraceRegion, "xpic_field_model": FieldModel, "xpic_field_envelope": FieldEnvelope,
            "xpic_trace_background": TraceBackground, "xpic_trace_collisions": TraceCollisions,
@@ -273,3 +285,10 @@ PROTOTYPES = {
     "xpic_probe_copy_bandwidth": ("int", ["xpic_ctx*", "int64_t", "int", "double*"]),
 }
 SYMBOLS = list(PROTOTYPES)  # every symbol include/xpic_hip.h declares
+# the entry points of include/xpic_set_particles.h, typed by load_library() as PROTOTYPES' are; tests/test_abi_set_particles.py
+# holds them to that header
+LOAD_PROTOTYPES = {
+    "xpic_set_particles": ("int", ["xpic_ctx*", "int", "const xpic_set_particles_params*", "int64_t", "int64_t", "int64_t",
+                                   "int64_t*", "double*"]),
+    "xpic_particles_number": ("int", ["xpic_ctx*", "int", "int", "const double*", "int64_t*"]),
+}

@@ -966,6 +966,22 @@ int xpic_inject_particles(xpic_ctx* ctx, int ionized, int ejected, const xpic_in
   return inject_particles(ctx, ctx->sorts[ionized], ctx->sorts[ejected], *params, pairs, step, added, energy2);
 }
 
+int xpic_set_particles(xpic_ctx* ctx, int sort, const xpic_set_particles_params* params, int64_t n, int64_t particle0,
+  int64_t step, int64_t* added, double* energy)
+{ // SetParticles::execute, set_particles.cpp:19-43
+  CTX_CHECK(ctx);
+  XPIC_CHECK(sort >= 0 && sort < (int)ctx->sorts.size(), "xpic_set_particles: unknown sort id");
+  XPIC_CHECK(params && added && energy, "xpic_set_particles: null argument");
+  return set_particles(ctx, ctx->sorts[sort], *params, n, particle0, step, added, energy);
+}
+
+int xpic_particles_number(xpic_ctx* ctx, int sort, int coordinate, const double geom[7], int64_t* out)
+{ // ParticlesBuilder::load_coordinate, particles_builder.cpp:16-34
+  CTX_CHECK(ctx);
+  XPIC_CHECK(sort >= 0 && sort < (int)ctx->sorts.size(), "xpic_particles_number: unknown sort id");
+  return particles_number(ctx, ctx->sorts[sort], coordinate, geom, out);
+}
+
 int xpic_set_coils_field(xpic_ctx* ctx, int field, int ncoils, const double* coils3)
 { // SetCoilsField::operator(), set_magnetic_field.cpp:38-150
   CTX_CHECK(ctx); FIELD_CHECK(field);

@@ -13,6 +13,8 @@
 // cells and damps by the same factors.
 #include <algorithm>
 #include <cmath>
+#include <cstdint>
+#include <string>
 #include <vector>
 
 #include "batch.h"
@@ -125,6 +127,15 @@ struct InjDev {
   uint64_t key; // stream of pair p: key + p * (odd constant), then splitmix
 };
 
+// the key of a call's streams: the seed's splitmix state, xor the step times a constant, splitmix
+inline uint64_t stream_key(uint64_t seed, int64_t step)
+{
+  uint64_t key = seed;
+  (void)splitmix(key);
+  key ^= (uint64_t)step * 0xD1342543DE82EF95ull;
+  return splitmix(key);
+}
+
 __device__ inline uint64_t pair_stream(const InjDev& P, int64_t p) { return P.key + (uint64_t)p * 0x2545F4914F6CDD1Dull; }
 
 // PreciseCoordinate / CoordinateInBox / CoordinateInCylinder (particles_load.cpp:6-30), draws in the reference's order
@@ -201,6 +212,106 @@ __global__ void __launch_bounds__(kBlock) k_inj_write(GridDev g, SortDev s, InjD
     }
     const double* v = pm[K];
     e[0] += 0.5 * (P.m[K] * (v[0] * v[0] + v[1] * v[1] + v[2] * v[2])) * mpw;
+  }
+  block_reduce_store<1, kBlock>(e, partial, 0, blockIdx.x);
+}
+
+// ---- SetParticles (include/xpic_set_particles.h) ---------------------------------------------------------------------
+// particle p draws from pair p's stream: its coordinate, then its momentum.  I: the part InjectParticles' generators read
+// (sort 0 of it); the rest belongs to CoordinateOnAnnulus, MaxwellCosinePerturbation and AngularMomentum.
+struct SetDev {
+  InjDev I;
+  int coord, mom;
+  double amp[3], wn[3], L[3], center[2];
+};
+
+// CoordinateOnAnnulus (particles_load.cpp:32-44); the other three are inj_coordinate
+__device__ inline void set_coordinate(const SetDev& P, uint64_t& st, double* r)
+{
+  if (P.coord != XPIC_COORD_ON_ANNULUS) return inj_coordinate(P.I, st, r);
+  const double* g = P.I.geom;
+  const double rr = sqrt(g[3] * g[3] + (g[4] * g[4] - g[3] * g[3]) * u01(st));
+  const double phi = 2.0 * M_PI * u01(st);
+  r[0] = g[0] + rr * cos(phi);
+  r[1] = g[1] + rr * sin(phi);
+  r[2] = g[2] + g[5] * (u01(st) - 0.5);
+}
+
+// temperature_momentum (:52-55)
+__device__ inline double set_thermal(const SetDev& P, int a, uint64_t& st)
+{
+  return sqrt(-2.0 * (P.I.T[0][a] * P.I.m[0] / kMec2) * log(u01(st)));
+}
+
+// MaxwellCosinePerturbation (:78-103, L of this call's box) and AngularMomentum (:105-125) as written; the other two are
+// inj_momentum
+__device__ inline void set_momentum(const SetDev& P, uint64_t& st, const double* r, double* p)
+{
+  if (P.mom == XPIC_MOMENTUM_COSINE_PERTURBATION) {
+    const double m = P.I.m[0];
+    for (int a = 0; a < 3; ++a) {
+      const double ph = sin(2.0 * M_PI * u01(st));
+      p[a] = ph * set_thermal(P, a, st);
+    }
+    const double den = sqrt(m * m + (p[0] * p[0] + p[1] * p[1] + p[2] * p[2]));
+    for (int a = 0; a < 3; ++a) {
+      p[a] /= den;
+      const double v0 = P.amp[a] * sqrt(P.I.T[0][a] / (m * kMec2));
+      p[a] += v0 * cos(2.0 * M_PI * P.wn[a] * r[a] / P.L[a]);
+    }
+  }
+  else if (P.mom == XPIC_MOMENTUM_ANGULAR) {
+    const double x = r[0] - P.center[0], y = r[1] - P.center[1];
+    const double rr = hypot(x, y);
+    const double t[3] = {set_thermal(P, 0, st), set_thermal(P, 1, st), set_thermal(P, 2, st)};
+    const double* v = P.I.value[0];
+    if (isinf(1.0 / rr)) { p[0] = 0.0 + t[0]; p[1] = 0.0 + t[1]; }
+    else { p[0] = -v[0] * (y / rr) + t[0]; p[1] = +v[1] * (x / rr) + t[1]; }
+    p[2] = v[2] + t[2];
+  }
+  else inj_momentum(P.I, 0, st, p);
+}
+
+// first pass over the particles p0 + [0, n) (grid-stride): the new records of every local cell, and their number (summed
+// over the wave, one atomic per wave and launch: a single counter taken once per 64 particles serialises the pass)
+__global__ void __launch_bounds__(kBlock) k_set_count(GridDev g, SetDev P, int64_t p0, int64_t n, int* add,
+  unsigned long long* nadded)
+{
+  int mine = 0;
+  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) {
+    uint64_t st = pair_stream(P.I, p0 + i);
+    double r[3];
+    set_coordinate(P, st, r);
+    const int c = cell_of(g, r[0], r[1], r[2]);
+    if (c >= 0) {
+      atomicAdd(&add[c], 1);
+      ++mine;
+    }
+  }
+  for (int o = 32; o > 0; o >>= 1) mine += __shfl_down(mine, o, 64);
+  if ((threadIdx.x & 63) == 0 && mine) atomicAdd(nadded, (unsigned long long)mine);
+}
+
+// second pass: the particle's record behind its cell's old records (cs: the old cell_start, ns: the new one), in the
+// slot the cell's cursor hands out; partial: the energy of the records written
+__global__ void __launch_bounds__(kBlock) k_set_write(GridDev g, SortDev s, SetDev P, int64_t p0, int64_t n,
+  const int* __restrict__ ns, int* cursor, double mpw, double* partial)
+{
+  double e[1] = {0.0};
+  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) {
+    uint64_t st = pair_stream(P.I, p0 + i);
+    double r[3], pm[3];
+    set_coordinate(P, st, r);
+    const int c = cell_of(g, r[0], r[1], r[2]);
+    if (c < 0) continue;
+    set_momentum(P, st, r, pm);
+    const long d = (long)ns[c] + (s.cell_start[c + 1] - s.cell_start[c]) + atomicAdd(&cursor[c], 1);
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      s.r2[a][d] = r[a];
+      s.v2[a][d] = pm[a];
+    }
+    e[0] += 0.5 * (P.I.m[0] * (pm[0] * pm[0] + pm[1] * pm[1] + pm[2] * pm[2])) * mpw;
   }
   block_reduce_store<1, kBlock>(e, partial, 0, blockIdx.x);
 }
@@ -464,10 +575,7 @@ int inject_particles(xpic_ctx* c, Sort& si, Sort& se, const xpic_inject_params& 
     for (int a = 0; a < 3; ++a) { P.value[k][a] = m.value[a]; P.T[k][a] = m.T[a]; }
     P.m[k] = sorts[k]->par.m;
   }
-  uint64_t key = p.seed;
-  (void)splitmix(key);
-  key ^= (uint64_t)step * 0xD1342543DE82EF95ull;
-  P.key = splitmix(key);
+  P.key = stream_key(p.seed, step);
   for (Sort* s : sorts) {
     XPIC_CALL(sort_materialize(c, *s)); // (a deferred re-binning whose assembly has not run)
     s->prebinned = false;               // (a pre-binning's keys would be taken for the new records' next step)
@@ -523,6 +631,147 @@ int inject_particles(xpic_ctx* c, Sort& si, Sort& se, const xpic_inject_params& 
   XPIC_CALL(comm_allreduce_sum_host(c, res, 3)); // (log_statistics, inject_particles.cpp:70-84)
   if (added) *added = (int64_t)res[0];
   if (energy2) { energy2[0] = res[1]; energy2[1] = res[2]; }
+  return 0;
+}
+
+namespace {
+
+const char* const kSetWho = "xpic_set_particles: ";
+
+bool all_finite(const double* v, int n)
+{
+  for (int i = 0; i < n; ++i)
+    if (!std::isfinite(v[i])) return false;
+  return true;
+}
+
+// the argument checks of set_particles; nothing has been touched when one of them fails
+int set_particles_params(const Sort& s, const xpic_set_particles_params& p, int64_t n, int64_t particle0, SetDev* P)
+{
+  const std::string who = kSetWho;
+  XPIC_CHECK(n >= 0 && particle0 >= 0 && p.chunk >= 0, who + "n, particle0 and chunk must not be negative");
+  XPIC_CHECK(particle0 <= INT64_MAX - n, who + "particle0 + n overflows");
+  XPIC_CHECK(p.coordinate >= XPIC_COORD_PRECISE && p.coordinate <= XPIC_COORD_ON_ANNULUS, who + "unknown coordinate generator");
+  XPIC_CHECK(p.momentum >= XPIC_MOMENTUM_PRECISE && p.momentum <= XPIC_MOMENTUM_ANGULAR, who + "unknown momentum generator");
+  XPIC_CHECK(std::isfinite(s.par.m) && s.par.m != 0.0 && s.par.Np > 0 && std::isfinite(s.par.n),
+    who + "the sort has no mass or no Np");
+  const int ngeom[4] = {3, 6, 5, 6};
+  XPIC_CHECK(all_finite(p.geom, ngeom[p.coordinate]), who + "non-finite geometry");
+  if (p.coordinate == XPIC_COORD_IN_CYLINDER) XPIC_CHECK(p.geom[3] >= 0.0, who + "negative radius");
+  if (p.coordinate == XPIC_COORD_ON_ANNULUS)
+    XPIC_CHECK(p.geom[3] >= 0.0 && p.geom[4] >= p.geom[3], who + "the annulus needs 0 <= inner_r <= outer_r");
+  *P = SetDev{};
+  P->coord = P->I.coord = p.coordinate;
+  P->mom = P->I.mkind[0] = p.momentum;
+  P->I.tov[0] = p.tov;
+  P->I.m[0] = s.par.m;
+  for (int i = 0; i < 7; ++i) P->I.geom[i] = p.geom[i];
+  if (p.momentum != XPIC_MOMENTUM_COSINE_PERTURBATION) {
+    XPIC_CHECK(all_finite(p.value, 3), who + "non-finite momentum");
+    for (int a = 0; a < 3; ++a) P->I.value[0][a] = p.value[a];
+  }
+  if (p.momentum != XPIC_MOMENTUM_PRECISE) {
+    XPIC_CHECK(all_finite(p.T, 3) && p.T[0] >= 0.0 && p.T[1] >= 0.0 && p.T[2] >= 0.0, who + "T must be finite and not negative");
+    for (int a = 0; a < 3; ++a) P->I.T[0][a] = p.T[a];
+  }
+  if (p.momentum == XPIC_MOMENTUM_COSINE_PERTURBATION) {
+    XPIC_CHECK(all_finite(p.amplitude, 3) && all_finite(p.wave_number, 3) && all_finite(p.box6, 6),
+      who + "non-finite perturbation");
+    for (int a = 0; a < 3; ++a) {
+      P->amp[a] = p.amplitude[a];
+      P->wn[a] = p.wave_number[a];
+      P->L[a] = p.box6[3 + a] - p.box6[a];
+      XPIC_CHECK(P->L[a] != 0.0, who + "the perturbation's box has no extent");
+    }
+  }
+  if (p.momentum == XPIC_MOMENTUM_ANGULAR) {
+    XPIC_CHECK(all_finite(p.center, 2), who + "non-finite center");
+    P->center[0] = p.center[0];
+    P->center[1] = p.center[1];
+  }
+  return 0;
+}
+
+}  // namespace
+
+int set_particles(xpic_ctx* c, Sort& s, const xpic_set_particles_params& p, int64_t n, int64_t particle0, int64_t step,
+  int64_t* added, double* energy)
+{
+  SetDev P;
+  XPIC_CALL(set_particles_params(s, p, n, particle0, &P));
+  P.I.key = stream_key(p.seed, step);
+  if (added) *added = 0;
+  if (energy) *energy = 0.0;
+  if (n == 0) return 0;
+  const int64_t chunk = p.chunk > 0 ? p.chunk : (int64_t)XPIC_SET_PARTICLES_CHUNK;
+  XPIC_CALL(sort_materialize(c, s)); // (a deferred re-binning whose assembly has not run)
+  XPIC_CALL(cmd_scratch(c));
+  Timed t(c, "cmd_set_particles");
+  // pass 1, every chunk: the new records per cell and their number
+  unsigned long long* nadd = (unsigned long long*)(c->red_out + 64);
+  XPIC_HIP(hipMemsetAsync(c->cmd_add, 0, sizeof(int) * (c->ncell + 1), c->stream));
+  XPIC_HIP(hipMemsetAsync(nadd, 0, sizeof(unsigned long long), c->stream));
+  for (int64_t i0 = 0; i0 < n; i0 += chunk) {
+    Timed tc(c, "cmd_set_count");
+    const int64_t ni = std::min(chunk, n - i0);
+    hipLaunchKernelGGL(k_set_count, dim3(rgrid(ni)), dim3(kBlock), 0, c->stream, c->g, P, particle0 + i0, ni, c->cmd_add, nadd);
+    XPIC_HIP(hipGetLastError());
+  }
+  unsigned long long hn = 0;
+  XPIC_HIP(hipMemcpyAsync(&hn, nadd, sizeof(hn), hipMemcpyDeviceToHost, c->stream));
+  XPIC_HIP(hipStreamSynchronize(c->stream));
+  // capacity (and the range of the cells' int counts and offsets: a cell's count that wrapped has hn beyond it), agreed on
+  // by all slabs before the sort changes (a slab that returned alone would hang the others)
+  const unsigned long long total_n = (unsigned long long)s.n + hn;
+  double over[1] = {(total_n > (unsigned long long)s.cap || total_n > 2147483000ull) ? 1.0 : 0.0};
+  XPIC_CALL(comm_allreduce_sum_host(c, over, 1));
+  XPIC_CHECK(over[0] == 0.0, std::string(kSetWho) + "sort capacity exceeded");
+  double res[2] = {(double)hn, 0.0}; // particles added, their energy
+  if (hn > 0) {
+    s.prebinned = false; // (a pre-binning's keys would be taken for the new records' next step)
+    const CmdGeom none{-1, {0, 0, 0, 0, 0, 0, 0}};
+    const unsigned nb = rgrid(c->ncell);
+    hipLaunchKernelGGL(k_cmd_count, dim3(nb), dim3(kBlock), 0, c->stream, c->g, s.d.cell_start, none, (const int*)c->cmd_add,
+      s.d.cell_count, (long)c->ncell, c->red_partial);
+    XPIC_HIP(hipGetLastError());
+    int total = 0;
+    XPIC_CALL(cmd_rebuild(c, s, none, &total, [&]() -> int {
+      // pass 2, every chunk: cmd_add becomes the cells' cursors; one energy per chunk, summed in the chunks' order
+      XPIC_HIP(hipMemsetAsync(c->cmd_add, 0, sizeof(int) * (c->ncell + 1), c->stream));
+      for (int64_t i0 = 0; i0 < n; i0 += chunk) {
+        Timed tw(c, "cmd_set_write");
+        const int64_t ni = std::min(chunk, n - i0);
+        const unsigned nw = rgrid(ni);
+        hipLaunchKernelGGL(k_set_write, dim3(nw), dim3(kBlock), 0, c->stream, c->g, s.d, P, particle0 + i0, ni, c->cmd_start,
+          c->cmd_add, s.par.n / s.par.Np, c->red_partial);
+        XPIC_HIP(hipGetLastError());
+        double e = 0.0;
+        XPIC_CALL(reduce_to_host(c, 1, nw, 1, false, &e, kSumThreads));
+        res[1] += e;
+      }
+      return 0;
+    }));
+  }
+  XPIC_CALL(comm_allreduce_sum_host(c, res, 2)); // (log_statistics, set_particles.cpp:49-51)
+  if (added) *added = (int64_t)res[0];
+  if (energy) *energy = res[1];
+  return 0;
+}
+
+int particles_number(xpic_ctx* c, const Sort& s, int coordinate, const double* geom, int64_t* out)
+{
+  const std::string who = "xpic_particles_number: ";
+  XPIC_CHECK(geom && out, who + "null argument");
+  XPIC_CHECK(coordinate >= XPIC_COORD_PRECISE && coordinate <= XPIC_COORD_ON_ANNULUS, who + "unknown coordinate generator");
+  const int Np = s.par.Np;
+  const double frac = Np / (c->g.dx * c->g.dy * c->g.dz); // particles_builder.cpp:17
+  double v;
+  if (coordinate == XPIC_COORD_PRECISE) v = Np;
+  else if (coordinate == XPIC_COORD_IN_BOX) v = (geom[3] - geom[0]) * (geom[4] - geom[1]) * (geom[5] - geom[2]) * frac;
+  else if (coordinate == XPIC_COORD_IN_CYLINDER) v = M_PI * (geom[3] * geom[3]) * geom[4] * frac;
+  else v = M_PI * (geom[4] * geom[4] - geom[3] * geom[3]) * geom[5] * frac;
+  XPIC_CHECK(std::isfinite(v) && std::fabs(v) < 9.0e18, who + "the count is not a 64-bit integer");
+  *out = (int64_t)v; // (the conversion to PetscInt truncates)
   return 0;
 }
 

@@ -381,6 +381,9 @@ int fields_damping(xpic_ctx* c, double* E, double* B, const double* B0, int geom
   double* energy);
 int inject_particles(xpic_ctx* c, Sort& si, Sort& se, const xpic_inject_params& p, int64_t pairs, int64_t step,
   int64_t* added, double* energy2);
+int set_particles(xpic_ctx* c, Sort& s, const xpic_set_particles_params& p, int64_t n, int64_t particle0, int64_t step,
+  int64_t* added, double* energy);
+int particles_number(xpic_ctx* c, const Sort& s, int coordinate, const double* geom, int64_t* out);
 int set_coils_field(xpic_ctx* c, double* F, int ncoils, const double* coils3);
 int set_mirror_field(xpic_ctx* c, double* F, double D, double R, double I);
 

@@ -406,6 +406,23 @@ PetscErrorCode SetParticles::execute(PetscInt /* t */) // src/commands/set_parti
   return 0;
 }
 
+SetParticlesDevice::SetParticlesDevice(interfaces::Simulation& sim, interfaces::Particles& particles,
+  int64_t number_of_particles, const xpic_set_particles_params& params)
+  : sim_(sim), particles_(particles), number_of_particles_(number_of_particles), params_(params)
+{
+}
+
+PetscErrorCode SetParticlesDevice::execute(PetscInt t)
+{
+  HIPCALL(xpic_set_particles(sim_.ctx, particles_.sort_id, &params_, std::max<int64_t>(number_of_particles_, 0), 0, t,
+    &added_particles, &added_energy));
+  char energy[40];
+  std::snprintf(energy, sizeof(energy), "%.17g", added_energy);
+  LOG("  Particles have been added into \"" << particles_.parameters.sort_name << "\" on the device: " << added_particles);
+  LOG("    energy: " << energy);
+  return 0;
+}
+
 SetMagneticField::SetMagneticField(interfaces::Simulation& sim, int field, int field_axpy, const Vector3R& v)
   : sim_(sim), field_(field), field_axpy_(field_axpy), value_(v)
 {
@@ -557,6 +574,74 @@ PetscErrorCode BinaryCollisions::execute(PetscInt t) // (an extension: no counte
   return 0;
 }
 
+// a SetParticles entry with "device": true -> xpic_set_particles' parameters and the builder's count
+// (xpic_particles_number).  Beside the reference's names it takes CoordinateOnAnnulus {center, inner_r, outer_r, height}
+// and AngularMomentum {center}, which the reference's builder does not offer.
+static std::unique_ptr<interfaces::Command> build_set_particles_device(interfaces::Simulation& simulation,
+  interfaces::Particles& particles, const Configuration::json_t& info)
+{
+  using interfaces::Builder;
+  xpic_set_particles_params p{};
+  const auto& ci = info.at("coordinate");
+  const std::string cname = ci.at("name").as_string();
+  if (cname == "PreciseCoordinate") {
+    p.coordinate = XPIC_COORD_PRECISE;
+    const Vector3R dot = Builder::parse_vector(ci, "value");
+    for (int i = 0; i < 3; ++i) p.geom[i] = dot[i];
+  }
+  else if (cname == "CoordinateInBox") {
+    p.coordinate = XPIC_COORD_IN_BOX;
+    load_geometry(ci, XPIC_GEOM_BOX, p.geom);
+  }
+  else if (cname == "CoordinateInCylinder") {
+    p.coordinate = XPIC_COORD_IN_CYLINDER;
+    load_geometry(ci, XPIC_GEOM_CYLINDER, p.geom);
+  }
+  else if (cname == "CoordinateOnAnnulus") {
+    p.coordinate = XPIC_COORD_ON_ANNULUS;
+    load_geometry(ci, XPIC_GEOM_CYLINDER, p.geom); // (the centre's and the height's defaults)
+    p.geom[5] = p.geom[4];
+    p.geom[3] = ci.at("inner_r").as_double();
+    p.geom[4] = ci.at("outer_r").as_double();
+  }
+  else throw std::runtime_error("Unknown coordinate generator name " + cname);
+  const auto& mi = info.at("momentum");
+  const std::string mname = mi.at("name").as_string();
+  const SortParameters& sp = particles.parameters;
+  const double T[3] = {sp.Tx, sp.Ty, sp.Tz}, drift[3] = {sp.px, sp.py, sp.pz};
+  for (int i = 0; i < 3; ++i) { p.T[i] = T[i]; p.value[i] = drift[i]; }
+  if (mname == "PreciseMomentum") {
+    p.momentum = XPIC_MOMENTUM_PRECISE;
+    const Vector3R value = Builder::parse_vector(mi, "value");
+    for (int i = 0; i < 3; ++i) p.value[i] = value[i];
+  }
+  else if (mname == "MaxwellianMomentum") {
+    p.momentum = XPIC_MOMENTUM_MAXWELLIAN;
+    p.tov = mi.contains("tov") ? mi.at("tov").as_bool() : false;
+  }
+  else if (mname == "MaxwellCosinePerturbation") {
+    p.momentum = XPIC_MOMENTUM_COSINE_PERTURBATION;
+    double box[7];
+    load_geometry(mi, XPIC_GEOM_BOX, box);
+    const Vector3R a = Builder::parse_vector(mi, "amplitude"), m = Builder::parse_vector(mi, "wave_number");
+    for (int i = 0; i < 3; ++i) { p.amplitude[i] = a[i]; p.wave_number[i] = m[i]; }
+    for (int i = 0; i < 6; ++i) p.box6[i] = box[i];
+  }
+  else if (mname == "AngularMomentum") {
+    p.momentum = XPIC_MOMENTUM_ANGULAR;
+    Vector3R c;
+    c[0] = 0.5 * geom_x; c[1] = 0.5 * geom_y;
+    if (mi.contains("center")) c = Builder::parse_vector(mi, "center");
+    for (int i = 0; i < 3; ++i) p.center[i] = c[i];
+  }
+  else throw std::runtime_error("Unknown coordinate generator name " + mname);
+  if (info.contains("seed")) p.seed = (uint64_t)info.at("seed").as_double();
+  int64_t number = 0;
+  if (xpic_particles_number(simulation.ctx, particles.sort_id, p.coordinate, p.geom, &number) != 0)
+    throw std::runtime_error(std::string("SetParticles (device): ") + xpic_last_error());
+  return std::make_unique<SetParticlesDevice>(simulation, particles, number, p);
+}
+
 // build_commands (src/commands/builders/command_builder.cpp:16-62) with ParticlesBuilder::load_coordinate /
 // load_momentum (particles_builder.cpp:9-68) and SetMagneticFieldBuilder (set_magnetic_field_builder.cpp:11-63)
 PetscErrorCode build_commands(interfaces::Simulation& simulation, const std::string& name,
@@ -578,12 +663,17 @@ PetscErrorCode build_commands(interfaces::Simulation& simulation, const std::str
     const std::string command = info.at("command").as_string();
     if (command == "SetParticles") {
       auto& particles = simulation.get_named_particles(info.at("particles").as_string());
+      const auto& ci = info.at("coordinate");
+      const std::string cname = ci.at("name").as_string();
+      if (info.contains("device") && info.at("device").as_bool()) {
+        result.emplace_back(build_set_particles_device(simulation, particles, info));
+        LOG("  SetParticles command (device) is added for \"" << particles.parameters.sort_name << "\"");
+        continue;
+      }
       const PetscInt Np = particles.parameters.Np;
       const PetscReal frac = Np / (dx * dy * dz);
       PetscInt number_of_particles = 0;
       CoordinateGenerator gc;
-      const auto& ci = info.at("coordinate");
-      const std::string cname = ci.at("name").as_string();
       if (cname == "PreciseCoordinate") {
         number_of_particles = Np;
         Vector3R dot = Builder::parse_vector(ci, "value");
@@ -643,6 +733,30 @@ PetscErrorCode build_commands(interfaces::Simulation& simulation, const std::str
             for (int c = 0; c < 3; ++c) result[c] /= g;
           }
           return result;
+        };
+      }
+      else if (mname == "MaxwellCosinePerturbation") { // particles_load.cpp:78-103, particles_builder.cpp:57-65
+        double box[7];
+        load_geometry(mi, XPIC_GEOM_BOX, box);
+        const Vector3R a = Builder::parse_vector(mi, "amplitude"), m = Builder::parse_vector(mi, "wave_number");
+        // (the reference keeps the extents in `static const` locals, so its first generator's box serves all; this
+        // one takes its own)
+        const Vector3R L{{box[3] - box[0], box[4] - box[1], box[5] - box[2]}};
+        SortParameters params = particles.parameters;
+        gm = [params, a, m, L](const Vector3R& coordinate) {
+          const PetscReal T[3] = {params.Tx, params.Ty, params.Tz};
+          Vector3R v;
+          for (int c = 0; c < 3; ++c) { // sin(2 pi u) is drawn before sqrt(-2..ln u), as in MaxwellianMomentum above
+            const PetscReal s = std::sin(2.0 * M_PI * random_01());
+            v[c] = s * temperature_momentum(T[c], params.m);
+          }
+          const PetscReal g = std::sqrt(params.m * params.m + v.squared());
+          for (int c = 0; c < 3; ++c) {
+            v[c] /= g;
+            const PetscReal v0 = a[c] * sqrt(T[c] / (params.m * mec2));
+            v[c] += v0 * std::cos(2.0 * M_PI * m[c] * coordinate[c] / L[c]);
+          }
+          return v;
         };
       }
       else throw std::runtime_error("Unknown coordinate generator name " + mname);

@@ -211,6 +211,24 @@ private:
   MomentumGenerator generate_momentum_;
 };
 
+// EXTENSION (not reference behaviour): a SetParticles entry with "device": true is drawn on the device by
+// xpic_set_particles from this build's counter-based stream ("seed", default 0) instead of std::mt19937 on the host;
+// the count is the builder's.  Without the key the entry takes the class above, as it always has.
+class SetParticlesDevice : public interfaces::Command {
+public:
+  SetParticlesDevice(interfaces::Simulation& sim, interfaces::Particles& particles, int64_t number_of_particles,
+    const xpic_set_particles_params& params);
+  PetscErrorCode execute(PetscInt t) override;
+  int64_t added_particles = 0;
+  PetscReal added_energy = 0;
+
+private:
+  interfaces::Simulation& sim_;
+  interfaces::Particles& particles_;
+  int64_t number_of_particles_;
+  xpic_set_particles_params params_;
+};
+
 class SetMagneticField : public interfaces::Command {
 public:
   SetMagneticField(interfaces::Simulation& sim, int field, int field_axpy, const Vector3R& uniform_value);
