@@ -73,6 +73,8 @@ int gmres(xpic_ctx* c, int op, const double* b, double* x, double rtol, double a
   XPIC_CALL(vec_set(c, x, 0.0));
   double bb;
   XPIC_CALL(vec_dot_host(c, b, b, &bb));
+  // (an infinite |b| would pass for converged below, inf <= rtol inf; the sum is all-reduced: every slab refuses alike)
+  XPIC_CHECK(std::isfinite(bb), "solve: the right-hand side is not finite");
   const double bnorm = std::sqrt(bb);
   // The preconditioned "correct" solve costs next to nothing per iteration: it is run two orders beyond the
   // requested tolerance, so its result does not depend on where inside the tolerance the iteration happens to stop
@@ -204,6 +206,7 @@ int cg(xpic_ctx* c, int op, const double* b, double* x, double rtol, double atol
   XPIC_CALL(vec_copy(c, p, b));
   double rr;
   XPIC_CALL(vec_dot_host(c, r, r, &rr));
+  XPIC_CHECK(std::isfinite(rr), "solve: the right-hand side is not finite");
   const double tol = std::max(rtol * std::sqrt(rr), atol);
   int its = 0;
   while (std::sqrt(rr) > tol && its < maxit) {
