@@ -954,4 +954,6 @@ int xpic_probe_copy_bandwidth(xpic_ctx* ctx, int64_t bytes, int reps, double* by
 #endif
 /* ---- SetParticles on the device and the builder's particle count: their entry points and their definition */
 #include "xpic_set_particles.h"
+/* ---- tracer sets that live on the device and ride along with the step, and grad |F| of a grid vector */
+#include "xpic_tracers.h"
 #endif

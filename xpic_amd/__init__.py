@@ -166,7 +166,7 @@ _lib = None
 
 
 def load_library():
-    """Loads libxpic_hip.so and types every entry point from PROTOTYPES and LOAD_PROTOTYPES; raises if it has not been built (no fallback
+    """Loads libxpic_hip.so and types every entry point from PROTOTYPES, LOAD_PROTOTYPES and TRACER_PROTOTYPES; raises if it has not been built (no fallback
     path exists).  The xpic_debug_*_stamps symbols of experiment builds are not in the header and stay untyped."""
     global _lib
     if _lib is not None:
@@ -175,7 +175,7 @@ def load_library():
         raise XpicError(f"{LIB_PATH} is missing: run `make` (or __graft_entry__.build()) first; "
                         "xpic_amd has no CPU fallback")
     L = C.CDLL(LIB_PATH)
-    for name, (ret, args) in dict(PROTOTYPES, **LOAD_PROTOTYPES).items():
+    for name, (ret, args) in dict(PROTOTYPES, **LOAD_PROTOTYPES, **TRACER_PROTOTYPES).items():
         f = getattr(L, name)
         f.restype, f.argtypes = CTYPES[ret], [CTYPES[a] for a in args]
     if L.xpic_version() & VERSION_EXPERIMENT_BIT and os.environ.get("XPIC_ALLOW_EXPERIMENT") != "1":
@@ -249,7 +249,87 @@ class LoadCommands:
         return out.value
 
 
-class Context(LoadCommands):
+class TracerState(collections.namedtuple(
+        "TracerState", "state exit_step iterations_sum iterations_max steps removed alive held dropped")):
+    """what TracerSet.get returns: the arrays of an OpenTrace, then the set's counts (steps done since it was created,
+    particles removed, particles alive, sample rows held, sample rows dropped)"""
+
+
+class TracerSet:
+    """A tracer set of a Context (include/xpic_tracers.h): made by Context.tracers, lives on the device until close()"""
+
+    def __init__(self, ctx, set_id, n, sample_capacity=0):
+        self.ctx, self.id, self.n, self.sample_capacity = ctx, set_id, n, sample_capacity
+
+    def advance(self, steps=1):
+        """`steps` steps on the context's E and B as they stand"""
+        self.ctx._ck(self.ctx.L.xpic_tracers_advance(self.ctx.h, self.id, int(steps)))
+
+    def attach(self, on=True):
+        """while attached, every Context.step advances the set by one step on the fields the step leaves behind"""
+        self.ctx._ck(self.ctx.L.xpic_tracers_attach(self.ctx.h, self.id, int(bool(on))))
+
+    def detach(self):
+        self.attach(False)
+
+    def get(self):
+        """-> TracerState; the arrays are copies"""
+        n = self.n
+        state, ex = np.zeros((n, 6)), np.zeros(n, dtype=np.int64)
+        tot, mx, info = np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int32), np.zeros(5, dtype=np.int64)
+        self.ctx._ck(self.ctx.L.xpic_tracers_get(self.ctx.h, self.id, _dp(state), _i64p(ex), _i64p(tot), _i32p(mx), _i64p(info)))
+        return TracerState(state, ex, tot, mx, *(int(v) for v in info))
+
+    def samples(self):
+        """drains the sample buffer -> (samples [rows][n][6], alive [rows]); row k of a set that has never been drained is
+        the state after step (k + 1) * sample_every"""
+        cap = self.sample_capacity
+        samples, alive, count = np.zeros((cap, self.n, 6)), np.zeros(cap, dtype=np.int64), C.c_int64()
+        self.ctx._ck(self.ctx.L.xpic_tracers_samples(self.ctx.h, self.id, _dp(samples), _i64p(alive), C.byref(count)))
+        return samples[:count.value], alive[:count.value]
+
+    def close(self):
+        if self.id is not None:
+            set_id, self.id = self.id, None
+            self.ctx._ck(self.ctx.L.xpic_tracers_destroy(self.ctx.h, set_id))
+
+
+class TracerCommands:
+    """grad |F| of a grid vector and the tracer sets (include/xpic_tracers.h), as methods of Context"""
+
+    def grad_abs_field(self, src, dst):
+        """dst = the central differences of |src| on the nodes, every index wrapped (xpic_grad_abs_field)"""
+        self._ck(self.L.xpic_grad_abs_field(self.h, int(src), int(dst)))
+
+    def tracers(self, kind, state, *params, region=None, step0=0, compact="never", gradB_field=None, sample_every=0,
+                sample_capacity=0, **tolerances):
+        """A tracer set -> TracerSet.  kind "full_orbit": params = (scheme, qm, dt) and atol, rtol, maxit as
+        full_orbit_trace_open's; kind "drift_kinetic": params = (qm, mp, dt) and eps, delta, maxit as
+        drift_kinetic_trace_open's, gradB_field a field id, None (grad B = 0) or "auto" (the set layer computes grad |B| of
+        the context's B before every advance).  region: a geometry dict or None (nothing is ever removed); step0 and
+        compact as the open traces'.  sample_every 0: no samples; the buffer holds sample_capacity rows."""
+        state = np.ascontiguousarray(state, dtype=np.float64).reshape(-1, 6)
+        k = TRACER_KINDS[kind]
+        if k == 0:
+            scheme, qm, dt = params
+            P = self._fo_params(scheme, qm, dt, *(tolerances.pop(w, v) for w, v in (("atol", 1e-7), ("rtol", 1e-7), ("maxit", 30))))
+        else:
+            qm, mp, dt = params
+            P = self._dk_params(qm, mp, dt, *(tolerances.pop(w, v) for w, v in (("eps", 1e-12), ("delta", 1e-12), ("maxit", 30))))
+        if tolerances:
+            raise XpicError("tracers: unknown arguments %s" % sorted(tolerances))
+        reg = None
+        if region is not None:
+            geom, gp = _geom7(region)
+            reg = C.byref(TraceRegion(geom, int(COMPACT.get(compact, compact)), (C.c_double * 7)(*gp[:7]), int(step0)))
+        gB = -1 if gradB_field is None else GRADB_AUTO if isinstance(gradB_field, str) and gradB_field == "auto" else int(gradB_field)
+        out = C.c_int()
+        self._ck(self.L.xpic_tracers_create(self.h, k, state.shape[0], C.cast(C.pointer(P), C.c_void_p), _dp(state), reg, gB,
+                                            int(sample_every), int(sample_capacity), C.byref(out)))
+        return TracerSet(self, out.value, state.shape[0], int(sample_capacity) if sample_every else 0)
+
+
+class Context(LoadCommands, TracerCommands):
     """One z-slab context = one `interfaces::Simulation` backend instance."""
 
     def __init__(self, scheme, n, d, dt, device=0, rank=0, nranks=1, self_ring=False):

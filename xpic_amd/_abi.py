@@ -292,3 +292,18 @@ LOAD_PROTOTYPES = {
                                    "int64_t*", "double*"]),
     "xpic_particles_number": ("int", ["xpic_ctx*", "int", "int", "const double*", "int64_t*"]),
 }
+# the entry points of include/xpic_tracers.h, typed by load_library() as PROTOTYPES' are; tests/test_abi_tracers.py holds them
+# to that header
+TRACER_PROTOTYPES = {
+    "xpic_grad_abs_field": ("int", ["xpic_ctx*", "int", "int"]),
+    "xpic_tracers_create": ("int", ["xpic_ctx*", "int", "int64_t", "const void*", "const double*", "const xpic_trace_region*",
+                                    "int", "int64_t", "int64_t", "int*"]),
+    "xpic_tracers_advance": ("int", ["xpic_ctx*", "int", "int64_t"]),
+    "xpic_tracers_attach": ("int", ["xpic_ctx*", "int", "int"]),
+    "xpic_tracers_get": ("int", ["xpic_ctx*", "int", "double*", "int64_t*", "int64_t*", "int*", "int64_t*"]),
+    "xpic_tracers_samples": ("int", ["xpic_ctx*", "int", "double*", "int64_t*", "int64_t*"]),
+    "xpic_tracers_destroy": ("int", ["xpic_ctx*", "int"]),
+}
+TRACERS_MAX_SETS = 8  # XPIC_TRACERS_MAX_SETS
+TRACER_KINDS = {"full_orbit": 0, "drift_kinetic": 1}  # XPIC_TRACERS_FULL_ORBIT, XPIC_TRACERS_DRIFT_KINETIC
+GRADB_AUTO = -2  # XPIC_GRADB_AUTO

@@ -266,15 +266,68 @@ int batch_compare_trace(xpic_ctx* c, const char* label, int launch_steps, int64_
 int live_compact(xpic_ctx* c, const char* label, const int64_t* exit_step, const int64_t* list, int64_t m, int64_t cap,
   int64_t* out, double* blk, int64_t* off);
 
+// The list of live particles of an open trace and what the host knows of it.  batch_trace keeps one for the length of a
+// call, a tracer set (tracers.hip) for its life.
+struct LiveList {
+  DevScratch<double> blk;        // live_compact's count per workgroup and
+  DevScratch<int64_t> off;       // its prefix: sized by the first compaction (the list only shrinks)
+  DevScratch<int64_t> lst[2];    // the list and the one the next compaction writes, alternating
+  const int64_t* list = nullptr; // the entries the next launch covers: null = every particle
+  int64_t listed = 0, live = 0;  // its entries, and how many of them are alive
+  int64_t gone = 0;              // what the device's `removed` count held when it was last read
+  int next = 0;                  // the buffer the next compaction writes
+  bool due = false;              // a launch has run since the list was last weighed (trace_compacts)
+};
+
+// The launches of steps first + 1 .. first + steps of a trace whose arrays `d` names, in launches of at most launch_steps
+// steps, each timed under `label`.  track: after every launch the count removed so far comes back (8 bytes, one
+// synchronisation), so the host knows how many entries are alive: when none is, the remaining launches are skipped, and by
+// `policy` (trace_compacts) the list is rebuilt in front of the next launch, timed under `compact_label`.  Without it
+// nothing is read back and nothing synchronises between the launches.  d.first and d.ns, d.list and d.m are set here.
+template <class Launch>
+int trace_launches(xpic_ctx* c, const char* label, const char* compact_label, int launch_steps, int64_t first, int64_t steps,
+  int policy, bool track, TraceDev& d, LiveList& L, Launch launch)
+{
+  const int64_t end = first + steps;
+  for (; first < end && L.live > 0; first += launch_steps) {
+    if (L.due && trace_compacts(policy, L.live, L.listed)) {
+      if (!L.blk.p) { // (the list only shrinks: the first compaction's workgroup count bounds the later ones)
+        const size_t nb = lane_grid(L.listed).x;
+        XPIC_CALL(L.blk.alloc(nb)); XPIC_CALL(L.off.alloc(nb));
+      }
+      // (so do the live counts: buffer 0 is as long as the first list, buffer 1 as the second, and they alternate)
+      if (!L.lst[L.next].p) XPIC_CALL(L.lst[L.next].alloc(L.live));
+      XPIC_CALL(live_compact(c, compact_label, (const int64_t*)d.exit_step, L.list, L.listed, L.live, L.lst[L.next].p, L.blk.p,
+        L.off.p));
+      L.list = L.lst[L.next].p;
+      L.listed = L.live;
+      L.next ^= 1;
+    }
+    L.due = false;
+    d.list = (const long long*)L.list; d.m = (long)L.listed;
+    d.first = (long)first; d.ns = (int)std::min<int64_t>(launch_steps, end - first);
+    {
+      Timed t(c, label);
+      launch(d);
+      XPIC_HIP(hipGetLastError());
+    }
+    if (!track) continue;
+    int64_t g = 0;
+    XPIC_HIP(hipMemcpyAsync(&g, d.removed, sizeof g, hipMemcpyDeviceToHost, c->stream));
+    XPIC_HIP(hipStreamSynchronize(c->stream));
+    L.live -= g - L.gone;
+    L.gone = g;
+    L.due = true;
+  }
+  return 0;
+}
+
 // The steps of A (TraceArrays, A.n > 0) in place in A.state_6, the particles kept on the device, with the region rule of
 // an open trace (include/xpic_hip.h: xpic_trace_region) when the kernel applies one.  `d` (TraceDev) comes
 // with nsamp (trace_sample_bytes) and extra set by the caller; its other members are filled here, and launch(d) starts
-// the kernel, each launch timed under `label`.  A.sums_4 is the caller's to stage (trace_call.h).  With A.removed, the
-// count removed so far comes back after every launch (8 bytes), so the host knows how many entries are alive: when none
-// is, the remaining launches are skipped, and by `policy` (trace_compacts) the list is rebuilt for the next launch, timed
-// under `compact_label`.  Without it nothing is read back and nothing synchronises between the launches.  The sample rows
-// behind a removed particle's last step are filled here, on the host, from the final state (fill_frozen_samples): a launch
-// no longer covers a particle that compaction has dropped.
+// the kernel (trace_launches, which tracks the live list when A.removed is given).  A.sums_4 is the caller's to stage
+// (trace_call.h).  The sample rows behind a removed particle's last step are filled here, on the host, from the final
+// state (fill_frozen_samples): a launch no longer covers a particle that compaction has dropped.
 template <class Launch>
 int batch_trace(xpic_ctx* c, const char* label, const char* compact_label, int launch_steps, const TraceArrays& A, int policy,
   int64_t step0, TraceDev d, Launch launch)
@@ -289,8 +342,8 @@ int batch_trace(xpic_ctx* c, const char* label, const char* compact_label, int l
   else exit_step = exit_own.data();
   int64_t live = 0;
   for (int64_t q = 0; q < n; ++q) live += exit_in[q] < 0;
-  DevScratch<double> s, sm, blk;
-  DevScratch<int64_t> tot, ex, al, rm, off, lst[2];
+  DevScratch<double> s, sm;
+  DevScratch<int64_t> tot, ex, al, rm;
   DevScratch<int> mx;
   XPIC_CALL(s.alloc(row)); XPIC_CALL(ex.alloc(n)); XPIC_CALL(rm.alloc(1));
   XPIC_CALL(zero(rm, 1, c->stream));
@@ -308,36 +361,9 @@ int batch_trace(xpic_ctx* c, const char* label, const char* compact_label, int l
   d.s = s.p; d.samples = sm.p; d.exit_step = (long long*)ex.p;
   d.it_sum = (long long*)tot.p; d.it_max = mx.p;
   d.alive = (unsigned long long*)al.p; d.removed = (unsigned long long*)rm.p;
-  const int64_t* list = nullptr; // the entries the next launch covers: null = every particle
-  int64_t listed = n, gone = 0;
-  int next = 0;                  // the buffer the next compaction writes
-  for (int64_t first = 0; first < steps && live > 0; first += launch_steps) {
-    d.list = (const long long*)list; d.m = (long)listed;
-    d.first = (long)first; d.ns = (int)std::min<int64_t>(launch_steps, steps - first);
-    {
-      Timed t(c, label);
-      launch(d);
-      XPIC_HIP(hipGetLastError());
-    }
-    if (!A.removed) continue;
-    int64_t g = 0;
-    XPIC_CALL(download(&g, rm, 1, c->stream));
-    XPIC_HIP(hipStreamSynchronize(c->stream));
-    live -= g - gone;
-    gone = g;
-    if (first + launch_steps < steps && live > 0 && trace_compacts(policy, live, listed)) {
-      if (!blk.p) { // (the list only shrinks: the first compaction's workgroup count bounds the later ones)
-        const size_t nb = lane_grid(listed).x;
-        XPIC_CALL(blk.alloc(nb)); XPIC_CALL(off.alloc(nb));
-      }
-      // (so do the live counts: buffer 0 is as long as the first list, buffer 1 as the second, and they alternate)
-      if (!lst[next].p) XPIC_CALL(lst[next].alloc(live));
-      XPIC_CALL(live_compact(c, compact_label, ex.p, list, listed, live, lst[next].p, blk.p, off.p));
-      list = lst[next].p;
-      listed = live;
-      next ^= 1;
-    }
-  }
+  LiveList L;
+  L.listed = n; L.live = live;
+  XPIC_CALL(trace_launches(c, label, compact_label, launch_steps, 0, steps, policy, A.removed != nullptr, d, L, launch));
   XPIC_CALL(download(h.data(), s, row, c->stream));
   XPIC_CALL(download(exit_step, ex, n, c->stream));
   if (A.counters) {
@@ -355,7 +381,7 @@ int batch_trace(xpic_ctx* c, const char* label, const char* compact_label, int l
     for (int64_t k = 0; k < nsamp; ++k) to_aos(hs.data() + row * k, n, A.samples + row * k);
     fill_frozen_samples(n, nsamp, A.sample_every, step0, exit_in.data(), exit_step, A.state_6, A.samples);
   }
-  if (A.removed) *A.removed = gone;
+  if (A.removed) *A.removed = L.gone;
   return 0;
 }
 

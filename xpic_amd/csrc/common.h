@@ -195,6 +195,8 @@ struct ProfileEntry {
   std::vector<std::pair<hipEvent_t, hipEvent_t>> pending;
 };
 
+struct TracerSets; // tracers.hip: the tracer sets of a context
+
 }  // namespace xpic
 
 struct xpic_ctx {
@@ -255,6 +257,7 @@ struct xpic_ctx {
   int64_t cmd_rank_n = 0;
   int64_t collide_large_cells = 0; // collide.hip: local cells of the last call that took the second path
   double* bg_profile[XPIC_TRACE_BG_MAX] = {}; // background.hip: the background profiles, [5][ncell] each; null: an empty slot
+  xpic::TracerSets* tracers = nullptr; // tracers.hip: made by the first xpic_tracers_create; null: xpic_step has nothing to carry
   double rtol = 1e-7, atol = 1e-7;
   int maxit = 100;
   xpic::Comm comm;
@@ -346,6 +349,7 @@ int halo_add(xpic_ctx* c, double* f, int width);      // owned planes += neighbo
 int matL_exchange_ghost_rows(xpic_ctx* c);  // blocking: post + finish
 int matL_ghost_rows_post(xpic_ctx* c);      // ship this slab's two ghost row planes (on the communication stream when overlapping)
 int matL_ghost_rows_finish(xpic_ctx* c);    // add the neighbours' rows into the first / last owned row plane
+int grad_abs_field(xpic_ctx* c, const double* src, double* dst); // dst = central differences of |src| on the nodes (G == 0)
 
 // particles.hip
 int sort_alloc(xpic_ctx* c, Sort& s, int64_t cap);
@@ -393,6 +397,10 @@ int collide(xpic_ctx* c, int sort_a, int sort_b, const xpic_collision_params& p,
 
 // background.hip: frees the background profiles (xpic_destroy)
 void background_free(xpic_ctx* c);
+
+// tracers.hip: one step of every attached set, in creation order (xpic_step, only when c->tracers); frees the sets (xpic_destroy)
+int tracers_ride(xpic_ctx* c);
+void tracers_free(xpic_ctx* c);
 
 // ecsim.hip
 int ecsim_fill_sort(xpic_ctx* c, Sort& s, const double* B, double* currI_sort, double* matL, bool first_sort, bool post_ghost_rows);

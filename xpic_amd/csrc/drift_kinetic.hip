@@ -152,14 +152,20 @@ int dk_trace(xpic_ctx* ctx, const TraceEntry& E, const xpic_dk_params* params, c
       if (E.closed) // its text takes no region: the driver's stand-ins for exit_step and removed stay unused
         hipLaunchKernelGGL(gradB ? k_dk_trace<true> : k_dk_trace<false>, lane_grid(n), dim3(kBlock), 0, ctx->stream, ctx->g,
           ctx->field[XPIC_E], ctx->field[XPIC_B], gradB, *params, n, d.s, d.first, d.ns, every, d.samples, d.it_sum, d.it_max);
-      else
-        hipLaunchKernelGGL(gradB ? k_dk_trace_open<true> : k_dk_trace_open<false>, lane_grid(d.m), dim3(kBlock), 0,
-          ctx->stream, ctx->g, ctx->field[XPIC_E], ctx->field[XPIC_B], gradB, *params, R, n, d.s, d.list, d.m, d.first, d.ns,
-          every, d.nsamp, d.samples, d.it_sum, d.it_max, d.exit_step, d.alive, d.removed);
+      else dk_launch_open(ctx, *params, gradB, R, n, every, d);
     });
 }
 
 }  // namespace
+
+// one launch of the open trace (trace_call.h): the entry point above and the tracer sets of tracers.hip start it here
+void dk_launch_open(xpic_ctx* ctx, const xpic_dk_params& P, const double* gradB, const OpenRegion& R, long n, long every,
+  const TraceDev& d)
+{
+  hipLaunchKernelGGL(gradB ? k_dk_trace_open<true> : k_dk_trace_open<false>, lane_grid(d.m), dim3(kBlock), 0, ctx->stream,
+    ctx->g, ctx->field[XPIC_E], ctx->field[XPIC_B], gradB, P, R, n, d.s, d.list, d.m, d.first, d.ns, every, d.nsamp, d.samples,
+    d.it_sum, d.it_max, d.exit_step, d.alive, d.removed);
+}
 
 }  // namespace xpic
 

@@ -1168,4 +1168,91 @@ int matL_exchange_ghost_rows(xpic_ctx* c)
   return matL_ghost_rows_finish(c);
 }
 
+// ---- grad |F| on the nodes (xpic_grad_abs_field, include/xpic_tracers.h) ---------------
+// out[c][node] = (|F|(node + e_c) - |F|(node - e_c)) / (2 d_c), |F| = sqrt((Fx Fx + Fy Fy) + Fz Fz) of the three components
+// stored at the node, every index wrapped (single z-slab, G == 0).  A plane march: a workgroup owns a tile of kGaX x kGaY
+// nodes in (x, y) and walks kGaZ planes of it.  Each thread keeps |F| of its kGaRows nodes for the planes z - 1, z, z + 1
+// in registers (the z difference), the plane z lies in LDS with a one-node ring around the tile (the x and y
+// differences).  |F| of a node is formed once by the tile that owns it, once more per tile edge or chunk end it borders.
+// Wave w of the workgroup owns the rows w, w + 4, .. of the tile: a wave reads and writes whole 512-byte runs of x.
+namespace {
+constexpr int kGaX = 64, kGaRows = 4, kGaY = (kBlock / kGaX) * kGaRows, kGaZ = 16;
+
+__device__ inline double ga_abs(const GridDev& g, const double* __restrict__ F, int x, int y, int z)
+{
+#pragma clang fp contract(off)
+  const long i = g.node(x, y, z);
+  const double fx = F[i], fy = F[i + g.cstride], fz = F[i + 2 * g.cstride];
+  return sqrt((fx * fx + fy * fy) + fz * fz);
+}
+
+__global__ void __launch_bounds__(kBlock) k_grad_abs(GridDev g, const double* __restrict__ F, double* __restrict__ out)
+{
+#pragma clang fp contract(off)
+  __shared__ double sm[kGaY + 2][kGaX + 2];
+  const int tx = threadIdx.x % kGaX, ty = threadIdx.x / kGaX, t = threadIdx.x;
+  const int x0 = blockIdx.x * kGaX, y0 = blockIdx.y * kGaY, z0 = blockIdx.z * kGaZ;
+  const int w = min(kGaX, g.nx - x0), h = min(kGaY, g.ny - y0), z1 = min(z0 + kGaZ, g.nzl);
+  const int x = x0 + tx;
+  const bool col = tx < w;
+  // the ring node this thread fills, if any: the rows below and above the tile, then the columns left and right of it
+  int hx = -1, hy = 0, sx = 0, sy = 0;
+  if (t < w) { hx = x0 + t; hy = g.wy(y0 - 1); sx = t + 1; sy = 0; }
+  else if (t < 2 * w) { hx = x0 + t - w; hy = g.wy(y0 + h); sx = t - w + 1; sy = h + 1; }
+  else if (t < 2 * w + h) { hx = g.wx(x0 - 1); hy = y0 + t - 2 * w; sx = 0; sy = t - 2 * w + 1; }
+  else if (t < 2 * w + 2 * h) { hx = g.wx(x0 + w); hy = y0 + t - 2 * w - h; sx = w + 1; sy = t - 2 * w - h + 1; }
+  double mprev[kGaRows], mcur[kGaRows], mnext[kGaRows];
+#pragma unroll
+  for (int r = 0; r < kGaRows; ++r) {
+    const int ly = ty + (kBlock / kGaX) * r;
+    const bool own = col && ly < h;
+    mprev[r] = own ? ga_abs(g, F, x, y0 + ly, g.wz(z0 - 1)) : 0.0;
+    mcur[r] = own ? ga_abs(g, F, x, y0 + ly, z0) : 0.0;
+    if (own) sm[ly + 1][tx + 1] = mcur[r];
+  }
+  if (hx >= 0) sm[sy][sx] = ga_abs(g, F, hx, hy, z0);
+  __syncthreads();
+  const double hdx = 2.0 * g.dx, hdy = 2.0 * g.dy, hdz = 2.0 * g.dz;
+  for (int z = z0; z < z1; ++z) {
+    const int zn = g.wz(z + 1);
+    const bool more = z + 1 < z1; // uniform: the plane z + 1 is this workgroup's too
+    double ring = 0.0;
+    if (more && hx >= 0) ring = ga_abs(g, F, hx, hy, zn);
+#pragma unroll
+    for (int r = 0; r < kGaRows; ++r) {
+      const int ly = ty + (kBlock / kGaX) * r;
+      if (!(col && ly < h)) continue;
+      mnext[r] = ga_abs(g, F, x, y0 + ly, zn);
+      const long i = g.node(x, y0 + ly, z);
+      out[i] = (sm[ly + 1][tx + 2] - sm[ly + 1][tx]) / hdx;
+      out[i + g.cstride] = (sm[ly + 2][tx + 1] - sm[ly][tx + 1]) / hdy;
+      out[i + 2 * g.cstride] = (mnext[r] - mprev[r]) / hdz;
+    }
+    __syncthreads(); // every read of plane z is done
+    if (more) {
+#pragma unroll
+      for (int r = 0; r < kGaRows; ++r) {
+        const int ly = ty + (kBlock / kGaX) * r;
+        if (col && ly < h) sm[ly + 1][tx + 1] = mnext[r];
+        mprev[r] = mcur[r];
+        mcur[r] = mnext[r];
+      }
+      if (hx >= 0) sm[sy][sx] = ring;
+    }
+    __syncthreads();
+  }
+}
+}  // namespace
+
+int grad_abs_field(xpic_ctx* c, const double* src, double* dst)
+{
+  const GridDev& g = c->g;
+  XPIC_CHECK(g.G == 0 && src != dst, "grad_abs_field: a slab with ghost planes, or in place");
+  Timed t(c, "grad_abs_field");
+  const dim3 grid((g.nx + kGaX - 1) / kGaX, (g.ny + kGaY - 1) / kGaY, (g.nzl + kGaZ - 1) / kGaZ);
+  hipLaunchKernelGGL(k_grad_abs, grid, dim3(kBlock), 0, c->stream, g, src, dst);
+  XPIC_HIP(hipGetLastError());
+  return 0;
+}
+
 }  // namespace xpic

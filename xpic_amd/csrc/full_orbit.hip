@@ -160,14 +160,19 @@ int fo_trace(xpic_ctx* ctx, const TraceEntry& E, const xpic_fo_params& P, const 
       if (E.closed) // its text takes no region: the driver's stand-ins for exit_step and removed stay unused
         hipLaunchKernelGGL(cn ? k_fo_trace<true> : k_fo_trace<false>, lane_grid(n), dim3(kBlock), 0, ctx->stream, ctx->g,
           ctx->field[XPIC_E], ctx->field[XPIC_B], P, n, d.s, d.first, d.ns, every, d.nsamp, d.samples, d.it_sum, d.it_max);
-      else
-        hipLaunchKernelGGL(cn ? k_fo_trace_open<true> : k_fo_trace_open<false>, lane_grid(d.m), dim3(kBlock), 0, ctx->stream,
-          ctx->g, ctx->field[XPIC_E], ctx->field[XPIC_B], P, R, n, d.s, d.list, d.m, d.first, d.ns, every, d.nsamp, d.samples,
-          d.it_sum, d.it_max, d.exit_step, d.alive, d.removed);
+      else fo_launch_open(ctx, P, R, n, every, d);
     });
 }
 
 }  // namespace
+
+// one launch of the open trace (trace_call.h): the entry point above and the tracer sets of tracers.hip start it here
+void fo_launch_open(xpic_ctx* ctx, const xpic_fo_params& P, const OpenRegion& R, long n, long every, const TraceDev& d)
+{
+  hipLaunchKernelGGL(P.scheme == XPIC_FO_CN ? k_fo_trace_open<true> : k_fo_trace_open<false>, lane_grid(d.m), dim3(kBlock), 0,
+    ctx->stream, ctx->g, ctx->field[XPIC_E], ctx->field[XPIC_B], P, R, n, d.s, d.list, d.m, d.first, d.ns, every, d.nsamp,
+    d.samples, d.it_sum, d.it_max, d.exit_step, d.alive, d.removed);
+}
 
 }  // namespace xpic
 

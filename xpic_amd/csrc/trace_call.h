@@ -117,4 +117,13 @@ int trace_call(xpic_ctx* ctx, const TraceEntry& E, int launch_steps, const Trace
   return 0;
 }
 
+#ifdef __HIPCC__
+// One launch of an open grid trace over the entries d names (full_orbit.hip, drift_kinetic.hip): what the open entry
+// points start from trace_call's launch, and what a tracer set (tracers.hip) starts on arrays that stay on the device.
+// n: the batch; every: sample_every (>= 1); gradB: the grad |B| vector or null
+void fo_launch_open(xpic_ctx* ctx, const xpic_fo_params& P, const OpenRegion& R, long n, long every, const TraceDev& d);
+void dk_launch_open(xpic_ctx* ctx, const xpic_dk_params& P, const double* gradB, const OpenRegion& R, long n, long every,
+  const TraceDev& d);
+#endif
+
 }  // namespace xpic

@@ -958,7 +958,80 @@ PetscErrorCode VelocityDistribution::diagnose(PetscInt t)
   return 0;
 }
 
+TracedParticles::TracedParticles(const std::string& out_dir, interfaces::Simulation& simulation, int set, int64_t n,
+  int64_t capacity, PetscInt period)
+  : simulation(simulation), out_dir_(out_dir), set_(set), n_(n), capacity_(capacity), period_(period)
+{
+}
+
+// the rows the set has sampled since the last file, [rows][n][6] float64; no rows (the call at `start`): no file
+PetscErrorCode TracedParticles::diagnose(PetscInt t)
+{
+  if (period_ > 0 && t % period_ != 0) return 0;
+  std::vector<double> rows((size_t)capacity_ * n_ * 6);
+  int64_t count = 0;
+  HIPCALL(xpic_tracers_samples(simulation.ctx, set_, rows.data(), nullptr, &count));
+  if (count == 0) return 0;
+  make_dirs(out_dir_);
+  std::ofstream f(out_dir_ + "/" + FieldView::format_time(t), std::ios::binary);
+  if (!f) throw std::runtime_error("Cannot open " + out_dir_ + "/" + FieldView::format_time(t));
+  f.write(reinterpret_cast<const char*>(rows.data()), (std::streamsize)((size_t)count * n_ * 6 * sizeof(double)));
+  return 0;
+}
+
 namespace {
+
+std::unique_ptr<interfaces::Diagnostic> build_traced_particles(interfaces::Simulation& simulation,
+  const Configuration::json_t& info)
+{
+  using interfaces::Builder;
+  static const char* const schemes[XPIC_FO_NSCHEMES] = {"M1A", "M1B", "MLF", "B1A", "B1B", "BLF", "C1A", "C1B", "CLF", "M2A",
+    "M2B", "C2A", "B2B", "EB1A", "EB1B", "EBLF", "EB2B", "CN"}; // enum xpic_fo_scheme
+  const std::string kind = info.at("kind").as_string();
+  if (kind != "full_orbit" && kind != "drift_kinetic") throw std::runtime_error("Unknown TracedParticles kind " + kind);
+  const bool dk = kind == "drift_kinetic";
+  const double qm = info.at("qm").as_double(), step = info.contains("dt") ? info.at("dt").as_double() : dt;
+  xpic_fo_params fo{qm, step, 1e-7, 1e-7, XPIC_FO_B1B, 30}; // the reference's tolerances and iteration limits
+  xpic_dk_params gc{qm, dk ? info.at("mp").as_double() : 1.0, step, 1e-12, 1e-12, 30};
+  if (info.contains("scheme")) {
+    const std::string name = info.at("scheme").as_string();
+    const auto it = std::find_if(std::begin(schemes), std::end(schemes), [&](const char* s) { return name == s; });
+    if (it == std::end(schemes)) throw std::runtime_error("Unknown TracedParticles scheme " + name);
+    fo.scheme = (int32_t)(it - std::begin(schemes));
+  }
+  std::vector<double> state;
+  for (auto&& point : info.at("points").arr) {
+    const auto &ci = point.at("coordinate"), &mi = point.at("momentum");
+    if (ci.at("name").as_string() != "PreciseCoordinate" || mi.at("name").as_string() != "PreciseMomentum")
+      throw std::runtime_error("TracedParticles points take PreciseCoordinate and PreciseMomentum");
+    const Vector3R r = Builder::parse_vector(ci, "value"), p = Builder::parse_vector(mi, "value");
+    for (int i = 0; i < 3; ++i) state.push_back(r[i]);
+    for (int i = 0; i < 3; ++i) state.push_back(p[i]);
+  }
+  const int64_t n = (int64_t)(state.size() / 6);
+  xpic_trace_region region{};
+  const bool open = info.contains("region");
+  if (open) {
+    region.geometry = geometry_kind(info.at("region").at("name").as_string());
+    region.compact = XPIC_COMPACT_AUTO;
+    load_geometry(info.at("region"), region.geometry, region.geom);
+    region.step0 = simulation.start;
+  }
+  const PetscInt period = info.contains("diagnose_period") ? ROUND_STEP(Builder::parse_value(info.at("diagnose_period")), dt)
+                                                           : diagnose_period;
+  const int64_t every = info.contains("sample_every") ? info.at("sample_every").as_int() : 1;
+  if (every < 1) throw std::runtime_error("TracedParticles sample_every should be >= 1");
+  const int64_t capacity = std::max<PetscInt>(period, 1) / every + 1; // the rows of one period, and the one a drain may find early
+  int set = -1;
+  const void* params = dk ? (const void*)&gc : (const void*)&fo;
+  if (check(nullptr, xpic_tracers_create(simulation.ctx, dk ? XPIC_TRACERS_DRIFT_KINETIC : XPIC_TRACERS_FULL_ORBIT, n, params,
+        state.data(), open ? &region : nullptr, XPIC_GRADB_AUTO, every, capacity, &set), "xpic_tracers_create") ||
+      check(nullptr, xpic_tracers_attach(simulation.ctx, set, 1), "xpic_tracers_attach"))
+    throw std::runtime_error("TracedParticles: the tracer set could not be created");
+  const std::string dir = CONFIG().out_dir + "/traced_particles" + (info.contains("name") ? "_" + info.at("name").as_string() : "");
+  LOG("  traced particles diagnostic is added: " << n << " " << kind << " tracers, period " << period << " [dt]");
+  return std::make_unique<TracedParticles>(dir, simulation, set, n, capacity, period);
+}
 
 // FieldViewBuilder::parse_region_start_size / parse_res_dir_suffix / check_region (field_view_builder.cpp:60-147)
 void parse_plane_position(const Configuration::json_t& info, std::string& plane, PetscReal& position)
@@ -1084,8 +1157,9 @@ PetscErrorCode build_diagnostics(interfaces::Simulation& simulation,
       result.emplace_back(std::make_unique<VelocityDistribution>(CONFIG().out_dir + "/" + particles + "/" + projector, simulation,
         simulation.get_named_particles(particles), proj, gkind, geom, vreg));
     }
+    else if (name == "TracedParticles") result.emplace_back(build_traced_particles(simulation, info));
     else throw std::runtime_error("Unknown diagnostic name " + name +
-      " (HIP backends: FieldView, DistributionMoment, VelocityDistribution)");
+      " (HIP backends: FieldView, DistributionMoment, VelocityDistribution, TracedParticles)");
   }
   return 0;
 }

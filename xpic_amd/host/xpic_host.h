@@ -433,6 +433,29 @@ private:
   double geom_[7], vreg_[6];
 };
 
+// EXTENSION (not reference behaviour): "TracedParticles", test particles that ride along with the run as a tracer set
+// (include/xpic_tracers.h).  Keys: "kind" ("full_orbit" | "drift_kinetic"), "scheme" (a full-orbit id, default "B1B"), "qm",
+// "mp" (drift kinetic), "dt" (default: the run's), "points": SetParticles-style entries {"coordinate": {"name":
+// "PreciseCoordinate", "value": xyz}, "momentum": {"name": "PreciseMomentum", "value": xyz}} (drift kinetic: the value is
+// {p_parallel, p_perp, mu_p}), optional "region" (a geometry as RemoveParticles'), "sample_every" (steps, default 1),
+// "diagnose_period" (default: the geometry's), "name" (a suffix of the directory).  A guiding-centre set takes grad |B| of
+// the run's B by XPIC_GRADB_AUTO.  The set is created and attached when the diagnostics are built; every diagnose_period the
+// sample rows held are drained into <out_dir>/traced_particles[_name]/<time> as raw float64 [rows][n][6].  The class
+// exists only where the key is present.
+class TracedParticles final : public interfaces::Diagnostic {
+public:
+  TracedParticles(const std::string& out_dir, interfaces::Simulation& simulation, int set, int64_t n, int64_t capacity,
+    PetscInt period);
+  PetscErrorCode diagnose(PetscInt t) override;
+
+private:
+  interfaces::Simulation& simulation;
+  std::string out_dir_;
+  int set_;
+  int64_t n_, capacity_;
+  PetscInt period_;
+};
+
 // ---- restart files (src/diagnostics/simulation_backup.cpp:30-160): <out_dir>/<t>/{E,B,B0} as PETSc binary Vecs
 // (big endian: int32 VEC_FILE_CLASSID = 1211214, int32 n, n doubles in natural [z][y][x][c] order), particles as
 // <sort_name> = raw big-endian doubles {r, p} per particle and <sort_name>.numparts = one big-endian int32
