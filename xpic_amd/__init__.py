@@ -166,8 +166,8 @@ _lib = None
 
 
 def load_library():
-    """Loads libxpic_hip.so and types every entry point from PROTOTYPES, LOAD_PROTOTYPES and TRACER_PROTOTYPES; raises if it has not been built (no fallback
-    path exists).  The xpic_debug_*_stamps symbols of experiment builds are not in the header and stay untyped."""
+    """Loads libxpic_hip.so and types every entry point from PROTOTYPES, LOAD_PROTOTYPES, TRACER_PROTOTYPES and
+    FIELD_LINE_PROTOTYPES; raises if it has not been built (no fallback path exists).  The xpic_debug_*_stamps symbols of experiment builds are not in the header and stay untyped."""
     global _lib
     if _lib is not None:
         return _lib
@@ -175,7 +175,7 @@ def load_library():
         raise XpicError(f"{LIB_PATH} is missing: run `make` (or __graft_entry__.build()) first; "
                         "xpic_amd has no CPU fallback")
     L = C.CDLL(LIB_PATH)
-    for name, (ret, args) in dict(PROTOTYPES, **LOAD_PROTOTYPES, **TRACER_PROTOTYPES).items():
+    for name, (ret, args) in dict(PROTOTYPES, **LOAD_PROTOTYPES, **TRACER_PROTOTYPES, **FIELD_LINE_PROTOTYPES).items():
         f = getattr(L, name)
         f.restype, f.argtypes = CTYPES[ret], [CTYPES[a] for a in args]
     if L.xpic_version() & VERSION_EXPERIMENT_BIT and os.environ.get("XPIC_ALLOW_EXPERIMENT") != "1":
@@ -329,7 +329,86 @@ class TracerCommands:
         return TracerSet(self, out.value, state.shape[0], int(sample_capacity) if sample_every else 0)
 
 
-class Context(LoadCommands, TracerCommands):
+class FieldLines(collections.namedtuple("FieldLines", "end length volume fmin smin fmax steps code samples directions")):
+    """What Context.field_lines / model_field_lines return.  The raw arrays, [2][n] each with row 0 the lanes that followed
+    +F and row 1 those that followed -F (end: [2][n][3]; samples: [2][n][nsamp][3] or None); a row whose direction was not
+    asked for (directions: 1, 2 or 3) is zeros, with code -1.  The properties combine the directions that were."""
+    __slots__ = ()
+
+    @property
+    def _rows(self):
+        return [d for d in (0, 1) if self.directions & (1 << d)]
+
+    @property
+    def total_length(self):
+        """the length of the whole line through each seed [n]"""
+        return self.length[self._rows].sum(axis=0)
+
+    @property
+    def total_volume(self):
+        """the flux-tube volume, the integral of dl / |F| along the whole line [n]"""
+        return self.volume[self._rows].sum(axis=0)
+
+    @property
+    def mirror_ratio(self):
+        """max |F| / min |F| over the whole line [n]"""
+        return self.fmax[self._rows].max(axis=0) / self.fmin[self._rows].min(axis=0)
+
+    @property
+    def codes(self):
+        """the two lanes' codes per seed [n][2] (LINE_CODES; -1: the direction was not followed)"""
+        return self.code.T.copy()
+
+    @property
+    def ends(self):
+        """the two end points per seed [n][2][3]"""
+        return self.end.transpose(1, 0, 2).copy()
+
+
+class FieldLineCommands:
+    """field lines of a grid vector or of an analytic model (include/xpic_field_lines.h), as methods of Context"""
+
+    def _field_lines(self, call, seeds, which, h, max_steps, region, directions, f_floor, close_tol, sample_every, launch_steps):
+        seeds = np.ascontiguousarray(seeds, dtype=np.float64).reshape(-1, 3)
+        n = seeds.shape[0]
+        if h is None or max_steps is None:
+            raise XpicError("field_lines: h and max_steps are required")
+        d = int(LINE_DIRECTIONS.get(directions, directions))
+        w = int(STAGGERS.get(which, which))
+        P = LineParams(float(h), int(max_steps), float(f_floor), float(close_tol), w, d, int(launch_steps), w)
+        reg = None
+        if region is not None:
+            geom, gp = _geom7(region)
+            reg = C.byref(TraceRegion(geom, COMPACT["never"], (C.c_double * 7)(*gp[:7]), 0))
+        nsamp = int(max_steps) // int(sample_every) if sample_every > 0 else 0
+        end = np.zeros((2, n, 3))
+        length, volume, fmin, smin, fmax = (np.zeros((2, n)) for _ in range(5))
+        steps, code = np.zeros((2, n), dtype=np.int64), np.full((2, n), -1, dtype=np.int32)
+        samples = np.zeros((2, n, nsamp, 3)) if sample_every > 0 else None
+        self._ck(call(n, _dp(seeds), C.byref(P), reg, int(sample_every), _dp(end), _dp(length), _dp(volume), _dp(fmin), _dp(smin),
+                      _dp(fmax), _i64p(steps), _i32p(code), _dp(samples)))
+        return FieldLines(end, length, volume, fmin, smin, fmax, steps, code, samples, d)
+
+    def field_lines(self, seeds, field=B, h=None, max_steps=None, region=None, directions="both", stagger=None, f_floor=0.0,
+                    close_tol=0.0, sample_every=0, launch_steps=0):
+        """The lines of the grid vector `field` through seeds [n][3] -> FieldLines.  h: the arc-length step; max_steps: 1 ..
+        LINES_MAX_STEPS per direction; region: a geometry dict as the open traces take, or None; directions: "+", "-" or
+        "both"; stagger: "B" or "E", how the vector is staggered (default: "E" for the field E, else "B"); a lane stops with
+        code "null" where |F| < f_floor (or is 0), with "closed" within close_tol of its seed (0: never); sample_every k:
+        every k-th point; launch_steps: steps per launch, 0 for the library's default (no result depends on it)."""
+        if stagger is None:
+            stagger = "E" if int(field) == E else "B"
+        return self._field_lines(lambda *a: self.L.xpic_field_lines(self.h, int(field), *a), seeds, stagger, h, max_steps, region,
+                                 directions, f_floor, close_tol, sample_every, launch_steps)
+
+    def model_field_lines(self, model, seeds, h=None, max_steps=None, region=None, directions="both", component="B",
+                          f_floor=0.0, close_tol=0.0, sample_every=0, launch_steps=0):
+        """field_lines on B (or component="E") of an analytic model (what field_model(...) returns); any context"""
+        return self._field_lines(lambda *a: self.L.xpic_model_field_lines(self.h, model, *a), seeds, component, h, max_steps,
+                                 region, directions, f_floor, close_tol, sample_every, launch_steps)
+
+
+class Context(LoadCommands, TracerCommands, FieldLineCommands):
     """One z-slab context = one `interfaces::Simulation` backend instance."""
 
     def __init__(self, scheme, n, d, dt, device=0, rank=0, nranks=1, self_ring=False):

@@ -307,3 +307,24 @@ TRACER_PROTOTYPES = {
 TRACERS_MAX_SETS = 8  # XPIC_TRACERS_MAX_SETS
 TRACER_KINDS = {"full_orbit": 0, "drift_kinetic": 1}  # XPIC_TRACERS_FULL_ORBIT, XPIC_TRACERS_DRIFT_KINETIC
 GRADB_AUTO = -2  # XPIC_GRADB_AUTO
+
+
+# include/xpic_field_lines.h: its struct (that header's, so not one of MIRRORS, which are xpic_hip.h's), its constants and its
+# entry points, typed by load_library() as PROTOTYPES' are; tests/test_abi_field_lines.py holds them to that header
+class LineParams(C.Structure):
+    _fields_ = [("h", C.c_double), ("max_steps", C.c_int64), ("f_floor", C.c_double), ("close_tol", C.c_double),
+                ("stagger", C.c_int32), ("directions", C.c_int32), ("launch_steps", C.c_int32), ("component", C.c_int32)]
+
+
+CTYPES["const xpic_line_params*"] = C.POINTER(LineParams)
+_LINES = ["int64_t", "const double*", "const xpic_line_params*", "const xpic_trace_region*", "int64_t", "double*", "double*",
+          "double*", "double*", "double*", "double*", "int64_t*", "int32_t*", "double*"]
+FIELD_LINE_PROTOTYPES = {
+    "xpic_field_lines": ("int", ["xpic_ctx*", "int"] + _LINES),
+    "xpic_model_field_lines": ("int", ["xpic_ctx*", "const xpic_field_model*"] + _LINES),
+}
+LINES_LAUNCH_STEPS = 256    # XPIC_LINES_LAUNCH_STEPS
+LINES_MAX_STEPS = 1 << 24   # XPIC_LINES_MAX_STEPS
+STAGGERS = {"B": 0, "E": 1}  # XPIC_STAGGER_B, XPIC_STAGGER_E
+LINE_DIRECTIONS = {"+": 1, "-": 2, "both": 3}
+LINE_CODES = {"maxsteps": 0, "left": 1, "null": 2, "closed": 3}  # XPIC_LINE_*

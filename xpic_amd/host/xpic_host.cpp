@@ -979,7 +979,74 @@ PetscErrorCode TracedParticles::diagnose(PetscInt t)
   return 0;
 }
 
+FieldLines::FieldLines(const std::string& out_dir, interfaces::Simulation& simulation, int field, std::vector<double> seeds,
+  const xpic_line_params& params, bool open, const xpic_trace_region& region, PetscInt period)
+  : simulation(simulation), out_dir_(out_dir), field_(field), seeds_(std::move(seeds)), params_(params), open_(open),
+    region_(region), period_(period)
+{
+}
+
+// the lines through the points on the field as it stands: [n][2][10] float64 (xpic_host.h)
+PetscErrorCode FieldLines::diagnose(PetscInt t)
+{
+  if (period_ > 0 && t % period_ != 0) return 0;
+  const size_t n = seeds_.size() / 3;
+  std::vector<double> end(6 * n), acc[5];
+  for (auto& a : acc) a.resize(2 * n);
+  std::vector<int64_t> steps(2 * n);
+  std::vector<int32_t> code(2 * n);
+  HIPCALL(xpic_field_lines(simulation.ctx, field_, (int64_t)n, seeds_.data(), &params_, open_ ? &region_ : nullptr, 0, end.data(),
+    acc[0].data(), acc[1].data(), acc[2].data(), acc[3].data(), acc[4].data(), steps.data(), code.data(), nullptr));
+  std::vector<double> rows(20 * n);
+  for (size_t q = 0; q < n; ++q)
+    for (size_t d = 0; d < 2; ++d) {
+      double* row = &rows[(2 * q + d) * 10];
+      const size_t slot = d * n + q;
+      for (int a = 0; a < 3; ++a) row[a] = end[3 * slot + a];
+      for (int k = 0; k < 5; ++k) row[3 + k] = acc[k][slot];
+      row[8] = (double)steps[slot];
+      row[9] = (double)code[slot];
+    }
+  make_dirs(out_dir_);
+  std::ofstream f(out_dir_ + "/" + FieldView::format_time(t), std::ios::binary);
+  if (!f) throw std::runtime_error("Cannot open " + out_dir_ + "/" + FieldView::format_time(t));
+  f.write(reinterpret_cast<const char*>(rows.data()), (std::streamsize)(rows.size() * sizeof(double)));
+  return 0;
+}
+
 namespace {
+
+std::unique_ptr<interfaces::Diagnostic> build_field_lines(interfaces::Simulation& simulation, const Configuration::json_t& info)
+{
+  using interfaces::Builder;
+  const std::string field = info.at("field").as_string();
+  const int id = simulation.get_named_vector(field);
+  std::vector<double> seeds;
+  for (auto&& point : info.at("points").arr) {
+    const auto& ci = point.at("coordinate");
+    if (ci.at("name").as_string() != "PreciseCoordinate") throw std::runtime_error("FieldLines points take PreciseCoordinate");
+    const Vector3R r = Builder::parse_vector(ci, "value");
+    for (int i = 0; i < 3; ++i) seeds.push_back(r[i]);
+  }
+  xpic_line_params params{};
+  params.h = info.at("h").as_double();
+  params.max_steps = info.at("max_steps").as_int();
+  params.f_floor = info.contains("f_floor") ? info.at("f_floor").as_double() : 0.0;
+  params.stagger = field == "E" ? XPIC_STAGGER_E : XPIC_STAGGER_B;
+  params.directions = 3;
+  xpic_trace_region region{};
+  const bool open = info.contains("region");
+  if (open) {
+    region.geometry = geometry_kind(info.at("region").at("name").as_string());
+    region.compact = XPIC_COMPACT_NEVER;
+    load_geometry(info.at("region"), region.geometry, region.geom);
+  }
+  const PetscInt period = info.contains("diagnose_period") ? ROUND_STEP(Builder::parse_value(info.at("diagnose_period")), dt)
+                                                           : diagnose_period;
+  const std::string dir = CONFIG().out_dir + "/field_lines" + (info.contains("name") ? "_" + info.at("name").as_string() : "");
+  LOG("  field lines diagnostic is added for " << field << ": " << seeds.size() / 3 << " points, period " << period << " [dt]");
+  return std::make_unique<FieldLines>(dir, simulation, id, std::move(seeds), params, open, region, period);
+}
 
 std::unique_ptr<interfaces::Diagnostic> build_traced_particles(interfaces::Simulation& simulation,
   const Configuration::json_t& info)
@@ -1158,8 +1225,9 @@ PetscErrorCode build_diagnostics(interfaces::Simulation& simulation,
         simulation.get_named_particles(particles), proj, gkind, geom, vreg));
     }
     else if (name == "TracedParticles") result.emplace_back(build_traced_particles(simulation, info));
+    else if (name == "FieldLines") result.emplace_back(build_field_lines(simulation, info));
     else throw std::runtime_error("Unknown diagnostic name " + name +
-      " (HIP backends: FieldView, DistributionMoment, VelocityDistribution, TracedParticles)");
+      " (HIP backends: FieldView, DistributionMoment, VelocityDistribution, TracedParticles, FieldLines)");
   }
   return 0;
 }

@@ -456,6 +456,30 @@ private:
   PetscInt period_;
 };
 
+// EXTENSION (not reference behaviour): "FieldLines", the lines of a field of the run through given points, traced on the
+// device (include/xpic_field_lines.h).  Keys: "field" ("E" | "B" | "B0"; E takes the electric stagger), "points": entries
+// {"coordinate": {"name": "PreciseCoordinate", "value": xyz}} as "TracedParticles" takes them (a "momentum" is not read),
+// "h", "max_steps", optional "region" (a geometry as RemoveParticles'), "f_floor" (default 0), "diagnose_period" (default:
+// the geometry's), "name" (a suffix of the directory).  Every diagnose_period the lines are traced both ways on the field
+// as it stands and <out_dir>/field_lines[_name]/<time> is written as raw float64 [n][2][10]: end x, end y, end z, length,
+// volume, fmin, smin, fmax, steps, code.  The class exists only where the key is present.
+class FieldLines final : public interfaces::Diagnostic {
+public:
+  FieldLines(const std::string& out_dir, interfaces::Simulation& simulation, int field, std::vector<double> seeds,
+    const xpic_line_params& params, bool open, const xpic_trace_region& region, PetscInt period);
+  PetscErrorCode diagnose(PetscInt t) override;
+
+private:
+  interfaces::Simulation& simulation;
+  std::string out_dir_;
+  int field_;
+  std::vector<double> seeds_;
+  xpic_line_params params_;
+  bool open_;
+  xpic_trace_region region_;
+  PetscInt period_;
+};
+
 // ---- restart files (src/diagnostics/simulation_backup.cpp:30-160): <out_dir>/<t>/{E,B,B0} as PETSc binary Vecs
 // (big endian: int32 VEC_FILE_CLASSID = 1211214, int32 n, n doubles in natural [z][y][x][c] order), particles as
 // <sort_name> = raw big-endian doubles {r, p} per particle and <sort_name>.numparts = one big-endian int32
