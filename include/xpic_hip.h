@@ -956,6 +956,8 @@ int xpic_probe_copy_bandwidth(xpic_ctx* ctx, int64_t bytes, int reps, double* by
 #include "xpic_set_particles.h"
 /* ---- tracer sets that live on the device and ride along with the step, and grad |F| of a grid vector */
 #include "xpic_tracers.h"
+/* ---- the moments of a tracer set on the grid, once or accumulated into maps on the device */
+#include "xpic_tracer_moments.h"
 /* ---- field lines of a grid vector or of an analytic model, traced on the device */
 #include "xpic_field_lines.h"
 #endif

@@ -45,7 +45,8 @@
  * refused; a set id that was never given out or has been destroyed is an error with a message in every call; xpic_destroy
  * frees the sets that are left.  Ids are not reused within a context.
  * Not offered as sets: the paired, triplet, model, timed and collisional traces; contexts of several z-slabs; tracers that
- * deposit charge or current. */
+ * deposit charge or current which the run reads.  The moments of a set, which nothing in the run reads, and their
+ * accumulation into maps while the set advances are xpic_tracer_moments.h's. */
 #ifndef XPIC_TRACERS_H
 #define XPIC_TRACERS_H
 #ifdef __cplusplus

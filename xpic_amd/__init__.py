@@ -166,8 +166,8 @@ _lib = None
 
 
 def load_library():
-    """Loads libxpic_hip.so and types every entry point from PROTOTYPES, LOAD_PROTOTYPES, TRACER_PROTOTYPES and
-    FIELD_LINE_PROTOTYPES; raises if it has not been built (no fallback path exists).  The xpic_debug_*_stamps symbols of experiment builds are not in the header and stay untyped."""
+    """Loads libxpic_hip.so and types every entry point from PROTOTYPES, LOAD_PROTOTYPES, TRACER_PROTOTYPES,
+    TRACER_MOMENT_PROTOTYPES and FIELD_LINE_PROTOTYPES; raises if it has not been built (no fallback path exists).  The xpic_debug_*_stamps symbols of experiment builds are not in the header and stay untyped."""
     global _lib
     if _lib is not None:
         return _lib
@@ -175,7 +175,8 @@ def load_library():
         raise XpicError(f"{LIB_PATH} is missing: run `make` (or __graft_entry__.build()) first; "
                         "xpic_amd has no CPU fallback")
     L = C.CDLL(LIB_PATH)
-    for name, (ret, args) in dict(PROTOTYPES, **LOAD_PROTOTYPES, **TRACER_PROTOTYPES, **FIELD_LINE_PROTOTYPES).items():
+    for name, (ret, args) in dict(PROTOTYPES, **LOAD_PROTOTYPES, **TRACER_PROTOTYPES, **TRACER_MOMENT_PROTOTYPES,
+                                   **FIELD_LINE_PROTOTYPES).items():
         f = getattr(L, name)
         f.restype, f.argtypes = CTYPES[ret], [CTYPES[a] for a in args]
     if L.xpic_version() & VERSION_EXPERIMENT_BIT and os.environ.get("XPIC_ALLOW_EXPERIMENT") != "1":
@@ -255,6 +256,33 @@ class TracerState(collections.namedtuple(
     particles removed, particles alive, sample rows held, sample rows dropped)"""
 
 
+def _region6(region):
+    """(start xyz, size xyz) in global cells, as six numbers or two triples, as the header's `const int region6[6]`"""
+    if region is None:
+        return None
+    return (C.c_int * 6)(*[int(v) for v in np.asarray(region, dtype=np.int64).reshape(6)])
+
+
+class TracerMap:
+    """A map of a TracerSet (include/xpic_tracer_moments.h): made by TracerSet.map, accumulates on the device until close()"""
+
+    def __init__(self, tracers, map_id, dof):
+        self.set, self.id, self.dof = tracers, map_id, dof
+
+    def get(self, reset=False):
+        """-> (array [nz][ny][nx][dof], deposits made, particle-deposits counted, the set's step count); array / deposits
+        is the time average.  reset: the map and its two counters are zeroed after the copy"""
+        ctx = self.set.ctx
+        out, info = np.zeros((ctx.nzl, ctx.n[1], ctx.n[0], self.dof)), np.zeros(3, dtype=np.int64)
+        ctx._ck(ctx.L.xpic_tracers_map_get(ctx.h, self.set.id, self.id, _dp(out), _i64p(info), int(bool(reset))))
+        return (out,) + tuple(int(v) for v in info)
+
+    def close(self):
+        if self.id is not None:
+            map_id, self.id = self.id, None
+            self.set.ctx._ck(self.set.ctx.L.xpic_tracers_map_destroy(self.set.ctx.h, self.set.id, map_id))
+
+
 class TracerSet:
     """A tracer set of a Context (include/xpic_tracers.h): made by Context.tracers, lives on the device until close()"""
 
@@ -287,6 +315,24 @@ class TracerSet:
         samples, alive, count = np.zeros((cap, self.n, 6)), np.zeros(cap, dtype=np.int64), C.c_int64()
         self.ctx._ck(self.ctx.L.xpic_tracers_samples(self.ctx.h, self.id, _dp(samples), _i64p(alive), C.byref(count)))
         return samples[:count.value], alive[:count.value]
+
+    def moment(self, name, q, m, weight=1.0, region=None):
+        """the moment `name` (a name of Context.moment) of the set's live particles as they stand -> (array
+        [nz][ny][nx][dof], particles counted).  q, m: the charge and mass of a tracer; weight: what n / Np is for a sort;
+        region: None (the whole box) or (start xyz, size xyz) in cells.  A particle counts iff floor(r / d) lies in it."""
+        ctx = self.ctx
+        out, counted = np.zeros((ctx.nzl, ctx.n[1], ctx.n[0], MOMENT_DOF[name])), C.c_int64()
+        ctx._ck(ctx.L.xpic_tracers_moment(ctx.h, self.id, MOMENTS[name], float(q), float(m), float(weight), _region6(region),
+                                          _dp(out), C.byref(counted)))
+        return out, counted.value
+
+    def map(self, name, q, m, weight=1.0, region=None, every=1):
+        """A map -> TracerMap: whenever the set's step count reaches a multiple of `every`, in an advance or a ride, the
+        moment is added into an accumulator on the device"""
+        ctx, out = self.ctx, C.c_int()
+        ctx._ck(ctx.L.xpic_tracers_map_create(ctx.h, self.id, MOMENTS[name], float(q), float(m), float(weight),
+                                              _region6(region), int(every), C.byref(out)))
+        return TracerMap(self, out.value, MOMENT_DOF[name])
 
     def close(self):
         if self.id is not None:

@@ -304,6 +304,18 @@ TRACER_PROTOTYPES = {
     "xpic_tracers_samples": ("int", ["xpic_ctx*", "int", "double*", "int64_t*", "int64_t*"]),
     "xpic_tracers_destroy": ("int", ["xpic_ctx*", "int"]),
 }
+# the entry points of include/xpic_tracer_moments.h, typed by load_library() as PROTOTYPES' are;
+# tests/test_abi_tracer_moments.py holds them to that header
+TRACER_MOMENT_PROTOTYPES = {
+    "xpic_tracers_moment": ("int", ["xpic_ctx*", "int", "int", "double", "double", "double", "const int*", "double*",
+                                    "int64_t*"]),
+    "xpic_tracers_map_create": ("int", ["xpic_ctx*", "int", "int", "double", "double", "double", "const int*", "int64_t",
+                                        "int*"]),
+    "xpic_tracers_map_get": ("int", ["xpic_ctx*", "int", "int", "double*", "int64_t*", "int"]),
+    "xpic_tracers_map_destroy": ("int", ["xpic_ctx*", "int", "int"]),
+}
+TRACERS_MAX_MAPS = 4  # XPIC_TRACERS_MAX_MAPS
+DEBUG_TRACER_MOMENT_LDS = 3  # XPIC_DEBUG_TRACER_MOMENT_LDS (xpic_debug_set)
 TRACERS_MAX_SETS = 8  # XPIC_TRACERS_MAX_SETS
 TRACER_KINDS = {"full_orbit": 0, "drift_kinetic": 1}  # XPIC_TRACERS_FULL_ORBIT, XPIC_TRACERS_DRIFT_KINETIC
 GRADB_AUTO = -2  # XPIC_GRADB_AUTO

@@ -793,6 +793,10 @@ int xpic_debug_set(xpic_ctx* ctx, int what, int64_t value)
     case XPIC_DEBUG_SURROGATE_SCALE:
       ctx->debug_surrogate_scale = (double)value / 1000.0;
       return 0;
+    case XPIC_DEBUG_TRACER_MOMENT_LDS:
+      XPIC_CHECK(value >= 0 && value <= kTracerMomentLds, "tracer moment LDS budget: 0 .. 9216 doubles");
+      ctx->tracer_moment_lds = (int)value;
+      return 0;
     default:
       XPIC_CHECK(false, "xpic_debug_set: unknown knob");
   }

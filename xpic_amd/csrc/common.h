@@ -196,6 +196,9 @@ struct ProfileEntry {
 };
 
 struct TracerSets; // tracers.hip: the tracer sets of a context
+// tracer_moments.hip: doubles of a workgroup's private copy of a moment's region: 72 KiB of the CU's 160 KiB of LDS, so that
+// two workgroups and their static arrays fit on a CU
+constexpr int kTracerMomentLds = 9216;
 
 }  // namespace xpic
 
@@ -257,6 +260,7 @@ struct xpic_ctx {
   int64_t cmd_rank_n = 0;
   int64_t collide_large_cells = 0; // collide.hip: local cells of the last call that took the second path
   double* bg_profile[XPIC_TRACE_BG_MAX] = {}; // background.hip: the background profiles, [5][ncell] each; null: an empty slot
+  int tracer_moment_lds = xpic::kTracerMomentLds; // tracer_moments.hip: the largest region x dof a workgroup keeps in LDS (xpic_debug_set)
   xpic::TracerSets* tracers = nullptr; // tracers.hip: made by the first xpic_tracers_create; null: xpic_step has nothing to carry
   double rtol = 1e-7, atol = 1e-7;
   int maxit = 100;

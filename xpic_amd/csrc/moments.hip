@@ -6,6 +6,7 @@
 
 #include "common.h"
 #include "device_common.h"
+#include "moment_deposit.h"
 
 namespace xpic {
 
@@ -23,88 +24,11 @@ constexpr int kMomWaves = 8;
 constexpr int kMomThreads = 64 * kMomWaves;
 constexpr int kMomTile = (kMomCX + 2) * (kMomCY + 2) * (kMomCZ + 2); // cells of the largest tile
 
-// global cells [s, e) per axis; full: the region spans the axis, its deposits wrap periodically (l_bound = bound, :104)
-struct MomRegion {
-  int s[3], e[3], full[3];
-  int bx[2], by[2], bz[2]; // local storage cells of the region on this slab (z relative to the first owned plane)
-  int nbx, nby;            // blocks along x, y
-};
-
-struct MomOut {
-  double* c[6];
-};
-
 struct MomParticles { // the records and cell_start of a sort: what the deposit reads of SortDev
   const double* r[3];
   const double* v[3];
   const int* cs;
 };
-
-template <int K> struct MomDof;
-template <> struct MomDof<XPIC_MOMENT_DENSITY> { static constexpr int v = 1; };
-template <> struct MomDof<XPIC_MOMENT_CURRENT> { static constexpr int v = 3; };
-template <> struct MomDof<XPIC_MOMENT_MOMENTUM_FLUX> { static constexpr int v = 6; };
-template <> struct MomDof<XPIC_MOMENT_MOMENTUM_FLUX_DIAG> { static constexpr int v = 3; };
-template <> struct MomDof<XPIC_MOMENT_MOMENTUM_FLUX_CYL> { static constexpr int v = 6; };
-template <> struct MomDof<XPIC_MOMENT_MOMENTUM_FLUX_DIAG_CYL> { static constexpr int v = 3; };
-
-// _get_v_cyl (:260-277): about the axis (geom_x / 2, geom_y / 2); a point ON the axis keeps its Cartesian components
-__device__ inline void v_cyl(double x, double y, double Lx, double Ly, const double* v, double* o)
-{
-  const double px = x - 0.5 * Lx, py = y - 0.5 * Ly;
-  const double r = hypot(px, py);
-  if (isinf(1.0 / r)) {
-    o[0] = v[0]; o[1] = v[1]; o[2] = v[2];
-    return;
-  }
-  o[0] = (+px * v[0] + py * v[1]) / r;
-  o[1] = (-py * v[0] + px * v[1]) / r;
-  o[2] = v[2];
-}
-
-// get_density ... get_momentum_flux_diag_cyl (:212-298), components in the reference's order
-template <int K>
-__device__ inline void moment_of(const GridDev& g, double q, double m, double x, double y, const double* v, double* o)
-{
-  if (K == XPIC_MOMENT_DENSITY) o[0] = 1.0;
-  if (K == XPIC_MOMENT_CURRENT) { o[0] = q * v[0]; o[1] = q * v[1]; o[2] = q * v[2]; }
-  if (K == XPIC_MOMENT_MOMENTUM_FLUX) {
-    o[0] = m * v[0] * v[0]; o[1] = m * v[0] * v[1]; o[2] = m * v[0] * v[2];
-    o[3] = m * v[1] * v[1]; o[4] = m * v[1] * v[2]; o[5] = m * v[2] * v[2];
-  }
-  if (K == XPIC_MOMENT_MOMENTUM_FLUX_DIAG) { o[0] = m * v[0] * v[0]; o[1] = m * v[1] * v[1]; o[2] = m * v[2] * v[2]; }
-  if (K == XPIC_MOMENT_MOMENTUM_FLUX_CYL || K == XPIC_MOMENT_MOMENTUM_FLUX_DIAG_CYL) {
-    double c[3];
-    v_cyl(x, y, g.Lx, g.Ly, v, c);
-    if (K == XPIC_MOMENT_MOMENTUM_FLUX_CYL) {
-      o[0] = m * c[0] * c[0]; o[1] = m * c[0] * c[1]; o[2] = m * c[0] * c[2];
-      o[3] = m * c[1] * c[1]; o[4] = m * c[1] * c[2]; o[5] = m * c[2] * c[2];
-    } else {
-      o[0] = m * c[0] * c[0]; o[1] = m * c[1] * c[1]; o[2] = m * c[2] * c[2];
-    }
-  }
-}
-
-// A deposit at the (unwrapped) global cell (x, y, zg) -> stored node of this slab, or -1 when the region rule drops it:
-// wrapped on the axes the region spans in full, then kept iff it lies in the region (DMLocalToGlobal of a
-// DM_BOUNDARY_GHOSTED axis discards the ghosts).  Deposits into the planes just outside the slab land in its ghost planes.
-__device__ inline long mom_target(const GridDev& g, const MomRegion& R, int x, int y, int zg)
-{
-  int p[3] = {x, y, zg};
-  const int n[3] = {g.nx, g.ny, g.nzg};
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    if (R.full[a]) p[a] = p[a] < 0 ? p[a] + n[a] : (p[a] >= n[a] ? p[a] - n[a] : p[a]);
-    if (p[a] < R.s[a] || p[a] >= R.e[a]) return -1;
-  }
-  int zl = p[2] - g.z0;
-  if (g.G > 0) { // a deposit that wrapped across the periodic z boundary belongs to the ghost plane on the other side
-    if (zl < -1) zl += g.nzg;
-    else if (zl > g.nzl) zl -= g.nzg;
-  }
-  if (zl < -g.G || zl >= g.nzl + g.G) return -1; // (a record far from its storage cell: nothing the reference could add)
-  return g.node(p[0], p[1], g.wz(zl));
-}
 
 // STRAY = false: the deposit into the tile and the tile's flush; a record whose 2 x 2 x 2 cells leave the tile (it sits away
 // from its storage cell: positions moved, cells not yet re-binned -- the phase entry points allow that state) only raises
@@ -142,19 +66,9 @@ __global__ void __launch_bounds__(kMomThreads) k_moment(GridDev g, MomParticles 
       if (p >= ge) continue;
       const double r[3] = {s.r[0][p], s.r[1][p], s.r[2][p]};
       const double v[3] = {s.v[0][p], s.v[1][p], s.v[2][p]};
-      // DistributionMoment::Shape::setup (:137-151): start = round(r / d - 1), spline_of_1st_order about the cell centres
-      const double pr[3] = {r[0] / g.dx, r[1] / g.dy, r[2] / g.dz};
       int st[3];
       double w[3][2];
-#pragma unroll
-      for (int a = 0; a < 3; ++a) {
-        st[a] = (int)round(pr[a] - 1.0);
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-          const double d = fabs(pr[a] - ((double)(st[a] + t) + 0.5));
-          w[a][t] = d <= 1.0 ? 1.0 - d : 0.0;
-        }
-      }
+      mom_shape(g, r, st, w); // DistributionMoment::Shape::setup (:137-151)
       const int tx = st[0] - (x0 - 1), ty = st[1] - (y0 - 1), tz = st[2] - g.z0 - (z0 - 1);
       const bool in_tile = tx >= 0 && tx + 1 < TX && ty >= 0 && ty + 1 < TY && tz >= 0 && tz + 1 < TZ;
       if (in_tile == STRAY) {
@@ -167,8 +81,7 @@ __global__ void __launch_bounds__(kMomThreads) k_moment(GridDev g, MomParticles 
       for (int k = 0; k < 8; ++k) {
         const int kk = (k + u) & 7;
         const int ix = kk & 1, iy = (kk >> 1) & 1, iz = kk >> 2;
-        const double cache = ((ix ? w[0][1] : w[0][0]) * (iy ? w[1][1] : w[1][0])) * (iz ? w[2][1] : w[2][0]);
-        const double si = cache * n_Np; // (:196)
+        const double si = mom_weight(w, kk) * n_Np; // (:196)
         if (si == 0.0) continue;
         if (!STRAY) {
           const int t = ((tz + iz) * TY + (ty + iy)) * TX + (tx + ix);
@@ -309,14 +222,8 @@ int moment_dof(int kind)
 int moment_region(xpic_ctx* c, Sort& s, int kind, const int* region6, double* const* comp)
 {
   const GridDev& g = c->g;
-  const int n[3] = {g.nx, g.ny, g.nzg};
   MomRegion R{};
-  for (int a = 0; a < 3; ++a) {
-    R.s[a] = region6 ? region6[a] : 0;
-    R.e[a] = region6 ? region6[a] + region6[3 + a] : n[a];
-    XPIC_CHECK(R.s[a] >= 0 && R.e[a] > R.s[a] && R.e[a] <= n[a], "moment region: start >= 0, size > 0, start + size <= n");
-    R.full[a] = R.s[a] == 0 && R.e[a] == n[a];
-  }
+  XPIC_CHECK(mom_region_of(g, region6, &R), "moment region: start >= 0, size > 0, start + size <= n");
   R.bx[0] = R.s[0]; R.bx[1] = R.e[0];
   R.by[0] = R.s[1]; R.by[1] = R.e[1];
   R.bz[0] = std::max(R.s[2], g.z0) - g.z0;

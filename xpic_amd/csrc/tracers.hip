@@ -3,7 +3,8 @@
 // sets, api.hip).  There is no kernel here.  A set is advanced by the open traces' own launches (fo_launch_open,
 // dk_launch_open: trace_call.h) through the launch loop the open traces run (trace_launches, LiveList: batch.h) and
 // compacted by trace_open.hip; what this file adds is the ownership of the arrays batch_trace stages for one call, the
-// bookkeeping that turns a set's life into one long call, and the sample buffer of fixed capacity.
+// bookkeeping that turns a set's life into one long call, and the sample buffer of fixed capacity.  The set itself is
+// tracer_set.h's, which tracer_moments.hip shares: the maps of a set take their deposits between the launches of advance.
 //
 // One long call: the kernels count steps from `first` (steps of the call before the launch), write sample row
 // step / sample_every - 1 while it is < nsamp, and set exit_step = R.step0 + first + the steps completed.  A set that has
@@ -20,43 +21,11 @@
 #include "common.h"
 #include "trace_call.h"
 #include "trace_open.h"
+#include "tracer_set.h"
 
 namespace xpic {
 
-struct TracerSet {
-  int id = 0, kind = 0;
-  int64_t n = 0;
-  xpic_fo_params fo{};
-  xpic_dk_params dk{};
-  OpenRegion R{};        // the region as given; without one: a box every finite position passes
-  bool tracked = false;  // a region was given: the removed count is read back after every launch (the live list's input)
-  int policy = XPIC_COMPACT_NEVER;
-  int gradB = -1;        // drift kinetic: a field id, -1 or XPIC_GRADB_AUTO
-  int64_t every = 0, cap = 0; // sample_every (0: none) and the rows the buffer holds
-  int64_t done = 0;      // steps since creation
-  int64_t base = 0;      // sample rows that were due before the buffer's row 0
-  int64_t dropped = 0;   // rows lost to a full buffer before `base`
-  bool attached = false;
-  DevScratch<double> s, sm;      // the state [6][n], the sample rows [cap][6][n]
-  DevScratch<int64_t> ex, tot, al, rm; // exit_step [n], iteration sums [n], alive [cap], the removed count
-  DevScratch<int> mx;            // iteration maxima [n]
-  LiveList L;
-
-  bool counters() const { return kind == XPIC_TRACERS_DRIFT_KINETIC || fo.scheme == XPIC_FO_CN; }
-  int64_t due() const { return every > 0 ? done / every : 0; }           // rows due since creation
-  int64_t held() const { return std::min(due() - base, cap); }          // rows in the buffer
-  int64_t lost() const { return dropped + (due() - base - held()); }    // rows dropped since creation
-};
-
-struct TracerSets {
-  std::vector<std::unique_ptr<TracerSet>> sets; // in creation order
-  int next_id = 0;
-  double* gradB = nullptr; // XPIC_GRADB_AUTO: grad |B|, allocated by the first advance that needs it; no field id names it
-};
-
-namespace {
-
-int find_set(xpic_ctx* ctx, const std::string& who, int id, TracerSet** out)
+int tracers_find(xpic_ctx* ctx, const std::string& who, int id, TracerSet** out)
 {
   XPIC_CHECK(ctx != nullptr, "null context");
   if (ctx->tracers)
@@ -65,6 +34,10 @@ int find_set(xpic_ctx* ctx, const std::string& who, int id, TracerSet** out)
   XPIC_CHECK(false, who + ": set " + std::to_string(id) + " does not exist (never created, or destroyed)");
   return 0;
 }
+
+namespace {
+
+int find_set(xpic_ctx* ctx, const std::string& who, int id, TracerSet** out) { return tracers_find(ctx, who, id, out); }
 
 bool wants_gradient(const TracerSet& T)
 {
@@ -81,7 +54,7 @@ int auto_gradient(xpic_ctx* ctx)
 
 // `steps` >= 0 steps of one set on the context's fields as they stand.  have_gradient: the caller has run auto_gradient on
 // this B already (a ride computes it once for all its sets)
-int advance(xpic_ctx* ctx, TracerSet& T, int64_t steps, bool have_gradient = false)
+int advance_plain(xpic_ctx* ctx, TracerSet& T, int64_t steps, bool have_gradient)
 {
   if (T.n > 0 && steps > 0) {
     const bool dk = T.kind == XPIC_TRACERS_DRIFT_KINETIC;
@@ -108,6 +81,24 @@ int advance(xpic_ctx* ctx, TracerSet& T, int64_t steps, bool have_gradient = fal
         T.tracked, d, T.L, [&](const TraceDev& l) { fo_launch_open(ctx, T.fo, R, n, every, l); }));
   }
   T.done += steps;
+  return 0;
+}
+
+// advance_plain for a set without maps.  With maps the steps are split where one of them is due (the set's step count
+// reaches a multiple of its `every`) and the deposit runs between the trace launches: by composition ((2) in
+// include/xpic_tracers.h) the set's own bits are those of the unsplit advance.  B does not change during the call, so
+// the pieces share one gradient.
+int advance(xpic_ctx* ctx, TracerSet& T, int64_t steps, bool have_gradient = false)
+{
+  if (T.maps.empty()) return advance_plain(ctx, T, steps, have_gradient);
+  while (steps > 0) {
+    int64_t piece = steps;
+    for (auto& m : T.maps) piece = std::min(piece, m->every - T.done % m->every);
+    XPIC_CALL(advance_plain(ctx, T, piece, have_gradient));
+    have_gradient = have_gradient || wants_gradient(T);
+    XPIC_CALL(tracer_maps_deposit(ctx, T));
+    steps -= piece;
+  }
   return 0;
 }
 

@@ -959,8 +959,9 @@ PetscErrorCode VelocityDistribution::diagnose(PetscInt t)
 }
 
 TracedParticles::TracedParticles(const std::string& out_dir, interfaces::Simulation& simulation, int set, int64_t n,
-  int64_t capacity, PetscInt period)
-  : simulation(simulation), out_dir_(out_dir), set_(set), n_(n), capacity_(capacity), period_(period)
+  int64_t capacity, PetscInt period, std::vector<Moment> moments)
+  : simulation(simulation), out_dir_(out_dir), set_(set), n_(n), capacity_(capacity), period_(period),
+    moments_(std::move(moments))
 {
 }
 
@@ -971,11 +972,31 @@ PetscErrorCode TracedParticles::diagnose(PetscInt t)
   std::vector<double> rows((size_t)capacity_ * n_ * 6);
   int64_t count = 0;
   HIPCALL(xpic_tracers_samples(simulation.ctx, set_, rows.data(), nullptr, &count));
-  if (count == 0) return 0;
-  make_dirs(out_dir_);
-  std::ofstream f(out_dir_ + "/" + FieldView::format_time(t), std::ios::binary);
-  if (!f) throw std::runtime_error("Cannot open " + out_dir_ + "/" + FieldView::format_time(t));
-  f.write(reinterpret_cast<const char*>(rows.data()), (std::streamsize)((size_t)count * n_ * 6 * sizeof(double)));
+  if (count > 0) {
+    make_dirs(out_dir_);
+    std::ofstream f(out_dir_ + "/" + FieldView::format_time(t), std::ios::binary);
+    if (!f) throw std::runtime_error("Cannot open " + out_dir_ + "/" + FieldView::format_time(t));
+    f.write(reinterpret_cast<const char*>(rows.data()), (std::streamsize)((size_t)count * n_ * 6 * sizeof(double)));
+  }
+  // the maps: the time average since the last file, the region's values [z][y][x][c] as float32; then the map starts anew
+  for (const Moment& m : moments_) {
+    const PetscInt dof = m.region.dof;
+    std::vector<double> data((size_t)geom_nx * geom_ny * geom_nz * dof);
+    int64_t info[3] = {0, 0, 0};
+    HIPCALL(xpic_tracers_map_get(simulation.ctx, set_, m.map, data.data(), info, 1));
+    if (info[0] == 0) continue;
+    std::vector<float> out;
+    out.reserve((size_t)m.region.size[0] * m.region.size[1] * m.region.size[2] * dof);
+    for (PetscInt z = m.region.start[2]; z < m.region.start[2] + m.region.size[2]; ++z)
+      for (PetscInt y = m.region.start[1]; y < m.region.start[1] + m.region.size[1]; ++y)
+        for (PetscInt x = m.region.start[0]; x < m.region.start[0] + m.region.size[0]; ++x)
+          for (PetscInt c = 0; c < dof; ++c)
+            out.push_back((float)(data[(((size_t)z * geom_ny + y) * geom_nx + x) * dof + c] / (double)info[0]));
+    make_dirs(m.dir);
+    std::ofstream f(m.dir + "/" + FieldView::format_time(t), std::ios::binary);
+    if (!f) throw std::runtime_error("Cannot open " + m.dir + "/" + FieldView::format_time(t));
+    f.write(reinterpret_cast<const char*>(out.data()), (std::streamsize)(out.size() * sizeof(float)));
+  }
   return 0;
 }
 
@@ -1048,6 +1069,10 @@ std::unique_ptr<interfaces::Diagnostic> build_field_lines(interfaces::Simulation
   return std::make_unique<FieldLines>(dir, simulation, id, std::move(seeds), params, open, region, period);
 }
 
+void parse_region(const Configuration::json_t& info, FieldView::Region& region, std::string& suffix, const std::string& name);
+void check_region(const FieldView::Region& region, const std::string& name);
+int moment_kind(const std::string& moment, int* dof);
+
 std::unique_ptr<interfaces::Diagnostic> build_traced_particles(interfaces::Simulation& simulation,
   const Configuration::json_t& info)
 {
@@ -1096,8 +1121,44 @@ std::unique_ptr<interfaces::Diagnostic> build_traced_particles(interfaces::Simul
       check(nullptr, xpic_tracers_attach(simulation.ctx, set, 1), "xpic_tracers_attach"))
     throw std::runtime_error("TracedParticles: the tracer set could not be created");
   const std::string dir = CONFIG().out_dir + "/traced_particles" + (info.contains("name") ? "_" + info.at("name").as_string() : "");
+  std::vector<TracedParticles::Moment> moments;
+  if (info.contains("moments"))
+    for (auto&& mi : info.at("moments").arr) {
+      const std::string moment = mi.at("moment").as_string(), what = "TracedParticles " + moment;
+      TracedParticles::Moment m;
+      int dof = 0;
+      const int mkind = moment_kind(moment, &dof);
+      if (mkind < 0) throw std::runtime_error("Unknown moment name " + moment + " for TracedParticles");
+      m.region.size[0] = geom_nx; m.region.size[1] = geom_ny; m.region.size[2] = geom_nz;
+      m.region.dim = dof > 1 ? 4 : 3; m.region.dof = dof; m.region.start[3] = 0; m.region.size[3] = dof;
+      std::string suffix;
+      if (mi.contains("region")) parse_region(mi.at("region"), m.region, suffix, what);
+      check_region(m.region, what);
+      const int region6[6] = {(int)m.region.start[0], (int)m.region.start[1], (int)m.region.start[2], (int)m.region.size[0],
+        (int)m.region.size[1], (int)m.region.size[2]};
+      const int64_t map_every = mi.contains("every") ? mi.at("every").as_int() : 1;
+      if (check(nullptr, xpic_tracers_map_create(simulation.ctx, set, mkind, mi.at("q").as_double(), mi.at("m").as_double(),
+            mi.contains("weight") ? mi.at("weight").as_double() : 1.0, region6, map_every, &m.map), "xpic_tracers_map_create"))
+        throw std::runtime_error("TracedParticles: the map of " + moment + " could not be created");
+      m.dir = dir + "/" + moment + (suffix.empty() ? "" : "_" + suffix);
+      moments.push_back(m);
+    }
   LOG("  traced particles diagnostic is added: " << n << " " << kind << " tracers, period " << period << " [dt]");
-  return std::make_unique<TracedParticles>(dir, simulation, set, n, capacity, period);
+  if (!moments.empty()) LOG("    with " << moments.size() << " moment maps");
+  return std::make_unique<TracedParticles>(dir, simulation, set, n, capacity, period, std::move(moments));
+}
+
+// distribution_moment_builder.cpp:16-23: name -> enum xpic_moment_kind and dof; -1: unknown
+int moment_kind(const std::string& moment, int* dof)
+{
+  static const struct { const char* name; int dof, kind; } known[] = {{"density", 1, XPIC_MOMENT_DENSITY},
+    {"current", 3, XPIC_MOMENT_CURRENT}, {"momentum_flux", 6, XPIC_MOMENT_MOMENTUM_FLUX},
+    {"momentum_flux_cyl", 6, XPIC_MOMENT_MOMENTUM_FLUX_CYL}, {"momentum_flux_diag", 3, XPIC_MOMENT_MOMENTUM_FLUX_DIAG},
+    {"momentum_flux_diag_cyl", 3, XPIC_MOMENT_MOMENTUM_FLUX_DIAG_CYL}};
+  const auto k = std::find_if(std::begin(known), std::end(known), [&](const auto& e) { return moment == e.name; });
+  if (k == std::end(known)) return -1;
+  *dof = k->dof;
+  return k->kind;
 }
 
 // FieldViewBuilder::parse_region_start_size / parse_res_dir_suffix / check_region (field_view_builder.cpp:60-147)
@@ -1188,20 +1249,16 @@ PetscErrorCode build_diagnostics(interfaces::Simulation& simulation,
     }
     else if (name == "DistributionMoment") {
       const std::string particles = info.at("particles").as_string(), moment = info.at("moment").as_string();
-      // distribution_moment_builder.cpp:16-23: name -> dof; here also -> enum xpic_moment_kind
-      static const struct { const char* name; int dof, kind; } known[] = {{"density", 1, XPIC_MOMENT_DENSITY},
-        {"current", 3, XPIC_MOMENT_CURRENT}, {"momentum_flux", 6, XPIC_MOMENT_MOMENTUM_FLUX},
-        {"momentum_flux_cyl", 6, XPIC_MOMENT_MOMENTUM_FLUX_CYL}, {"momentum_flux_diag", 3, XPIC_MOMENT_MOMENTUM_FLUX_DIAG},
-        {"momentum_flux_diag_cyl", 3, XPIC_MOMENT_MOMENTUM_FLUX_DIAG_CYL}};
-      const auto k = std::find_if(std::begin(known), std::end(known), [&](const auto& e) { return moment == e.name; });
-      if (k == std::end(known)) throw std::runtime_error("Unknown moment name " + moment + " for particles " + particles);
-      region.dim = k->dof > 1 ? 4 : 3; region.dof = k->dof; region.start[3] = 0; region.size[3] = k->dof;
+      int mdof = 0;
+      const int mkind = moment_kind(moment, &mdof); // distribution_moment_builder.cpp:16-23: name -> dof; here also -> enum xpic_moment_kind
+      if (mkind < 0) throw std::runtime_error("Unknown moment name " + moment + " for particles " + particles);
+      region.dim = mdof > 1 ? 4 : 3; region.dof = mdof; region.start[3] = 0; region.size[3] = mdof;
       if (info.contains("region")) parse_region(info.at("region"), region, suffix, particles + " " + moment);
       check_region(region, particles + " " + moment);
       LOG("  " << moment << " diagnostic is added for " << particles << ", suffix: " << (suffix.empty() ? "<empty>" : suffix));
       if (!suffix.empty()) suffix = "_" + suffix;
       result.emplace_back(std::make_unique<DistributionMoment>(CONFIG().out_dir + "/" + particles + "/" + moment + suffix,
-        simulation, simulation.get_named_particles(particles), k->kind, region));
+        simulation, simulation.get_named_particles(particles), mkind, region));
     }
     else if (name == "VelocityDistribution") { // velocity_distribution_builder.cpp:13-115
       const std::string particles = info.at("particles").as_string(), projector = info.at("projector").as_string();

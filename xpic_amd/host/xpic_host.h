@@ -442,10 +442,21 @@ private:
 // the run's B by XPIC_GRADB_AUTO.  The set is created and attached when the diagnostics are built; every diagnose_period the
 // sample rows held are drained into <out_dir>/traced_particles[_name]/<time> as raw float64 [rows][n][6].  The class
 // exists only where the key is present.
+// Optional "moments": a list of {"moment" (a DistributionMoment name), "q", "m", optional "weight" (default 1), "every"
+// (steps, default 1) and "region" (as FieldView's)}: each is a map of the set (include/xpic_tracer_moments.h).  Every
+// diagnose_period the map's time average, out / deposits, is written as float32 to
+// <out_dir>/traced_particles[_name]/<moment>/<time> in DistributionMoment's file layout (the region's values
+// [z][y][x][c]) and the map is reset; a period without a deposit (the call at `start`) writes no file.  An entry without
+// the key runs and writes as it did before the key existed.
 class TracedParticles final : public interfaces::Diagnostic {
 public:
+  struct Moment {
+    int map;
+    FieldView::Region region;
+    std::string dir;
+  };
   TracedParticles(const std::string& out_dir, interfaces::Simulation& simulation, int set, int64_t n, int64_t capacity,
-    PetscInt period);
+    PetscInt period, std::vector<Moment> moments = {});
   PetscErrorCode diagnose(PetscInt t) override;
 
 private:
@@ -454,6 +465,7 @@ private:
   int set_;
   int64_t n_, capacity_;
   PetscInt period_;
+  std::vector<Moment> moments_;
 };
 
 // EXTENSION (not reference behaviour): "FieldLines", the lines of a field of the run through given points, traced on the
