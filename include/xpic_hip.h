@@ -960,4 +960,6 @@ int xpic_probe_copy_bandwidth(xpic_ctx* ctx, int64_t bytes, int reps, double* by
 #include "xpic_tracer_moments.h"
 /* ---- field lines of a grid vector or of an analytic model, traced on the device */
 #include "xpic_field_lines.h"
+/* ---- Gauss's law on the device: its residual and a cleaner (a scalar Poisson CG) */
+#include "xpic_gauss.h"
 #endif

@@ -167,7 +167,7 @@ _lib = None
 
 def load_library():
     """Loads libxpic_hip.so and types every entry point from PROTOTYPES, LOAD_PROTOTYPES, TRACER_PROTOTYPES,
-    TRACER_MOMENT_PROTOTYPES and FIELD_LINE_PROTOTYPES; raises if it has not been built (no fallback path exists).  The xpic_debug_*_stamps symbols of experiment builds are not in the header and stay untyped."""
+    TRACER_MOMENT_PROTOTYPES, FIELD_LINE_PROTOTYPES and GAUSS_PROTOTYPES; raises if it has not been built (no fallback path exists).  The xpic_debug_*_stamps symbols of experiment builds are not in the header and stay untyped."""
     global _lib
     if _lib is not None:
         return _lib
@@ -176,7 +176,7 @@ def load_library():
                         "xpic_amd has no CPU fallback")
     L = C.CDLL(LIB_PATH)
     for name, (ret, args) in dict(PROTOTYPES, **LOAD_PROTOTYPES, **TRACER_PROTOTYPES, **TRACER_MOMENT_PROTOTYPES,
-                                   **FIELD_LINE_PROTOTYPES).items():
+                                   **FIELD_LINE_PROTOTYPES, **GAUSS_PROTOTYPES).items():
         f = getattr(L, name)
         f.restype, f.argtypes = CTYPES[ret], [CTYPES[a] for a in args]
     if L.xpic_version() & VERSION_EXPERIMENT_BIT and os.environ.get("XPIC_ALLOW_EXPERIMENT") != "1":
@@ -454,7 +454,50 @@ class FieldLineCommands:
                                  region, directions, f_floor, close_tol, sample_every, launch_steps)
 
 
-class Context(LoadCommands, TracerCommands, FieldLineCommands):
+class GaussClean(collections.namedtuple("GaussClean", "iterations before after mean gphi phi")):
+    """One clean: CG iterations, |res|_2 before and after (the latter from the corrected field), the mean charge density
+    taken out (the neutralising background), |G phi|_2, and phi [nzl][ny][nx] where it was asked for (else None)"""
+
+
+class GaussCommands:
+    """Gauss's law div E = rho on the device (include/xpic_gauss.h; the reference has no cleaner), as methods of Context.
+    The calls use the vector W2 as scratch."""
+
+    def gauss_background(self, rho):
+        """a static charge density [nzl][ny][nx] that counts with the sorts' (None clears it)"""
+        if rho is not None:
+            rho = np.ascontiguousarray(rho, dtype=np.float64).reshape(self.nzl, self.n[1], self.n[0])
+        self._ck(self.L.xpic_gauss_background(self.h, _dp(rho)))
+
+    def gauss_residual(self, field=E, want_residual=False):
+        """res = D F - (rho - mean rho) -> dict(l1, l2, mean, rho_l2) (+ residual [nzl][ny][nx] with want_residual)"""
+        res = np.zeros((self.nzl, self.n[1], self.n[0])) if want_residual else None
+        o = np.zeros(4)
+        self._ck(self.L.xpic_gauss_residual(self.h, int(field), _dp(res), _dp(o)))
+        out = dict(l1=o[0], l2=o[1], mean=o[2], rho_l2=o[3])
+        if want_residual:
+            out["residual"] = res
+        return out
+
+    def gauss_clean(self, field=E, rtol=1e-10, atol=0.0, maxit=GAUSS_MAXIT, want_phi=False):
+        """F <- F - G phi with D G phi = res, by CG until |r|_2 <= max(rtol |rho - mean|_2, atol) -> GaussClean; raises
+        XpicError (the field untouched) when maxit iterations do not get there"""
+        phi = np.zeros((self.nzl, self.n[1], self.n[0])) if want_phi else None
+        o, its = np.zeros(4), C.c_int()
+        self._ck(self.L.xpic_gauss_clean(self.h, int(field), float(rtol), float(atol), int(maxit), _dp(phi), C.byref(its), _dp(o)))
+        return GaussClean(its.value, o[0], o[1], o[2], o[3], phi)
+
+    def set_gauss_clean(self, every, rtol=1e-10, atol=0.0, maxit=GAUSS_MAXIT):
+        """every k > 0: each step() whose count is a multiple of k cleans E before the tracer sets ride; 0: off"""
+        self._ck(self.L.xpic_set_gauss_clean(self.h, int(every), float(rtol), float(atol), int(maxit)))
+
+    def gauss_info(self):
+        o = np.zeros(6)
+        self._ck(self.L.xpic_gauss_info(self.h, _dp(o)))
+        return dict(cleans=int(o[0]), iterations=int(o[1]), before=o[2], after=o[3], mean=o[4], last_iterations=int(o[5]))
+
+
+class Context(LoadCommands, TracerCommands, FieldLineCommands, GaussCommands):
     """One z-slab context = one `interfaces::Simulation` backend instance."""
 
     def __init__(self, scheme, n, d, dt, device=0, rank=0, nranks=1, self_ring=False):

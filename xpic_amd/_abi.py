@@ -340,3 +340,14 @@ LINES_MAX_STEPS = 1 << 24   # XPIC_LINES_MAX_STEPS
 STAGGERS = {"B": 0, "E": 1}  # XPIC_STAGGER_B, XPIC_STAGGER_E
 LINE_DIRECTIONS = {"+": 1, "-": 2, "both": 3}
 LINE_CODES = {"maxsteps": 0, "left": 1, "null": 2, "closed": 3}  # XPIC_LINE_*
+
+# the entry points of include/xpic_gauss.h (Gauss's law: its residual and the cleaner), typed by load_library() as PROTOTYPES'
+# are; tests/test_abi_gauss.py holds them to that header
+GAUSS_PROTOTYPES = {
+    "xpic_gauss_background": ("int", ["xpic_ctx*", "const double*"]),
+    "xpic_gauss_residual": ("int", ["xpic_ctx*", "int", "double*", "double*"]),
+    "xpic_gauss_clean": ("int", ["xpic_ctx*", "int", "double", "double", "int", "double*", "int*", "double*"]),
+    "xpic_set_gauss_clean": ("int", ["xpic_ctx*", "int", "double", "double", "int"]),
+    "xpic_gauss_info": ("int", ["xpic_ctx*", "double*"]),
+}
+GAUSS_MAXIT = 10000  # the package's default iteration limit of a clean

@@ -410,6 +410,7 @@ int xpic_destroy(xpic_ctx* ctx)
   (void)hipFree(ctx->cmd_start); (void)hipFree(ctx->cmd_add); (void)hipFree(ctx->cmd_rank);
   background_free(ctx);
   tracers_free(ctx);
+  gauss_free(ctx);
   (void)hipFree(ctx->abar32); (void)hipFree(ctx->abar_work); (void)hipFree(ctx->abar_r);
   (void)hipFree(ctx->lrow_buf[0]); (void)hipFree(ctx->lrow_buf[1]);
   for (int i = 0; i < 4; ++i) (void)hipFree(ctx->halo_buf[i]);
@@ -839,6 +840,8 @@ int xpic_step(xpic_ctx* ctx, int* ksp_iterations)
     default: rc = step_ecsimcorr(ctx, &its); break;
   }
   if (ksp_iterations) *ksp_iterations = its;
+  ctx->steps_done += 1;
+  if (rc == 0 && ctx->gauss_every > 0 && ctx->steps_done % ctx->gauss_every == 0) rc = gauss_ride(ctx); // div E = rho restored
   if (rc == 0 && ctx->tracers) rc = tracers_ride(ctx); // the attached tracer sets, on the E and B the step leaves behind
   return rc;
 }

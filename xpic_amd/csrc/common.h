@@ -262,6 +262,14 @@ struct xpic_ctx {
   double* bg_profile[XPIC_TRACE_BG_MAX] = {}; // background.hip: the background profiles, [5][ncell] each; null: an empty slot
   int tracer_moment_lds = xpic::kTracerMomentLds; // tracer_moments.hip: the largest region x dof a workgroup keeps in LDS (xpic_debug_set)
   xpic::TracerSets* tracers = nullptr; // tracers.hip: made by the first xpic_tracers_create; null: xpic_step has nothing to carry
+  // gauss.hip: six scalar planes in two stored vectors {p, r, Ap} {phi, rho, spare} (made by the first gauss call), the static
+  // background charge (one component; null: none), the clean that rides with xpic_step (every 0: none) and xpic_gauss_info's numbers
+  double* gauss_ws = nullptr;
+  double* gauss_bg = nullptr;
+  int gauss_every = 0, gauss_maxit = 0;
+  double gauss_rtol = 0, gauss_atol = 0;
+  int64_t steps_done = 0; // calls of xpic_step
+  double gauss_info[6] = {0, 0, 0, 0, 0, 0};
   double rtol = 1e-7, atol = 1e-7;
   int maxit = 100;
   xpic::Comm comm;
@@ -405,6 +413,11 @@ void background_free(xpic_ctx* c);
 // tracers.hip: one step of every attached set, in creation order (xpic_step, only when c->tracers); frees the sets (xpic_destroy)
 int tracers_ride(xpic_ctx* c);
 void tracers_free(xpic_ctx* c);
+
+// gauss.hip (an extension: the reference has no Gauss-law cleaner): the clean of XPIC_E that rides with xpic_step (only when
+// c->gauss_every); frees the solve's vectors (xpic_destroy)
+int gauss_ride(xpic_ctx* c);
+void gauss_free(xpic_ctx* c);
 
 // ecsim.hip
 int ecsim_fill_sort(xpic_ctx* c, Sort& s, const double* B, double* currI_sort, double* matL, bool first_sort, bool post_ghost_rows);

@@ -227,8 +227,16 @@ PetscErrorCode Simulation::initialize()
   XCALL(build_commands(*this, "StepPresets", step_presets_));
   XCALL(build_diagnostics(*this, diagnostics_));
 
+  GaussLaw* gauss = nullptr; // (an extension; a config without the key runs as before)
+  if (const Configuration::json_t* info = CONFIG().json.find("GaussLaw")) {
+    auto diagnostic = std::make_unique<GaussLaw>(*this, *info);
+    gauss = diagnostic.get();
+    diagnostics_.emplace_back(std::move(diagnostic));
+  }
+
   LOG("Executing presets");
   for (auto&& preset : presets) XCALL(preset->execute(start));
+  if (gauss) XCALL(gauss->start());
   for (auto& diagnostic : diagnostics_) XCALL(diagnostic->diagnose(start));
   return 0;
 }
@@ -1488,6 +1496,49 @@ PetscErrorCode ChargeConservation::add_columns(PetscInt t)
   }
   add(13, "N1dQ_tot", "% .6e", norm[2 * particles.size()]);
   add(13, "N2dQ_tot", "% .6e", norm[2 * particles.size() + 1]);
+  return 0;
+}
+
+// ---- GaussLaw (an extension: no counterpart in the reference): the start clean, the clean that rides with the step, one table
+GaussLaw::GaussLaw(interfaces::Simulation& simulation, const Configuration::json_t& info)
+  : TableDiagnostic(CONFIG().out_dir + "/temporal/gauss_law.txt"), simulation(simulation)
+{
+  if (info.contains("at_start")) at_start_ = info.at("at_start").as_bool();
+  if (info.contains("every")) every_ = info.at("every").as_int();
+  if (info.contains("rtol")) rtol_ = info.at("rtol").as_double();
+  if (info.contains("atol")) atol_ = info.at("atol").as_double();
+  if (info.contains("maxit")) maxit_ = info.at("maxit").as_int();
+  if (info.contains("background") && info.at("background").as_string() != "neutralize")
+    throw std::runtime_error("GaussLaw: \"background\" is \"neutralize\" or absent");
+  if (every_ < 0) throw std::runtime_error("GaussLaw: \"every\" must be >= 0");
+  LOG("  GaussLaw is added: at_start " << at_start_ << ", every " << every_ << ", rtol " << rtol_ << ", atol " << atol_);
+}
+
+PetscErrorCode GaussLaw::start()
+{
+  for (auto& sort : simulation.particles_) XCALL(sort->flush());
+  if (at_start_) {
+    int its = 0;
+    double o4[4];
+    HIPCALL(xpic_gauss_clean(simulation.ctx, XPIC_E, rtol_, atol_, maxit_, nullptr, &its, o4));
+    LOG("  Gauss law at start: |res| " << o4[0] << " -> " << o4[1] << ", " << its << " iterations, mean charge " << o4[2]);
+  }
+  HIPCALL(xpic_set_gauss_clean(simulation.ctx, every_, rtol_, atol_, maxit_));
+  return 0;
+}
+
+PetscErrorCode GaussLaw::add_columns(PetscInt t)
+{
+  double info[6], o4[4];
+  HIPCALL(xpic_gauss_info(simulation.ctx, info));
+  const bool cleaned = info[0] != cleans_seen_; // a clean ran since the last row: at the start, or inside this step
+  cleans_seen_ = info[0];
+  if (!cleaned) HIPCALL(xpic_gauss_residual(simulation.ctx, XPIC_E, nullptr, o4));
+  add_int(6, "Time", t);
+  add(13, "Res_before", "% .6e", cleaned ? info[2] : o4[1]);
+  add(13, "Res_after", "% .6e", cleaned ? info[3] : o4[1]);
+  add(13, "Mean_rho", "% .6e", cleaned ? info[4] : o4[2]);
+  add_int(10, "Iterations", cleaned ? (long)info[5] : 0);
   return 0;
 }
 

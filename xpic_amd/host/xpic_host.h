@@ -370,6 +370,26 @@ private:
   interfaces::Simulation& simulation;
 };
 
+// The optional top-level "GaussLaw" object (an extension: the reference has no Gauss-law cleaner; include/xpic_gauss.h):
+//   {"at_start": bool, "every": int, "rtol": 1e-10, "atol": 0, "maxit": 10000, "background": "neutralize"}
+// at_start: the run's initial E is cleaned once the presets have loaded the particles (the electrostatic start); every k > 0:
+// xpic_step cleans E on every k-th step.  "background": "neutralize" (the default, and the only kind) names what the clean
+// does with a net charge: its mean is taken out as a uniform neutralising background and reported.  One row per diagnosed
+// step in temporal/gauss_law.txt: |res|_2 before and after, the mean taken out, the iterations; on a step without a clean
+// both norms are the residual as it stands and the iterations are 0.
+class GaussLaw : public TableDiagnostic {
+public:
+  GaussLaw(interfaces::Simulation& simulation, const Configuration::json_t& info);
+  PetscErrorCode start(); // after the presets, before the first diagnose
+  PetscErrorCode add_columns(PetscInt t) override;
+
+private:
+  interfaces::Simulation& simulation;
+  bool at_start_ = false;
+  int every_ = 0, maxit_ = 10000;
+  double rtol_ = 1e-10, atol_ = 0.0, cleans_seen_ = 0.0;
+};
+
 class MomentumConservation : public TableDiagnostic { // src/diagnostics/momentum_conservation.cpp:7-131
 public:
   explicit MomentumConservation(interfaces::Simulation& simulation);
