@@ -56,7 +56,7 @@ enum xpic_field {
   XPIC_CURRJE = 7, XPIC_W0 = 8, XPIC_W1 = 9, XPIC_W2 = 10, XPIC_NFIELDS = 11
 };
 
-enum xpic_scheme { XPIC_BASIC = 0, XPIC_ECSIM = 1, XPIC_ECSIMCORR = 2 };
+enum xpic_scheme { XPIC_BASIC = 0, XPIC_ECSIM = 1, XPIC_ECSIMCORR = 2, XPIC_ES = 3 /* electrostatic: xpic_es.h */ };
 
 /* operator / method selector of xpic_solve */
 enum xpic_solve_op {
@@ -962,4 +962,6 @@ int xpic_probe_copy_bandwidth(xpic_ctx* ctx, int64_t bytes, int reps, double* by
 #include "xpic_field_lines.h"
 /* ---- Gauss's law on the device: its residual and a cleaner (a scalar Poisson CG) */
 #include "xpic_gauss.h"
+/* ---- the electrostatic scheme XPIC_ES: Boris push, fused charge deposit, Poisson solve */
+#include "xpic_es.h"
 #endif

@@ -167,7 +167,7 @@ _lib = None
 
 def load_library():
     """Loads libxpic_hip.so and types every entry point from PROTOTYPES, LOAD_PROTOTYPES, TRACER_PROTOTYPES,
-    TRACER_MOMENT_PROTOTYPES, FIELD_LINE_PROTOTYPES and GAUSS_PROTOTYPES; raises if it has not been built (no fallback path exists).  The xpic_debug_*_stamps symbols of experiment builds are not in the header and stay untyped."""
+    TRACER_MOMENT_PROTOTYPES, FIELD_LINE_PROTOTYPES, GAUSS_PROTOTYPES and ES_PROTOTYPES; raises if it has not been built (no fallback path exists).  The xpic_debug_*_stamps symbols of experiment builds are not in the header and stay untyped."""
     global _lib
     if _lib is not None:
         return _lib
@@ -176,7 +176,7 @@ def load_library():
                         "xpic_amd has no CPU fallback")
     L = C.CDLL(LIB_PATH)
     for name, (ret, args) in dict(PROTOTYPES, **LOAD_PROTOTYPES, **TRACER_PROTOTYPES, **TRACER_MOMENT_PROTOTYPES,
-                                   **FIELD_LINE_PROTOTYPES, **GAUSS_PROTOTYPES).items():
+                                   **FIELD_LINE_PROTOTYPES, **GAUSS_PROTOTYPES, **ES_PROTOTYPES).items():
         f = getattr(L, name)
         f.restype, f.argtypes = CTYPES[ret], [CTYPES[a] for a in args]
     if L.xpic_version() & VERSION_EXPERIMENT_BIT and os.environ.get("XPIC_ALLOW_EXPERIMENT") != "1":
@@ -497,7 +497,19 @@ class GaussCommands:
         return dict(cleans=int(o[0]), iterations=int(o[1]), before=o[2], after=o[3], mean=o[4], last_iterations=int(o[5]))
 
 
-class Context(LoadCommands, TracerCommands, FieldLineCommands, GaussCommands):
+class EsCommands:
+    """The electrostatic scheme "es" (include/xpic_es.h; the reference has none), as methods of Context: the scheme itself
+    is Context("es", ...).step(), which returns the CG iterations of the step's Poisson solve."""
+
+    def es_push(self, sort):
+        """the electrostatic scheme's gather, kick, full move and charge deposit of one sort (include/xpic_es.h) -> that
+        sort's rho [nzl][ny][nx] at the new positions; no re-bin (update_cells) and no field solve"""
+        rho = np.zeros((self.nzl, self.n[1], self.n[0]))
+        self._ck(self.L.xpic_es_push(self.h, int(sort), _dp(rho)))
+        return rho
+
+
+class Context(LoadCommands, TracerCommands, FieldLineCommands, GaussCommands, EsCommands):
     """One z-slab context = one `interfaces::Simulation` backend instance."""
 
     def __init__(self, scheme, n, d, dt, device=0, rank=0, nranks=1, self_ring=False):
@@ -777,6 +789,7 @@ class Context(LoadCommands, TracerCommands, FieldLineCommands, GaussCommands):
         self._ck(self.L.xpic_set_overlap(self.h, int(on)))  # bit 0: operator halos, bit 1: matL ghost rows
 
     def step(self):
+        """one timestep -> the step's Krylov iterations ("es": the CG iterations of its Poisson solve)"""
         its = C.c_int()
         self._ck(self.L.xpic_step(self.h, C.byref(its)))
         return its.value

@@ -3,10 +3,10 @@ load_library() types every symbol from the table; tests/test_abi.py holds table,
 import ctypes as C
 
 E, B, B0, J, EP, EC, CURRI, CURRJE, W0, W1, W2 = range(11)
-BASIC, ECSIM, ECSIMCORR = 0, 1, 2
+BASIC, ECSIM, ECSIMCORR, ES = 0, 1, 2, 3
 OP_MATA_GMRES, OP_MATM_GMRES, OP_MATM_CG = 0, 1, 2
 LSTENCIL = 123
-SCHEMES = {"basic": BASIC, "ecsim": ECSIM, "ecsimcorr": ECSIMCORR}
+SCHEMES = {"basic": BASIC, "ecsim": ECSIM, "ecsimcorr": ECSIMCORR, "es": ES}
 
 
 class Geometry(C.Structure):
@@ -351,3 +351,10 @@ GAUSS_PROTOTYPES = {
     "xpic_gauss_info": ("int", ["xpic_ctx*", "double*"]),
 }
 GAUSS_MAXIT = 10000  # the package's default iteration limit of a clean
+
+# the entry point of include/xpic_es.h (the electrostatic scheme's particle phase alone), typed by load_library() as
+# PROTOTYPES' are; tests/test_abi_es.py holds it to that header
+ES_PROTOTYPES = {
+    "xpic_es_push": ("int", ["xpic_ctx*", "int", "double*"]),
+}
+ES_RTOL, ES_ATOL, ES_MAXIT = 1e-10, 1e-14, 10000  # the tolerances an "es" context is created with (xpic_es.h)

@@ -222,6 +222,23 @@ static int step_basic(xpic_ctx* c)
   return 0;
 }
 
+// The electrostatic step (include/xpic_es.h; an extension: the reference has no electrostatic scheme): per sort the fused
+// push + charge deposit of es.hip and the re-binning, then Gauss's law restored on E^n with the charge of r^{n+1} by
+// gauss.hip's clean -- E^n is the solve's warm start, rot E and the mean of E are not touched, XPIC_B is never written.
+static int step_es(xpic_ctx* c, int* its)
+{
+  double *E = c->field[XPIC_E], *B = c->field[XPIC_B], *rho = c->es_rho;
+  XPIC_CALL(halo_fill(c, E));
+  XPIC_CALL(halo_fill(c, B));
+  XPIC_HIP(hipMemsetAsync(rho, 0, sizeof(double) * c->nvec, c->stream));
+  for (auto& s : c->sorts) {
+    XPIC_CALL(es_push(c, s, E, B, rho));
+    XPIC_CALL(sort_rebin(c, s, 0.0, true, 0)); // correct_coordinates + update_cells, as the basic step's
+  }
+  XPIC_CALL(halo_add(c, rho, 3)); // the ghost planes' share goes to its owners (charge_density's DMLocalToGlobal ADD)
+  return gauss_clean_given(c, rho, c->rtol, c->atol, c->maxit, its);
+}
+
 static int calc_energy(xpic_ctx* c, Sort& s)
 {
   double o[5];
@@ -312,7 +329,9 @@ int xpic_create(const xpic_geometry* geom, int scheme, xpic_ctx** out)
   XPIC_CHECK(geom->n[2] % geom->nranks == 0, "nz must be divisible by the number of z-slabs");
   // (self_ring slabs too: halo_add's two sides are one launch and must not overlap, 2 x 3 planes)
   XPIC_CHECK((geom->nranks == 1 && !geom->self_ring) || geom->n[2] / geom->nranks >= 6, "a z-slab must hold at least 6 planes");
-  XPIC_CHECK(scheme == XPIC_BASIC || scheme == XPIC_ECSIM || scheme == XPIC_ECSIMCORR, "unknown scheme");
+  XPIC_CHECK(scheme == XPIC_BASIC || scheme == XPIC_ECSIM || scheme == XPIC_ECSIMCORR || scheme == XPIC_ES, "unknown scheme");
+  XPIC_CHECK(scheme != XPIC_ES || (geom->n[0] >= 6 && geom->n[1] >= 6 && geom->n[2] / geom->nranks >= 6),
+    "the electrostatic scheme needs every grid extent, and every z-slab, >= 6 cells");
   int ndev = 0;
   XPIC_HIP(hipGetDeviceCount(&ndev));
   XPIC_CHECK(ndev > 0, "no HIP device: the xpic HIP path has no CPU fallback");
@@ -349,7 +368,9 @@ int xpic_create(const xpic_geometry* geom, int scheme, xpic_ctx** out)
   c->ncell = g.nown;
   XPIC_HIP(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
   for (int f = 0; f < XPIC_NFIELDS; ++f) {
-    const bool need = scheme != XPIC_BASIC || (f != XPIC_EP && f != XPIC_EC && f != XPIC_CURRI && f != XPIC_CURRJE);
+    // (the electrostatic scheme: E, B and the work vectors; no current, no B0)
+    const bool need = scheme == XPIC_ES ? (f == XPIC_E || f == XPIC_B || f >= XPIC_W0)
+                                        : (scheme != XPIC_BASIC || (f != XPIC_EP && f != XPIC_EC && f != XPIC_CURRI && f != XPIC_CURRJE));
     if (!need) continue;
     XPIC_HIP(hipMalloc(&c->field[f], sizeof(double) * c->nvec));
     XPIC_HIP(hipMemsetAsync(c->field[f], 0, sizeof(double) * c->nvec, c->stream));
@@ -357,7 +378,14 @@ int xpic_create(const xpic_geometry* geom, int scheme, xpic_ctx** out)
   XPIC_HIP(hipMalloc(&c->red_partial, sizeof(double) * kMaxDots * kRedBlocks));
   XPIC_HIP(hipMalloc(&c->red_out, sizeof(double) * 128));
   XPIC_HIP(hipHostMalloc(&c->red_host, sizeof(double) * 64));
-  if (scheme != XPIC_BASIC) {
+  if (scheme == XPIC_ES) {
+    // the Gauss vectors and the charge accumulator; the tolerances of an unpreconditioned CG on the Laplacian (xpic_es.h)
+    XPIC_CALL(gauss_reserve(c));
+    XPIC_HIP(hipMalloc(&c->es_rho, sizeof(double) * c->nvec));
+    XPIC_HIP(hipMemsetAsync(c->es_rho, 0, sizeof(double) * c->nvec, c->stream));
+    c->rtol = 1e-10; c->atol = 1e-14; c->maxit = 10000;
+  }
+  if (scheme == XPIC_ECSIM || scheme == XPIC_ECSIMCORR) {
     XPIC_HIP(hipMalloc(&c->matL, sizeof(double) * matL_doubles(g)));
     XPIC_HIP(hipMemsetAsync(c->matL, 0, sizeof(double) * matL_doubles(g), c->stream));
     XPIC_HIP(hipMalloc(&c->kry_V, sizeof(double) * c->nvec * 31));
@@ -391,7 +419,7 @@ int xpic_create(const xpic_geometry* geom, int scheme, xpic_ctx** out)
   }
   // the round table of the Esirkepov pushes is sized with the context too (a push finds it there; without room for it the
   // pushes compose their rounds themselves, on this rank alone: no collective depends on it)
-  if (scheme != XPIC_ECSIM && g.nx >= 6 && g.ny >= 6 && g.nzl >= 6) esk_table_alloc(c);
+  if ((scheme == XPIC_BASIC || scheme == XPIC_ECSIMCORR) && g.nx >= 6 && g.ny >= 6 && g.nzl >= 6) esk_table_alloc(c);
   XPIC_HIP(hipStreamSynchronize(c->stream));
   *out = c;
   return 0;
@@ -411,6 +439,7 @@ int xpic_destroy(xpic_ctx* ctx)
   background_free(ctx);
   tracers_free(ctx);
   gauss_free(ctx);
+  (void)hipFree(ctx->es_rho);
   (void)hipFree(ctx->abar32); (void)hipFree(ctx->abar_work); (void)hipFree(ctx->abar_r);
   (void)hipFree(ctx->lrow_buf[0]); (void)hipFree(ctx->lrow_buf[1]);
   for (int i = 0; i < 4; ++i) (void)hipFree(ctx->halo_buf[i]);
@@ -437,9 +466,11 @@ int xpic_add_sort(xpic_ctx* ctx, const xpic_sort_params* p, int64_t capacity, in
   Sort s;
   s.par = *p;
   XPIC_CALL(sort_alloc(ctx, s, capacity));
-  double** cur = ctx->scheme == XPIC_BASIC ? &s.J : &s.currI;
-  XPIC_HIP(hipMalloc(cur, sizeof(double) * ctx->nvec));
-  XPIC_HIP(hipMemsetAsync(*cur, 0, sizeof(double) * ctx->nvec, ctx->stream));
+  if (ctx->scheme != XPIC_ES) { // (an electrostatic sort has no current)
+    double** cur = ctx->scheme == XPIC_BASIC ? &s.J : &s.currI;
+    XPIC_HIP(hipMalloc(cur, sizeof(double) * ctx->nvec));
+    XPIC_HIP(hipMemsetAsync(*cur, 0, sizeof(double) * ctx->nvec, ctx->stream));
+  }
   if (ctx->scheme == XPIC_ECSIMCORR) {
     XPIC_HIP(hipMalloc(&s.currJe, sizeof(double) * ctx->nvec));
     XPIC_HIP(hipMemsetAsync(s.currJe, 0, sizeof(double) * ctx->nvec, ctx->stream));
@@ -631,6 +662,7 @@ int xpic_ecsim_fill_current(xpic_ctx* ctx)
 {
   CTX_CHECK(ctx);
   XPIC_CHECK(ctx->scheme != XPIC_BASIC, "basic scheme has no ECSIM current");
+  XPIC_CHECK(ctx->scheme != XPIC_ES, "electrostatic scheme has no ECSIM current");
   return ecsim_fill_current(ctx);
 }
 
@@ -638,6 +670,7 @@ int xpic_ecsim_second_push(xpic_ctx* ctx, int sort)
 {
   CTX_CHECK(ctx); SORT_CHECK(sort);
   XPIC_CHECK(ctx->scheme != XPIC_BASIC, "basic scheme has no second_push");
+  XPIC_CHECK(ctx->scheme != XPIC_ES, "electrostatic scheme has no second_push");
   XPIC_CALL(halo_fill(ctx, ctx->field[XPIC_EP]));
   XPIC_CALL(halo_fill(ctx, ctx->field[XPIC_B]));
   return ecsim_second_push(ctx, ctx->sorts[sort], ctx->field[XPIC_EP], ctx->field[XPIC_B]);
@@ -837,6 +870,7 @@ int xpic_step(xpic_ctx* ctx, int* ksp_iterations)
   switch (ctx->scheme) {
     case XPIC_BASIC: rc = step_basic(ctx); break;
     case XPIC_ECSIM: rc = step_ecsim(ctx, &its); break;
+    case XPIC_ES: rc = step_es(ctx, &its); break;
     default: rc = step_ecsimcorr(ctx, &its); break;
   }
   if (ksp_iterations) *ksp_iterations = its;
@@ -888,7 +922,7 @@ int xpic_momentum(xpic_ctx* ctx, double* out) // MomentumConservation::calculate
 
 static double* sort_current(xpic_ctx* ctx, Sort& s)
 {
-  return ctx->scheme == XPIC_BASIC ? s.J : (ctx->scheme == XPIC_ECSIM ? s.currI : s.currJe);
+  return ctx->scheme == XPIC_BASIC ? s.J : (ctx->scheme == XPIC_ECSIM ? s.currI : (ctx->scheme == XPIC_ECSIMCORR ? s.currJe : nullptr));
 }
 
 // the first nc components of a stored vector, per owned node: out[i * stride + j]
@@ -907,6 +941,19 @@ int xpic_charge_density(xpic_ctx* ctx, int sort, double* rho_zyx)
   double* tmp = ctx->field[XPIC_W2];
   XPIC_CALL(charge_density(ctx, ctx->sorts[sort], tmp));
   return export_components(ctx, tmp, 1, 1, rho_zyx);
+}
+
+int xpic_es_push(xpic_ctx* ctx, int sort, double* rho_zyx)
+{
+  CTX_CHECK(ctx); SORT_CHECK(sort);
+  XPIC_CHECK(ctx->scheme == XPIC_ES, "xpic_es_push needs the electrostatic scheme");
+  XPIC_CHECK(rho_zyx, "null argument");
+  XPIC_CALL(halo_fill(ctx, ctx->field[XPIC_E]));
+  XPIC_CALL(halo_fill(ctx, ctx->field[XPIC_B]));
+  XPIC_HIP(hipMemsetAsync(ctx->es_rho, 0, sizeof(double) * ctx->nvec, ctx->stream));
+  XPIC_CALL(es_push(ctx, ctx->sorts[sort], ctx->field[XPIC_E], ctx->field[XPIC_B], ctx->es_rho));
+  XPIC_CALL(halo_add(ctx, ctx->es_rho, 3));
+  return export_components(ctx, ctx->es_rho, 1, 1, rho_zyx);
 }
 
 int xpic_moment(xpic_ctx* ctx, int sort, int kind, const int region6[6], double* out)
@@ -1041,6 +1088,7 @@ int xpic_charge_collect(xpic_ctx* ctx) // ChargeConservation::initialize, charge
 int xpic_charge_columns(xpic_ctx* ctx, double* out) // ChargeConservation::add_columns, :125-171
 {
   CTX_CHECK(ctx);
+  XPIC_CHECK(ctx->scheme != XPIC_ES, "xpic_charge_columns: the electrostatic scheme has no current to take the divergence of");
   double* sum = ctx->field[XPIC_W0];
   double* diff = ctx->field[XPIC_W1];
   double* fresh = ctx->field[XPIC_W2];
@@ -1056,7 +1104,7 @@ int xpic_charge_columns(xpic_ctx* ctx, double* out) // ChargeConservation::add_c
     XPIC_CALL(div_neg_add(ctx, sort_current(ctx, s), diff));
     XPIC_CALL(scalar_norm12_host(ctx, diff, out + 2 * i));
   }
-  double* total = ctx->scheme == XPIC_BASIC ? ctx->field[XPIC_J] : (ctx->scheme == XPIC_ECSIM ? ctx->field[XPIC_CURRI] : ctx->field[XPIC_CURRJE]);
+  double* total = ctx->scheme == XPIC_BASIC ? ctx->field[XPIC_J] : (ctx->scheme == XPIC_ECSIM ? ctx->field[XPIC_CURRI] : ctx->field[XPIC_CURRJE]); // (XPIC_ES was refused above)
   XPIC_CALL(div_neg_add(ctx, total, sum));
   XPIC_CALL(scalar_norm12_host(ctx, sum, out + 2 * i));
   return 0;

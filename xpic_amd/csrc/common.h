@@ -270,6 +270,9 @@ struct xpic_ctx {
   double gauss_rtol = 0, gauss_atol = 0;
   int64_t steps_done = 0; // calls of xpic_step
   double gauss_info[6] = {0, 0, 0, 0, 0, 0};
+  // es.hip: the electrostatic step's charge accumulator (a stored vector whose component 0 is rho: the halo exchange adds whole
+  // vectors), made with an XPIC_ES context; null on every other scheme
+  double* es_rho = nullptr;
   double rtol = 1e-7, atol = 1e-7;
   int maxit = 100;
   xpic::Comm comm;
@@ -418,6 +421,14 @@ void tracers_free(xpic_ctx* c);
 // c->gauss_every); frees the solve's vectors (xpic_destroy)
 int gauss_ride(xpic_ctx* c);
 void gauss_free(xpic_ctx* c);
+int gauss_reserve(xpic_ctx* c); // the solve's vectors, made now (an XPIC_ES context sizes its memory at create)
+// the clean of XPIC_E with a charge it is handed (component 0 of a stored vector, ghost planes already added; the background
+// and the mean are dealt with here) instead of a deposit of its own: the electrostatic step's field solve
+int gauss_clean_given(xpic_ctx* c, const double* rho_vec, double rtol, double atol, int maxit, int* iterations);
+
+// es.hip: the electrostatic scheme's particle phase of one sort -- gather at r, kick, full move, deposit of the new position
+// into component 0 of rho_vec (added to what is there; ghost planes included, the caller adds them to their owners)
+int es_push(xpic_ctx* c, Sort& s, const double* E, const double* B, double* rho_vec);
 
 // ecsim.hip
 int ecsim_fill_sort(xpic_ctx* c, Sort& s, const double* B, double* currI_sort, double* matL, bool first_sort, bool post_ghost_rows);

@@ -29,6 +29,8 @@
 //     directly with fp64 atomics (slow path, same arithmetic as the reference's loop).
 //   * The boxes are merged in a circular LDS J window (11 x 4 x 4 nodes per component); the columns the march has
 //     passed leave with one fp64 atomic per node.
+// (es.hip's k_es_push carries a copy of MODE 0's gather -- node ranges, weight expressions, summation order -- at the stored
+// position: a change to that gather belongs there too.)
 #include <cstdlib>
 #include <cstring>
 

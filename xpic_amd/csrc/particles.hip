@@ -723,7 +723,7 @@ int sort_alloc(xpic_ctx* c, Sort& s, int64_t cap)
   s.d.src = nullptr; s.d.inc = nullptr;
   s.d.bucket = nullptr; s.d.bucket_cap = 0; s.d.ncell = c->ncell;
   XPIC_HIP(hipMalloc(&s.d.src, sizeof(int) * (cap + 1))); // deferred scatter (into the assembly, or into the next Esirkepov push)
-  if (c->scheme != XPIC_BASIC) {
+  if (c->scheme == XPIC_ECSIM || c->scheme == XPIC_ECSIMCORR) {
     // buckets of XPIC_BUCKET_CAP source indices per cell, where they cost at most as much as the particles' keys
     // (twice the mean occupancy the capacity allows, in steps of 32, at most XPIC_BUCKET_CAP: a Poisson cell never gets there)
     long bcap = ((2 * cap / c->ncell + 32 + 31) / 32) * 32;
@@ -1156,6 +1156,7 @@ int charge_density(xpic_ctx* c, Sort& s, double* rho_vec)
   XPIC_CALL(sort_materialize(c, s)); // (a deferred re-binning whose assembly has not run)
   XPIC_HIP(hipMemsetAsync(rho_vec, 0, sizeof(double) * c->nvec, c->stream));
   if (s.n > 0) {
+    Timed t(c, "charge_density");
     hipLaunchKernelGGL(k_charge_density, dim3(pgrid(s.n)), dim3(kBlock), 0, c->stream, c->g, s.d, s.n,
       s.par.q * (s.par.n / s.par.Np), rho_vec);
     XPIC_HIP(hipGetLastError());

@@ -219,7 +219,8 @@ PetscErrorCode Simulation::initialize()
 
   // the always-on conservation diagnostic (simulation.cpp:39-50)
   diagnostics_.emplace_back(std::make_unique<Energy>(*this));
-  diagnostics_.emplace_back(std::make_unique<ChargeConservation>(*this)); // simulation.cpp:52-53
+  // (the electrostatic scheme has no current to take the divergence of)
+  if (scheme() != XPIC_ES) diagnostics_.emplace_back(std::make_unique<ChargeConservation>(*this)); // simulation.cpp:52-53
   diagnostics_.emplace_back(std::make_unique<MomentumConservation>(*this)); // simulation.cpp:55-56
 
   std::vector<std::unique_ptr<Command>> presets;
@@ -230,6 +231,11 @@ PetscErrorCode Simulation::initialize()
   GaussLaw* gauss = nullptr; // (an extension; a config without the key runs as before)
   if (const Configuration::json_t* info = CONFIG().json.find("GaussLaw")) {
     auto diagnostic = std::make_unique<GaussLaw>(*this, *info);
+    gauss = diagnostic.get();
+    diagnostics_.emplace_back(std::move(diagnostic));
+  }
+  else if (scheme() == XPIC_ES) { // the step's own solve is tabulated whether the key is there or not
+    auto diagnostic = std::make_unique<GaussLaw>(*this);
     gauss = diagnostic.get();
     diagnostics_.emplace_back(std::move(diagnostic));
   }
@@ -355,6 +361,15 @@ PetscErrorCode ecsim::Simulation::timestep_implementation(PetscInt /* t */)
   return 0;
 }
 
+PetscErrorCode electrostatic::Simulation::timestep_implementation(PetscInt /* t */)
+{
+  int its = 0;
+  HIPCALL(xpic_step(ctx, &its));
+  last_cg_iterations = its;
+  LOG("  Poisson CG has finished, iterations: " << its);
+  return 0;
+}
+
 std::unique_ptr<interfaces::Simulation> build_simulation()
 {
   const std::string simulation_str = CONFIG().json.at("Simulation").as_string();
@@ -362,6 +377,7 @@ std::unique_ptr<interfaces::Simulation> build_simulation()
   if (simulation_str == "basic") simulation = std::make_unique<basic::Simulation>();
   else if (simulation_str == "ecsim") simulation = std::make_unique<ecsim::Simulation>();
   else if (simulation_str == "ecsimcorr") simulation = std::make_unique<ecsimcorr::Simulation>();
+  else if (simulation_str == "electrostatic") simulation = std::make_unique<electrostatic::Simulation>();
   else throw std::runtime_error("Unkown simulation is used: " + simulation_str);
   LOG("Simulation is built, scheme " << simulation_str);
   return simulation;
@@ -1340,6 +1356,7 @@ PetscErrorCode SimulationBackup::save(PetscInt t)
   if (n3 > (size_t)INT32_MAX) throw std::runtime_error("SimulationBackup: the Vec length exceeds the 32-bit PetscInt of the file format");
   std::vector<double> data(n3);
   for (const char* name : kBackupFields) { // save_fields :48-63, VecView of a DMDA vector = natural ordering
+    if (simulation.scheme() == XPIC_ES && std::string(name) == "B0") continue; // (the electrostatic scheme holds no B0)
     HIPCALL(xpic_field_get(simulation.ctx, simulation.get_named_vector(name), data.data()));
     std::ofstream f(dir + "/" + name, std::ios::binary);
     const int32_t header[2] = {kVecFileClassId, (int32_t)n3};
@@ -1374,6 +1391,7 @@ PetscErrorCode SimulationBackup::load(PetscInt t)
   const size_t n3 = (size_t)geom_nx * geom_ny * geom_nz * 3;
   std::vector<double> data(n3);
   for (const char* name : kBackupFields) { // load_fields :117-131
+    if (simulation.scheme() == XPIC_ES && std::string(name) == "B0") continue;
     std::ifstream f(dir + "/" + name, std::ios::binary);
     int32_t header[2] = {0, 0};
     if (!f || !get_be(f, header, 4, 2) || header[0] != kVecFileClassId || (size_t)header[1] != n3 ||
@@ -1511,7 +1529,15 @@ GaussLaw::GaussLaw(interfaces::Simulation& simulation, const Configuration::json
   if (info.contains("background") && info.at("background").as_string() != "neutralize")
     throw std::runtime_error("GaussLaw: \"background\" is \"neutralize\" or absent");
   if (every_ < 0) throw std::runtime_error("GaussLaw: \"every\" must be >= 0");
+  if (every_ > 0 && simulation.scheme() == XPIC_ES)
+    throw std::runtime_error("GaussLaw: \"every\" is refused on an electrostatic simulation: its step solves Gauss's law itself");
   LOG("  GaussLaw is added: at_start " << at_start_ << ", every " << every_ << ", rtol " << rtol_ << ", atol " << atol_);
+}
+
+GaussLaw::GaussLaw(interfaces::Simulation& simulation)
+  : TableDiagnostic(CONFIG().out_dir + "/temporal/gauss_law.txt"), simulation(simulation)
+{
+  LOG("  GaussLaw table is added (the electrostatic step's own solve)");
 }
 
 PetscErrorCode GaussLaw::start()
@@ -1523,7 +1549,7 @@ PetscErrorCode GaussLaw::start()
     HIPCALL(xpic_gauss_clean(simulation.ctx, XPIC_E, rtol_, atol_, maxit_, nullptr, &its, o4));
     LOG("  Gauss law at start: |res| " << o4[0] << " -> " << o4[1] << ", " << its << " iterations, mean charge " << o4[2]);
   }
-  HIPCALL(xpic_set_gauss_clean(simulation.ctx, every_, rtol_, atol_, maxit_));
+  if (simulation.scheme() != XPIC_ES) HIPCALL(xpic_set_gauss_clean(simulation.ctx, every_, rtol_, atol_, maxit_));
   return 0;
 }
 

@@ -189,6 +189,22 @@ public:
 };
 }  // namespace ecsimcorr
 
+namespace electrostatic {
+// "Simulation": "electrostatic" (an extension: the reference has no electrostatic scheme; include/xpic_es.h): the XPIC_ES
+// context behind the usual Particles, Presets and energy tables.  B is the external static field (SetMagneticField with
+// "field": "B"; the scheme holds no B0, so backups hold E and B); there is no current, so no charge_conservation.txt.  The
+// "GaussLaw" key: at_start is honoured (the electrostatic start), "every" > 0 is refused -- the step solves Gauss's law
+// itself; temporal/gauss_law.txt is written with or without the key, one row per step from the step's own solve.
+class Simulation final : public interfaces::Simulation {
+public:
+  int scheme() const override { return XPIC_ES; }
+  PetscInt last_cg_iterations = 0;
+
+protected:
+  PetscErrorCode timestep_implementation(PetscInt timestep) override;
+};
+}  // namespace electrostatic
+
 /// @returns Concrete simulation using `config` specification (src/interfaces/simulation.cpp:160-182).
 std::unique_ptr<interfaces::Simulation> build_simulation();
 
@@ -380,6 +396,7 @@ private:
 class GaussLaw : public TableDiagnostic {
 public:
   GaussLaw(interfaces::Simulation& simulation, const Configuration::json_t& info);
+  explicit GaussLaw(interfaces::Simulation& simulation); // no key (an electrostatic run's table): the defaults below
   PetscErrorCode start(); // after the presets, before the first diagnose
   PetscErrorCode add_columns(PetscInt t) override;
 
