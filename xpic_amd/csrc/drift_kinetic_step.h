@@ -1,12 +1,14 @@
 // drift_kinetic_step.h -- the device functions of drift_kinetic.hip: the gather and one step of the drift-kinetic pusher,
 // the twin of full_orbit_step.h.  They are in a header so that compare_trace.hip, which advances a guiding centre beside a
-// full orbit in one lane, inlines the same text as k_dk_push and k_dk_trace.  Included after common.h, device_common.h and
-// ie_shape.h, with `#pragma clang fp contract(on)` in force: contraction per source expression only, so every caller
-// rounds alike.
+// full orbit in one lane, inlines the same text as k_dk_push and k_dk_trace.  Included with `#pragma clang fp contract(on)`
+// in force: contraction per source expression only, so every caller rounds alike; shape2.h (Shape2, segment_gather_E,
+// len3 / dot3 / cross3) comes in here, under that pragma.
 //   DriftKineticEsirkepov::interpolate   src/algorithms/drift_kinetic_implicit.cpp:11-31
 //   DriftKineticPush::process            src/algorithms/drift_kinetic_push.cpp:48-160
 //   PointByField                         src/interfaces/point.h:37-58
 #pragma once
+
+#include "shape2.h"
 
 namespace xpic {
 
@@ -16,17 +18,7 @@ struct DKPoint {
   double r[3], ppar, pperp, mu;
 };
 
-// Vector3::length (src/utils/vector3.h:160-164) is std::hypot of three arguments
-__device__ inline double len3(const double* a) { return norm3d(a[0], a[1], a[2]); }
-__device__ inline double dot3(const double* a, const double* b) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; }
-// Vector3::cross (:212-219)
-__device__ inline void cross3(const double* a, const double* b, double* o)
-{
-  o[0] = +(a[1] * b[2] - a[2] * b[1]);
-  o[1] = -(a[0] * b[2] - a[2] * b[0]);
-  o[2] = +(a[0] * b[1] - a[1] * b[0]);
-}
-// Vector3::normalized (:150-158)
+// Vector3::normalized (src/utils/vector3.h:150-158)
 __device__ inline void normalized3(const double* a, double* o)
 {
   const double l = len3(a);
@@ -35,9 +27,9 @@ __device__ inline void normalized3(const double* a, double* o)
 }
 
 // DriftKineticEsirkepov::interpolate(E_p, B_p, gradB_p, rn, r0): E_p with the segment shape of (rn, r0)
-// (ImplicitEsirkepov::interpolate, implicit_esirkepov.cpp:71-90), B_p and gradB_p with Shape::setup(rn, 1.5,
-// spline_of_2nd_order) (src/utils/shape.cpp:31-41) and SimpleInterpolation's magnetic products (shape.h:65-72): one set
-// of weights, one pass over the nodes.  GRAD = false is the reference's gradB_g == nullptr: gradB_p = 0.
+// (segment_gather_E), B_p and gradB_p with Shape2::setup(rn) and SimpleInterpolation's magnetic products
+// (shape.h:65-72): one set of weights, one pass over the nodes.  GRAD = false is the reference's gradB_g == nullptr:
+// gradB_p = 0.
 template <bool GRAD>
 __device__ inline void dk_fields(const GridDev& g, const double* __restrict__ E, const double* __restrict__ B,
   const double* __restrict__ gB, const double* rn, const double* r0, double* Ep, double* Bp, double* gBp)
@@ -54,72 +46,27 @@ __device__ inline void dk_fields(const GridDev& g, const double* __restrict__ E,
     for (int a = 0; a < 3; ++a) { Ep[a] = nan; Bp[a] = nan; gBp[a] = GRAD ? nan : 0.0; }
     return;
   }
-  {
-    IEShape sh;
-    sh.setup(g, rn, r0);
-    Ep[0] = Ep[1] = Ep[2] = 0.0;
-#pragma unroll
-    for (int cx = 0; cx < 3; cx++) {
-      const int cy = (cx + 1) % 3, cz = (cx + 2) % 3;
-#pragma unroll
-      for (int i = 0; i < 2; i++)
-#pragma unroll
-        for (int j = 0; j < 3; j++)
-#pragma unroll
-          for (int k = 0; k < 3; k++) { // i[cx], i[cy], i[cz] of the reference's loop nest, m = its running index
-            int o[3];
-            o[cx] = i; o[cy] = j; o[cz] = k;
-            const int m = ((cx * 2 + i) * 3 + j) * 3 + k;
-            Ep[cx] += E[cx * g.cstride + ie_node(g, sh.start[0] + o[0], sh.start[1] + o[1], sh.start[2] + o[2])] * sh.cache[m];
-          }
-    }
-  }
+  IEShape seg;
+  seg.setup(g, rn, r0);
+  segment_gather_E(g, E, seg, Ep);
   Bp[0] = Bp[1] = Bp[2] = 0.0;
   gBp[0] = gBp[1] = gBp[2] = 0.0;
-  // x and y weights in registers, the z pair formed plane by plane: the plane loop stays rolled, which keeps the 96 loads
-  // of a plane in flight without holding all 384 of the footprint in registers
-  int st[3], sz[3];
-  double No[2][4], Sh[2][4], prz = 0.0;
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    const double pr = rn[a] / d[a];
-    st[a] = (int)round(pr - 1.5);
-    sz[a] = (int)floor(pr + 1.5) + 1 - st[a]; // 3 or 4
-    if (a == 2) { prz = pr; break; }
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      const double gx = (double)(st[a] + t);
-      No[a][t] = spline2_ref(pr - gx);
-      Sh[a][t] = spline2_ref(pr - (gx + 0.5));
+  Shape2 sh;
+  sh.setup(g, rn);
+  sh.nodes([&](int gx, int gy, int gz, double Noz, double Shz, double Noy, double Shy, double Nox, double Shx) {
+    const long o = ie_node(g, gx, gy, gz);
+    const double wx = Shz * Shy * Nox;
+    const double wy = Shz * Noy * Shx;
+    const double wz = Noz * Shy * Shx;
+    Bp[0] += B[o] * wx;
+    Bp[1] += B[g.cstride + o] * wy;
+    Bp[2] += B[2 * g.cstride + o] * wz;
+    if (GRAD) {
+      gBp[0] += gB[o] * wx;
+      gBp[1] += gB[g.cstride + o] * wy;
+      gBp[2] += gB[2 * g.cstride + o] * wz;
     }
-  }
-#pragma unroll 1
-  for (int kz = 0; kz < sz[2]; ++kz) {
-    const double gz = (double)(st[2] + kz);
-    const double Noz = spline2_ref(prz - gz), Shz = spline2_ref(prz - (gz + 0.5));
-#pragma unroll
-    for (int jy = 0; jy < 4; ++jy) {
-      if (jy < sz[1]) {
-#pragma unroll
-        for (int ix = 0; ix < 4; ++ix) {
-          if (ix < sz[0]) {
-            const long o = ie_node(g, st[0] + ix, st[1] + jy, st[2] + kz);
-            const double wx = Shz * Sh[1][jy] * No[0][ix];
-            const double wy = Shz * No[1][jy] * Sh[0][ix];
-            const double wz = Noz * Sh[1][jy] * Sh[0][ix];
-            Bp[0] += B[o] * wx;
-            Bp[1] += B[g.cstride + o] * wy;
-            Bp[2] += B[2 * g.cstride + o] * wz;
-            if (GRAD) {
-              gBp[0] += gB[o] * wx;
-              gBp[1] += gB[g.cstride + o] * wy;
-              gBp[2] += gB[2 * g.cstride + o] * wz;
-            }
-          }
-        }
-      }
-    }
-  }
+  });
 }
 
 // DriftKineticPush::get_Vd (drift_kinetic_push.cpp:111-119)

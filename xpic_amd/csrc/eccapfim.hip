@@ -14,6 +14,7 @@
 #include "common.h"
 #include "device_common.h"
 #include "ie_shape.h"
+#include "shape2.h"
 
 namespace xpic {
 
@@ -28,45 +29,19 @@ __global__ void __launch_bounds__(kBlock) k_ie_interpolate(GridDev g, const doub
   if (q >= n) return;
   const double rn[3] = {rn3[3 * q], rn3[3 * q + 1], rn3[3 * q + 2]}, r0[3] = {r03[3 * q], r03[3 * q + 1], r03[3 * q + 2]};
   // B: Shape::setup(midpoint, 1.5, spline_of_2nd_order) + SimpleInterpolation (magnetic products, shape.h:65-72)
-  double Bp[3] = {0, 0, 0};
-  {
-    const double d[3] = {g.dx, g.dy, g.dz};
-    int st[3], sz[3];
-    double No[3][4], Sh[3][4];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-      const double pr = 0.5 * (rn[a] + r0[a]) / d[a];
-      st[a] = (int)round(pr - 1.5);
-      sz[a] = (int)floor(pr + 1.5) + 1 - st[a];
-#pragma unroll
-      for (int t = 0; t < 4; ++t) {
-        const double gx = (double)(st[a] + t);
-        No[a][t] = spline2_ref(pr - gx);
-        Sh[a][t] = spline2_ref(pr - (gx + 0.5));
-      }
-    }
-    for (int kz = 0; kz < sz[2]; ++kz)
-      for (int jy = 0; jy < sz[1]; ++jy)
-        for (int ix = 0; ix < sz[0]; ++ix) {
-          const long o = ie_node(g, st[0] + ix, st[1] + jy, st[2] + kz);
-          Bp[0] += B[o] * (Sh[2][kz] * Sh[1][jy] * No[0][ix]);
-          Bp[1] += B[g.cstride + o] * (Sh[2][kz] * No[1][jy] * Sh[0][ix]);
-          Bp[2] += B[2 * g.cstride + o] * (No[2][kz] * Sh[1][jy] * Sh[0][ix]);
-        }
-  }
+  const double rm[3] = {0.5 * (rn[0] + r0[0]), 0.5 * (rn[1] + r0[1]), 0.5 * (rn[2] + r0[2])};
+  double Ep[3], Bp[3] = {0, 0, 0};
+  Shape2 mid;
+  mid.setup(g, rm);
+  mid.nodes([&](int gx, int gy, int gz, double Noz, double Shz, double Noy, double Shy, double Nox, double Shx) {
+    const long o = ie_node(g, gx, gy, gz);
+    Bp[0] += B[o] * (Shz * Shy * Nox);
+    Bp[1] += B[g.cstride + o] * (Shz * Noy * Shx);
+    Bp[2] += B[2 * g.cstride + o] * (Noz * Shy * Shx);
+  });
   IEShape sh;
   sh.setup(g, rn, r0);
-  double Ep[3] = {0, 0, 0};
-  int m = 0;
-#pragma unroll
-  for (int cx = 0; cx < 3; cx++) {
-    const int cy = (cx + 1) % 3, cz = (cx + 2) % 3;
-    int i[3];
-    for (i[cx] = 0; i[cx] < 2; i[cx]++)
-      for (i[cy] = 0; i[cy] < 3; i[cy]++)
-        for (i[cz] = 0; i[cz] < 3; i[cz]++)
-          Ep[cx] += E[cx * g.cstride + ie_node(g, sh.start[0] + i[0], sh.start[1] + i[1], sh.start[2] + i[2])] * sh.cache[m++];
-  }
+  segment_gather_E(g, E, sh, Ep);
 #pragma unroll
   for (int c = 0; c < 3; ++c) { Ep3[3 * q + c] = Ep[c]; Bp3[3 * q + c] = Bp[c]; }
 }
@@ -79,20 +54,11 @@ __global__ void __launch_bounds__(kBlock) k_ie_decompose(GridDev g, double* J, l
   const double rn[3] = {rn3[3 * q], rn3[3 * q + 1], rn3[3 * q + 2]}, r0[3] = {r03[3 * q], r03[3 * q + 1], r03[3 * q + 2]};
   IEShape sh;
   sh.setup(g, rn, r0);
-  int m = 0;
-#pragma unroll
-  for (int cx = 0; cx < 3; cx++) {
-    const int cy = (cx + 1) % 3, cz = (cx + 2) % 3;
-    const double av = alpha[q] * v3[3 * q + cx];
-    int i[3];
-    for (i[cx] = 0; i[cx] < 2; i[cx]++)
-      for (i[cy] = 0; i[cy] < 3; i[cy]++)
-        for (i[cz] = 0; i[cz] < 3; i[cz]++) {
-          const double w = av * sh.cache[m++];
-          if (w != 0.0)
-            unsafeAtomicAdd(&J[cx * g.cstride + ie_node(g, sh.start[0] + i[0], sh.start[1] + i[1], sh.start[2] + i[2])], w);
-        }
-  }
+  const double av[3] = {alpha[q] * v3[3 * q], alpha[q] * v3[3 * q + 1], alpha[q] * v3[3 * q + 2]};
+  segment_nodes(g, sh, [&](int cx, long o, double c) {
+    const double w = av[cx] * c;
+    if (w != 0.0) unsafeAtomicAdd(&J[cx * g.cstride + o], w);
+  });
 }
 
 __global__ void __launch_bounds__(kBlock) k_cell_traversal(GridDev g, long n, const double* end3, const double* start3,

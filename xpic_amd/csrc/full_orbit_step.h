@@ -1,9 +1,8 @@
 // full_orbit_step.h -- the device functions of full_orbit.hip: the gathers and one step of every scheme.  They are in a
 // header so that tools/full_orbit_host.cpp can compile the same text for the host and run it against the numpy
-// restatement (tests/full_orbit_ref.py) without a GPU.  Included after common.h, device_common.h and ie_shape.h, with
-// `#pragma clang fp contract(on)` in force: contraction per source expression only, so every caller rounds alike.
-//   Shape::setup(r, 1.5, spline_of_2nd_order)   src/utils/shape.cpp:31-41
-//   SimpleInterpolation, Shape::electric / magnetic   src/utils/shape.h:54-72
+// restatement (tests/full_orbit_ref.py) without a GPU.  Included with `#pragma clang fp contract(on)` in force:
+// contraction per source expression only, so every caller rounds alike; shape2.h (Shape2, segment_gather_E, len3 / dot3 /
+// cross3) comes in here, under that pragma.
 //   BorisPush                                   src/algorithms/boris_push.cpp:19-91
 //   process_<id>                                tests/boris_push/boris_push.h:20-198
 //   CrankNicolsonPush::process                  src/algorithms/crank_nicolson_push.cpp:31-71
@@ -11,6 +10,8 @@
 // A lane whose |B_p| is exactly 0 keeps its v in update_vM / vB / vC1 / vC2: the reference's update_v_impl forms
 // v.parallel_to(B_p.normalized()) there, which divides by zero.
 #pragma once
+
+#include "shape2.h"
 
 namespace xpic {
 
@@ -30,34 +31,15 @@ __device__ inline void fo_store(double* __restrict__ s, long n, long q, const FO
   s[3 * n + q] = p.p[0]; s[4 * n + q] = p.p[1]; s[5 * n + q] = p.p[2];
 }
 
-// Vector3::length (src/utils/vector3.h:160-164) is std::hypot of three arguments
-__device__ inline double fo_len3(const double* a)
-{
-#ifdef XPIC_FO_HOST
-  return std::hypot(a[0], a[1], a[2]);
-#else
-  return norm3d(a[0], a[1], a[2]);
-#endif
-}
-__device__ inline double fo_dot3(const double* a, const double* b) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; }
-// Vector3::cross (:212-219)
-__device__ inline void fo_cross3(const double* a, const double* b, double* o)
-{
-  o[0] = +(a[1] * b[2] - a[2] * b[1]);
-  o[1] = -(a[0] * b[2] - a[2] * b[0]);
-  o[2] = +(a[0] * b[1] - a[1] * b[0]);
-}
-
 // a position that is not a number, or further out than an int counts cells, has no node: no index is formed from it
 __device__ inline bool fo_in_range(const GridDev& g, const double* r)
 {
   return fabs(r[0]) <= 1e9 * g.dx && fabs(r[1]) <= 1e9 * g.dy && fabs(r[2]) <= 1e9 * g.dz;
 }
 
-// E_p and B_p at r: one Shape::setup(r), one pass over its nodes with the electric products (E_x: No_z No_y Sh_x,
+// E_p and B_p at r: one Shape2::setup(r), one pass over its nodes with the electric products (E_x: No_z No_y Sh_x,
 // E_y: No_z Sh_y No_x, E_z: Sh_z No_y No_x) and the magnetic ones (B_x: Sh_z Sh_y No_x, B_y: Sh_z No_y Sh_x,
-// B_z: No_z Sh_y Sh_x).  WITH_E = false: the magnetic half only (Ep untouched).  The x and y weights stay in registers,
-// the z pair is formed plane by plane and the plane loop stays rolled (at most 4 trips, 16 nodes each).
+// B_z: No_z Sh_y Sh_x).  WITH_E = false: the magnetic half only (Ep untouched).
 template <bool WITH_E>
 __device__ inline void fo_gather(const GridDev& g, const double* __restrict__ E, const double* __restrict__ B,
   const double* r, double* Ep, double* Bp)
@@ -71,53 +53,25 @@ __device__ inline void fo_gather(const GridDev& g, const double* __restrict__ E,
     }
     return;
   }
-  const double d[3] = {g.dx, g.dy, g.dz};
   if (WITH_E) Ep[0] = Ep[1] = Ep[2] = 0.0;
   Bp[0] = Bp[1] = Bp[2] = 0.0;
-  int st[3], sz[3];
-  double No[2][4], Sh[2][4], prz = 0.0;
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    const double pr = r[a] / d[a];
-    st[a] = (int)round(pr - 1.5);
-    sz[a] = (int)floor(pr + 1.5) + 1 - st[a]; // 3 or 4
-    if (a == 2) { prz = pr; break; }
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      const double gx = (double)(st[a] + t);
-      No[a][t] = spline2_ref(pr - gx);
-      Sh[a][t] = spline2_ref(pr - (gx + 0.5));
+  Shape2 sh;
+  sh.setup(g, r);
+  sh.nodes([&](int gx, int gy, int gz, double Noz, double Shz, double Noy, double Shy, double Nox, double Shx) {
+    const long o = ie_node(g, gx, gy, gz);
+    if (WITH_E) {
+      Ep[0] += E[o] * (Noz * Noy * Shx);
+      Ep[1] += E[g.cstride + o] * (Noz * Shy * Nox);
+      Ep[2] += E[2 * g.cstride + o] * (Shz * Noy * Nox);
     }
-  }
-  const int nz = sz[2] < 4 ? sz[2] : 4; // 3 or 4 by construction; the bound does not depend on that
-#pragma unroll 1
-  for (int kz = 0; kz < nz; ++kz) {
-    const double gz = (double)(st[2] + kz);
-    const double Noz = spline2_ref(prz - gz), Shz = spline2_ref(prz - (gz + 0.5));
-#pragma unroll
-    for (int jy = 0; jy < 4; ++jy) {
-      if (jy < sz[1]) {
-#pragma unroll
-        for (int ix = 0; ix < 4; ++ix) {
-          if (ix < sz[0]) {
-            const long o = ie_node(g, st[0] + ix, st[1] + jy, st[2] + kz);
-            if (WITH_E) {
-              Ep[0] += E[o] * (Noz * No[1][jy] * Sh[0][ix]);
-              Ep[1] += E[g.cstride + o] * (Noz * Sh[1][jy] * No[0][ix]);
-              Ep[2] += E[2 * g.cstride + o] * (Shz * No[1][jy] * No[0][ix]);
-            }
-            Bp[0] += B[o] * (Shz * Sh[1][jy] * No[0][ix]);
-            Bp[1] += B[g.cstride + o] * (Shz * No[1][jy] * Sh[0][ix]);
-            Bp[2] += B[2 * g.cstride + o] * (Noz * Sh[1][jy] * Sh[0][ix]);
-          }
-        }
-      }
-    }
-  }
+    Bp[0] += B[o] * (Shz * Shy * Nox);
+    Bp[1] += B[g.cstride + o] * (Shz * Noy * Shx);
+    Bp[2] += B[2 * g.cstride + o] * (Noz * Shy * Shx);
+  });
 }
 
 // ImplicitEsirkepov::interpolate(E_p, B_p, rn, r0): B_p with Shape(0.5 (rn + r0)) and the magnetic products, E_p with the
-// 54 weights of the segment (ie_shape.h), in the reference's order of the running index
+// 54 weights of the segment (ie_shape.h; segment_gather_E)
 __device__ inline void fo_gather_segment(const GridDev& g, const double* __restrict__ E, const double* __restrict__ B,
   const double* rn, const double* r0, double* Ep, double* Bp)
 {
@@ -131,22 +85,7 @@ __device__ inline void fo_gather_segment(const GridDev& g, const double* __restr
   fo_gather<false>(g, E, B, rm, Ep, Bp);
   IEShape sh;
   sh.setup(g, rn, r0);
-  Ep[0] = Ep[1] = Ep[2] = 0.0;
-#pragma unroll
-  for (int cx = 0; cx < 3; cx++) {
-    const int cy = (cx + 1) % 3, cz = (cx + 2) % 3;
-#pragma unroll
-    for (int i = 0; i < 2; i++)
-#pragma unroll
-      for (int j = 0; j < 3; j++)
-#pragma unroll
-        for (int k = 0; k < 3; k++) { // i[cx], i[cy], i[cz] of the reference's loop nest, m = its running index
-          int o[3];
-          o[cx] = i; o[cy] = j; o[cz] = k;
-          const int m = ((cx * 2 + i) * 3 + j) * 3 + k;
-          Ep[cx] += E[cx * g.cstride + ie_node(g, sh.start[0] + o[0], sh.start[1] + o[1], sh.start[2] + o[2])] * sh.cache[m];
-        }
-  }
+  segment_gather_E(g, E, sh, Ep);
 }
 
 // BorisPush::update_r (boris_push.cpp:19-22)
@@ -161,7 +100,7 @@ enum { FO_VM = 0, FO_VB = 1, FO_VC1 = 2, FO_VC2 = 3, FO_VEB = 4 };
 // update_vM / vB / vC1 / vC2 (boris_push.cpp:24-46): the angle pair of get_theta_* (:60-83), then update_v_impl (:85-91)
 __device__ inline void fo_update_v_magnetic(int kind, double dt, double qm, const double* Bp, double* v)
 {
-  const double lenB = fo_len3(Bp);
+  const double lenB = len3(Bp);
   const double theta = (-1.0) * qm * lenB * dt;
   double first, second; // the AnglePair: "sine" and "cosine"
   if (kind == FO_VM) { first = sin(theta); second = cos(theta); }
@@ -182,13 +121,13 @@ __device__ inline void fo_update_v_magnetic(int kind, double dt, double qm, cons
   double b[3], vp[3], vt[3], bxvt[3];
 #pragma unroll
   for (int c = 0; c < 3; ++c) b[c] = Bp[c] / lenB; // Vector3::normalized (vector3.h:150-158)
-  const double vb = fo_dot3(v, b), bb = fo_dot3(b, b);
+  const double vb = dot3(v, b), bb = dot3(b, b);
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
     vp[c] = (vb * b[c]) / bb; // parallel_to (:195-199)
     vt[c] = v[c] - vp[c];     // transverse_to (:201-205)
   }
-  fo_cross3(b, vt, bxvt);
+  cross3(b, vt, bxvt);
 #pragma unroll
   for (int c = 0; c < 3; ++c) v[c] = vp[c] + second * vt[c] + first * bxvt[c];
 }
@@ -204,9 +143,9 @@ __device__ inline void fo_update_vEB(double dt, double qm, const double* Ep, con
     b[c] = -alpha * Bp[c];
     w[c] = v[c] + 0.5 * a[c];
   }
-  fo_cross3(b, w, bw);
-  fo_cross3(b, bw, bbw);
-  const double den = 1.0 + 0.25 * fo_dot3(b, b);
+  cross3(b, w, bw);
+  cross3(b, bw, bbw);
+  const double den = 1.0 + 0.25 * dot3(b, b);
 #pragma unroll
   for (int c = 0; c < 3; ++c) v[c] += a[c] + (bw[c] + 0.5 * bbw[c]) / den;
 }
@@ -280,10 +219,10 @@ __device__ inline double fo_cn_residue(double dt, double qm, const FOPoint& pn, 
   const double* Ep, const double* Bp)
 {
   double vxB[3], res[3];
-  fo_cross3(vh, Bp, vxB);
+  cross3(vh, Bp, vxB);
 #pragma unroll
   for (int c = 0; c < 3; ++c) res[c] = (pn.p[c] - p0.p[c]) - dt * qm * (Ep[c] + vxB[c]);
-  return fo_len3(res);
+  return len3(res);
 }
 
 // CrankNicolsonPush::process(dt, pn, p0) (:31-71), statement by statement; pn enters as the initial guess.  Returns the
@@ -311,8 +250,8 @@ __device__ inline int fo_cn_process(const SRC& src, double qm, double dt, double
       b[c] = alpha * Bp[c];
       w[c] = p0.p[c] + a[c];
     }
-    fo_cross3(w, b, wxb);
-    const double wb = fo_dot3(w, b), den = (1.0 + fo_dot3(b, b));
+    cross3(w, b, wxb);
+    const double wb = dot3(w, b), den = (1.0 + dot3(b, b));
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
       vh[c] = (w[c] + wxb[c] + b[c] * wb) / den;

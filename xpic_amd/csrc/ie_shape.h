@@ -1,5 +1,6 @@
 // ie_shape.h -- the segment shape of ImplicitEsirkepov (src/algorithms/implicit_esirkepov.cpp:11-57) and the node
-// numbering of its gathers, shared by eccapfim.hip and drift_kinetic.hip.
+// numbering of its gathers, shared by eccapfim.hip and the tracers.  shape2.h walks its 54 weights (segment_nodes,
+// segment_gather_E).
 #pragma once
 
 #include "common.h"

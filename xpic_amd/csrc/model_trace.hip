@@ -151,8 +151,8 @@ __device__ inline void ex3_sums(const TimedModelSource& src, double qm, double d
 #pragma unroll
   for (int c = 0; c < 3; ++c) vh[c] = 0.5 * (pn.p[c] + p0.p[c]);
   src.segment(pn.r, p0.r, Es, Bs);
-  sum[0] += 0.5 * (fo_dot3(pn.p, pn.p) - fo_dot3(p0.p, p0.p)) - qm * dt * fo_dot3(vh, Es);
-  const double vb = fo_dot3(vh, Bs), bb = fo_dot3(Bs, Bs);
+  sum[0] += 0.5 * (dot3(pn.p, pn.p) - dot3(p0.p, p0.p)) - qm * dt * dot3(vh, Es);
+  const double vb = dot3(vh, Bs), bb = dot3(Bs, Bs);
 #pragma unroll
   for (int c = 0; c < 3; ++c) sum[1 + c] += vh[c] - (vb * Bs[c]) / bb;
 }

@@ -7,6 +7,7 @@
 #include "batch.h"
 #include "common.h"
 #include "device_common.h"
+#include "shape2.h"
 
 #ifndef XPIC_BUCKET_CAP
 #define XPIC_BUCKET_CAP 128 // source indices a cell's bucket holds (deferred scatter); a fuller cell sends the step through k_index
@@ -521,7 +522,7 @@ __global__ void __launch_bounds__(kBlock) k_scale_v(SortDev s, int64_t n, double
 }
 
 // ParticlesChargeDensity::collect (src/diagnostics/charge_conservation.cpp:34-97): 3 x 3 x 3 nodes from
-// ceil(r/dx - 1.5), weight spline2_ref in x, y and z, value q * n/Np.  Diagnostic, off the hot path: plain atomics.
+// deposit_weights3 (shape2.h), value q * n/Np.  Diagnostic, off the hot path: plain atomics.
 __global__ void __launch_bounds__(kBlock) k_charge_density(GridDev g, SortDev s, int64_t n, double qn, double* rho)
 {
   const int64_t p = (int64_t)blockIdx.x * kBlock + threadIdx.x;
@@ -529,12 +530,7 @@ __global__ void __launch_bounds__(kBlock) k_charge_density(GridDev g, SortDev s,
   const double pr[3] = {s.r[0][p] / g.dx, s.r[1][p] / g.dy, s.r[2][p] / g.dz};
   int st[3];
   double w[3][3];
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    st[a] = (int)ceil(pr[a] - 1.5);
-#pragma unroll
-    for (int t = 0; t < 3; ++t) w[a][t] = spline2_ref(pr[a] - (double)(st[a] + t));
-  }
+  deposit_weights3(pr, st, w);
   st[2] -= g.z0;
 #pragma unroll
   for (int k = 0; k < 3; ++k)
@@ -557,38 +553,22 @@ __global__ void __launch_bounds__(kBlock) k_momentum(GridDev g, SortDev s, int64
 {
   double a[6] = {0, 0, 0, 0, 0, 0};
   const int64_t stride = (int64_t)gridDim.x * kBlock;
-  const double dd[3] = {g.dx, g.dy, g.dz};
   for (int64_t p = (int64_t)blockIdx.x * kBlock + threadIdx.x; p < n; p += stride) {
     const double r[3] = {s.r[0][p], s.r[1][p], s.r[2][p]};
     const double v[3] = {s.v[0][p], s.v[1][p], s.v[2][p]};
-    int st[3], sz[3];
-    double No[3][4], Sh[3][4];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      const double pr = r[c] / dd[c];
-      st[c] = (int)round(pr - 1.5);              // Shape::make_start
-      sz[c] = (int)floor(pr + 1.5) + 1 - st[c];  // Shape::make_end
-#pragma unroll
-      for (int t = 0; t < 4; ++t) {
-        const double gx = (double)(st[c] + t);
-        No[c][t] = spline2_ref(pr - gx);
-        Sh[c][t] = spline2_ref(pr - (gx + 0.5));
-      }
-    }
-    st[2] -= g.z0;
-    for (int kz = 0; kz < sz[2]; ++kz)
-      for (int jy = 0; jy < sz[1]; ++jy)
-        for (int ix = 0; ix < sz[0]; ++ix) {
-          const long node = g.nodew(st[0] + ix, st[1] + jy, st[2] + kz);
-          const double ns = No[2][kz] * No[1][jy] * No[0][ix];
-          a[0] += m * v[0] * ns;
-          a[1] += m * v[1] * ns;
-          a[2] += m * v[2] * ns;
-          // Shape::electric (shape.h:54-61)
-          a[3] += q * E[node] * (No[2][kz] * No[1][jy] * Sh[0][ix]);
-          a[4] += q * E[g.cstride + node] * (No[2][kz] * Sh[1][jy] * No[0][ix]);
-          a[5] += q * E[2 * g.cstride + node] * (Sh[2][kz] * No[1][jy] * No[0][ix]);
-        }
+    Shape2 sh;
+    sh.setup(g, r);
+    sh.nodes([&](int gx, int gy, int gz, double Noz, double Shz, double Noy, double Shy, double Nox, double Shx) {
+      const long node = g.nodew(gx, gy, gz - g.z0);
+      const double ns = Noz * Noy * Nox;
+      a[0] += m * v[0] * ns;
+      a[1] += m * v[1] * ns;
+      a[2] += m * v[2] * ns;
+      // Shape::electric (shape.h:54-61)
+      a[3] += q * E[node] * (Noz * Noy * Shx);
+      a[4] += q * E[g.cstride + node] * (Noz * Shy * Nox);
+      a[5] += q * E[2 * g.cstride + node] * (Shz * Noy * Nox);
+    });
   }
   block_reduce_store<6, kBlock>(a, partial, nblocks, blockIdx.x);
 }
