@@ -16,7 +16,8 @@
  *                      right-hand side, and the mean taken out is the uniform neutralising background.  It is returned;
  *     res            = D F - rho~.
  * Clean: solve D G phi = res for the mean-free phi by unpreconditioned conjugate gradients from phi = 0, then
- * F <- F - G phi.  rot(+) F and the sum of each component of F do not change.
+ * F <- F - G phi.  rot(+) F and the sum of each component of F do not change.  (A context may choose the direct solve of
+ * xpic_poisson.h instead of CG; `iterations` then counts its applications.  CG is the default.)
  * Stopping rule: |r|_2 <= max(rtol |rho~|_2, atol) -- relative to the charge, not to the entering residual.  When CG's
  * recurrence meets it the residual res - D G phi is formed explicitly once and the iteration goes on from it if that one
  * does not.  An entering residual that meets the rule: 0 iterations, F is not written.  No convergence within maxit

@@ -964,4 +964,6 @@ int xpic_probe_copy_bandwidth(xpic_ctx* ctx, int64_t bytes, int reps, double* by
 #include "xpic_gauss.h"
 /* ---- the electrostatic scheme XPIC_ES: Boris push, fused charge deposit, Poisson solve */
 #include "xpic_es.h"
+/* ---- the direct Poisson solve for the cleans and the XPIC_ES step: a separable Hartley transform */
+#include "xpic_poisson.h"
 #endif

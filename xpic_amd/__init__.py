@@ -167,7 +167,7 @@ _lib = None
 
 def load_library():
     """Loads libxpic_hip.so and types every entry point from PROTOTYPES, LOAD_PROTOTYPES, TRACER_PROTOTYPES,
-    TRACER_MOMENT_PROTOTYPES, FIELD_LINE_PROTOTYPES, GAUSS_PROTOTYPES and ES_PROTOTYPES; raises if it has not been built (no fallback path exists).  The xpic_debug_*_stamps symbols of experiment builds are not in the header and stay untyped."""
+    TRACER_MOMENT_PROTOTYPES, FIELD_LINE_PROTOTYPES, GAUSS_PROTOTYPES, ES_PROTOTYPES and POISSON_PROTOTYPES; raises if it has not been built (no fallback path exists).  The xpic_debug_*_stamps symbols of experiment builds are not in the header and stay untyped."""
     global _lib
     if _lib is not None:
         return _lib
@@ -176,7 +176,7 @@ def load_library():
                         "xpic_amd has no CPU fallback")
     L = C.CDLL(LIB_PATH)
     for name, (ret, args) in dict(PROTOTYPES, **LOAD_PROTOTYPES, **TRACER_PROTOTYPES, **TRACER_MOMENT_PROTOTYPES,
-                                   **FIELD_LINE_PROTOTYPES, **GAUSS_PROTOTYPES, **ES_PROTOTYPES).items():
+                                   **FIELD_LINE_PROTOTYPES, **GAUSS_PROTOTYPES, **ES_PROTOTYPES, **POISSON_PROTOTYPES).items():
         f = getattr(L, name)
         f.restype, f.argtypes = CTYPES[ret], [CTYPES[a] for a in args]
     if L.xpic_version() & VERSION_EXPERIMENT_BIT and os.environ.get("XPIC_ALLOW_EXPERIMENT") != "1":
@@ -509,7 +509,34 @@ class EsCommands:
         return rho
 
 
-class Context(LoadCommands, TracerCommands, FieldLineCommands, GaussCommands, EsCommands):
+class PoissonCommands:
+    """The direct Poisson solve (include/xpic_poisson.h; the reference has none), as methods of Context: which solve the
+    cleans and the "es" step take, and one application of the transform solve alone."""
+
+    def set_poisson_solver(self, kind):
+        """"cg" (the default of every context) or "direct": the separable Hartley-transform solve with iterative refinement,
+        on contexts without ghost planes and with extents up to POISSON_MAX_EXTENT; a clean's and a step's iterations then
+        count its applications"""
+        if kind not in POISSON_SOLVERS and not isinstance(kind, int):
+            raise XpicError("set_poisson_solver: %r is none of %s" % (kind, sorted(POISSON_SOLVERS)))
+        self._ck(self.L.xpic_set_poisson_solver(self.h, int(POISSON_SOLVERS.get(kind, kind))))
+
+    @property
+    def poisson_solver(self):
+        kind = C.c_int()
+        self._ck(self.L.xpic_get_poisson_solver(self.h, C.byref(kind)))
+        return {v: k for k, v in POISSON_SOLVERS.items()}[kind.value]
+
+    def poisson_apply(self, rhs):
+        """one application of the transform solve to rhs - mean(rhs) [nz][ny][nx] -> the mean-free phi with D G phi = that;
+        no refinement, whatever poisson_solver is"""
+        rhs = np.ascontiguousarray(rhs, dtype=np.float64).reshape(self.nzl, self.n[1], self.n[0])
+        phi = np.zeros_like(rhs)
+        self._ck(self.L.xpic_poisson_apply(self.h, _dp(rhs), _dp(phi)))
+        return phi
+
+
+class Context(LoadCommands, TracerCommands, FieldLineCommands, GaussCommands, EsCommands, PoissonCommands):
     """One z-slab context = one `interfaces::Simulation` backend instance."""
 
     def __init__(self, scheme, n, d, dt, device=0, rank=0, nranks=1, self_ring=False):

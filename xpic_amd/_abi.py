@@ -358,3 +358,13 @@ ES_PROTOTYPES = {
     "xpic_es_push": ("int", ["xpic_ctx*", "int", "double*"]),
 }
 ES_RTOL, ES_ATOL, ES_MAXIT = 1e-10, 1e-14, 10000  # the tolerances an "es" context is created with (xpic_es.h)
+
+# the entry points of include/xpic_poisson.h (the direct Poisson solve and the choice between it and CG), typed by
+# load_library() as PROTOTYPES' are; tests/test_abi_poisson.py holds them to that header
+POISSON_PROTOTYPES = {
+    "xpic_set_poisson_solver": ("int", ["xpic_ctx*", "int"]),
+    "xpic_get_poisson_solver": ("int", ["xpic_ctx*", "int*"]),
+    "xpic_poisson_apply": ("int", ["xpic_ctx*", "const double*", "double*"]),
+}
+POISSON_SOLVERS = {"cg": 0, "direct": 1}  # enum xpic_poisson_solver
+POISSON_MAX_EXTENT = 1024  # XPIC_POISSON_MAX_EXTENT

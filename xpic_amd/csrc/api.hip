@@ -439,6 +439,7 @@ int xpic_destroy(xpic_ctx* ctx)
   background_free(ctx);
   tracers_free(ctx);
   gauss_free(ctx);
+  poisson_free(ctx);
   (void)hipFree(ctx->es_rho);
   (void)hipFree(ctx->abar32); (void)hipFree(ctx->abar_work); (void)hipFree(ctx->abar_r);
   (void)hipFree(ctx->lrow_buf[0]); (void)hipFree(ctx->lrow_buf[1]);

@@ -270,6 +270,11 @@ struct xpic_ctx {
   double gauss_rtol = 0, gauss_atol = 0;
   int64_t steps_done = 0; // calls of xpic_step
   double gauss_info[6] = {0, 0, 0, 0, 0, 0};
+  // poisson.hip: which solve the cleans take (enum xpic_poisson_solver; CG unless xpic_set_poisson_solver says otherwise), and
+  // the direct solve's tables, made by its first use: the Hartley matrix of each axis (equal extents share one) and lam
+  int poisson_kind = XPIC_POISSON_CG;
+  double* poisson_H[3] = {nullptr, nullptr, nullptr};
+  double* poisson_lam[3] = {nullptr, nullptr, nullptr};
   // es.hip: the electrostatic step's charge accumulator (a stored vector whose component 0 is rho: the halo exchange adds whole
   // vectors), made with an XPIC_ES context; null on every other scheme
   double* es_rho = nullptr;
@@ -425,6 +430,13 @@ int gauss_reserve(xpic_ctx* c); // the solve's vectors, made now (an XPIC_ES con
 // the clean of XPIC_E with a charge it is handed (component 0 of a stored vector, ghost planes already added; the background
 // and the mean are dealt with here) instead of a deposit of its own: the electrostatic step's field solve
 int gauss_clean_given(xpic_ctx* c, const double* rho_vec, double rtol, double atol, int maxit, int* iterations);
+
+// poisson.hip (include/xpic_poisson.h; an extension: the reference has no such solver): one application of the separable
+// Hartley-transform solve of D G phi = rhs on four distinct scalar planes (out = or += the mean-free phi; w0, w1 overwritten);
+// the refusals of a context it cannot serve (ghost planes, an extent above the cap); frees the tables (xpic_destroy)
+int poisson_check(const xpic_ctx* c);
+int poisson_transform_solve(xpic_ctx* c, const double* rhs, double* w0, double* w1, double* out, bool add);
+void poisson_free(xpic_ctx* c);
 
 // es.hip: the electrostatic scheme's particle phase of one sort -- gather at r, kick, full move, deposit of the new position
 // into component 0 of rho_vec (added to what is there; ghost planes included, the caller adds them to their owners)

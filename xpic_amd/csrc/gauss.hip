@@ -5,6 +5,8 @@
 // component's planes: a scalar lives as one component of a stored vector (planes p, r, Ap of one, phi, rho, res of a
 // second), and no kernel here reads more than the planes it names.  One CG iteration moves 11 scalar vectors, as
 // krylov.hip's CG on matM moves 11 3-vectors: k_lap_dot (2), k_gauss_update (6), k_gauss_dir (3), two small reductions.
+// poisson_direct is the other solve (include/xpic_poisson.h): poisson.hip's transform solve with iterative refinement, on
+// the planes p and Ap as its work planes; the entry points of that header stand at the end of this file.
 #include <cmath>
 
 #include "common.h"
@@ -41,6 +43,14 @@ __global__ void __launch_bounds__(kBlock) k_gauss_acc(GridDev g, const double* _
     else if (MODE == 1) dst[off + i] = src[off + i];
     else dst[off + i] += src[off + i];
   }
+}
+
+// dst = src - shift on the owned nodes of one component
+__global__ void __launch_bounds__(kBlock) k_gauss_shift(GridDev g, const double* __restrict__ src, double shift, double* __restrict__ dst)
+{
+  const long off = (long)g.G * g.plane;
+  const long stride = (long)gridDim.x * kBlock;
+  for (long i = (long)blockIdx.x * kBlock + threadIdx.x; i < g.nown; i += stride) dst[off + i] = src[off + i] - shift;
 }
 
 // partial[blk] = sum (rho - shift)   (shift = 0: the plain sum, bit for bit)
@@ -302,6 +312,39 @@ int poisson_cg(xpic_ctx* c, double rr, double tol, int maxit, int* its_out, bool
   return 0;
 }
 
+// The direct path (poisson.hip; XPIC_POISSON_DIRECT), poisson_cg's contract: phi from 0 until |r|_2 <= tol, phi's ghost
+// planes filled.  One application of the transform solve to r is added to phi and r = res - D G phi is formed explicitly;
+// a residual above the tolerance is solved for again (iterative refinement).  its counts the applications.  Not converged:
+// maxit applications, or one that did not halve the residual it was given (what rounding leaves is reached, or not a number).
+int poisson_direct(xpic_ctx* c, double rr, double tol, int maxit, int* its_out, bool* converged, double* rnorm)
+{
+  const GridDev& g = c->g;
+  double *p = plane_of(c, kP), *r = plane_of(c, kR), *Ap = plane_of(c, kAp), *phi = plane_of(c, kPhi), *res = plane_of(c, kRes);
+  XPIC_CALL(acc_plane<1>(c, res, r));
+  const unsigned sblocks = red_blocks(g, 1);
+  const long off = (long)g.G * g.plane; // (0: the direct path runs on contexts without ghost planes only)
+  int its = 0;
+  double rn = std::sqrt(rr);
+  *converged = false;
+  while (its < maxit) {
+    XPIC_CALL(poisson_transform_solve(c, r + off, p + off, Ap + off, phi + off, its > 0));
+    ++its;
+    XPIC_CALL(halo_fill(c, vector_of(c, kPhi), 1));
+    double rr1;
+    hipLaunchKernelGGL(k_lap_residual, dim3(sblocks), dim3(kBlock), 0, c->stream, g, phi, res, r, c->red_partial);
+    XPIC_HIP(hipGetLastError());
+    XPIC_CALL(reduce_to_host(c, 1, (int)sblocks, 1, true, &rr1));
+    const double rn1 = std::sqrt(rr1);
+    const bool halved = rn1 <= 0.5 * rn; // (false for a NaN)
+    rn = rn1;
+    if (rn1 <= tol) { *converged = true; break; }
+    if (!halved) break;
+  }
+  *its_out = its;
+  *rnorm = rn;
+  return 0;
+}
+
 int gauss_clean(xpic_ctx* c, int field, double rtol, double atol, int maxit, double* phi_zyx, int* iterations, double* out4,
   const double* rho_given = nullptr)
 {
@@ -318,7 +361,8 @@ int gauss_clean(xpic_ctx* c, int field, double rtol, double atol, int maxit, dou
   else {
     bool converged;
     double rn;
-    XPIC_CALL(poisson_cg(c, o3[1], tol, maxit, &its, &converged, &rn));
+    if (c->poisson_kind == XPIC_POISSON_DIRECT) XPIC_CALL(poisson_direct(c, o3[1], tol, maxit, &its, &converged, &rn));
+    else XPIC_CALL(poisson_cg(c, o3[1], tol, maxit, &its, &converged, &rn));
     if (!converged) {
       set_error("gauss clean did not converge: " + std::to_string(its) + " iterations, |r| = " + std::to_string(rn) +
         ", tolerance " + std::to_string(tol));
@@ -442,6 +486,50 @@ int xpic_gauss_info(xpic_ctx* ctx, double* out6)
   XPIC_CHECK(out6, "null argument");
   for (int i = 0; i < 6; ++i) out6[i] = ctx->gauss_info[i];
   return 0;
+}
+
+// ---- include/xpic_poisson.h
+int xpic_set_poisson_solver(xpic_ctx* ctx, int kind)
+{
+  XPIC_CHECK(ctx != nullptr, "null context");
+  XPIC_CHECK(kind == XPIC_POISSON_CG || kind == XPIC_POISSON_DIRECT, "poisson: unknown solver kind");
+  if (kind == XPIC_POISSON_DIRECT) XPIC_CALL(poisson_check(ctx));
+  ctx->poisson_kind = kind;
+  return 0;
+}
+
+int xpic_get_poisson_solver(xpic_ctx* ctx, int* kind)
+{
+  XPIC_CHECK(ctx != nullptr, "null context");
+  XPIC_CHECK(kind, "null argument");
+  *kind = ctx->poisson_kind;
+  return 0;
+}
+
+int xpic_poisson_apply(xpic_ctx* ctx, const double* rhs_zyx, double* phi_zyx)
+{
+  XPIC_CHECK(ctx != nullptr, "null context");
+  XPIC_CHECK(rhs_zyx && phi_zyx, "null argument");
+  XPIC_CALL(poisson_check(ctx));
+  XPIC_CALL(gauss_alloc(ctx));
+  const GridDev& g = ctx->g;
+  double *res = plane_of(ctx, kRes), *r = plane_of(ctx, kR);
+  XPIC_HIP(hipMemcpyAsync(res, rhs_zyx, sizeof(double) * g.nown, hipMemcpyHostToDevice, ctx->stream));
+  // the mean in two passes (charge_mean's refinement), taken out before the transform sees the data
+  const unsigned blocks = red_blocks(g, 4);
+  double mean = 0.0;
+  for (int pass = 0; pass < 2; ++pass) {
+    hipLaunchKernelGGL(k_gauss_sum, dim3(blocks), dim3(kBlock), 0, ctx->stream, g, res, mean, ctx->red_partial);
+    XPIC_HIP(hipGetLastError());
+    double sum;
+    XPIC_CALL(reduce_to_host(ctx, 1, (int)blocks, 1, true, &sum));
+    XPIC_CHECK(std::isfinite(sum), "poisson: the right-hand side is not finite");
+    mean += sum / (double)g.nown;
+  }
+  hipLaunchKernelGGL(k_gauss_shift, dim3(blocks), dim3(kBlock), 0, ctx->stream, g, res, mean, r);
+  XPIC_HIP(hipGetLastError());
+  XPIC_CALL(poisson_transform_solve(ctx, r, plane_of(ctx, kP), plane_of(ctx, kAp), plane_of(ctx, kPhi), false));
+  return scalar_to_host(ctx, plane_of(ctx, kPhi), phi_zyx);
 }
 
 }  // extern "C"

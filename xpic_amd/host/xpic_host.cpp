@@ -1526,6 +1526,11 @@ GaussLaw::GaussLaw(interfaces::Simulation& simulation, const Configuration::json
   if (info.contains("rtol")) rtol_ = info.at("rtol").as_double();
   if (info.contains("atol")) atol_ = info.at("atol").as_double();
   if (info.contains("maxit")) maxit_ = info.at("maxit").as_int();
+  if (info.contains("solver")) {
+    const std::string solver = info.at("solver").as_string();
+    if (solver != "cg" && solver != "direct") throw std::runtime_error("GaussLaw: \"solver\" is \"cg\" or \"direct\"");
+    solver_ = solver == "direct" ? XPIC_POISSON_DIRECT : XPIC_POISSON_CG;
+  }
   if (info.contains("background") && info.at("background").as_string() != "neutralize")
     throw std::runtime_error("GaussLaw: \"background\" is \"neutralize\" or absent");
   if (every_ < 0) throw std::runtime_error("GaussLaw: \"every\" must be >= 0");
@@ -1543,6 +1548,7 @@ GaussLaw::GaussLaw(interfaces::Simulation& simulation)
 PetscErrorCode GaussLaw::start()
 {
   for (auto& sort : simulation.particles_) XCALL(sort->flush());
+  if (solver_ >= 0) HIPCALL(xpic_set_poisson_solver(simulation.ctx, solver_)); // (no key: the context's default, CG)
   if (at_start_) {
     int its = 0;
     double o4[4];

@@ -387,7 +387,9 @@ private:
 };
 
 // The optional top-level "GaussLaw" object (an extension: the reference has no Gauss-law cleaner; include/xpic_gauss.h):
-//   {"at_start": bool, "every": int, "rtol": 1e-10, "atol": 0, "maxit": 10000, "background": "neutralize"}
+//   {"at_start": bool, "every": int, "rtol": 1e-10, "atol": 0, "maxit": 10000, "background": "neutralize", "solver": "cg"}
+// solver: "cg" or "direct" (include/xpic_poisson.h: the Hartley-transform solve, whose iterations count its applications), for
+// the start clean, the riding clean and an electrostatic simulation's step alike; without the key nothing is set.
 // at_start: the run's initial E is cleaned once the presets have loaded the particles (the electrostatic start); every k > 0:
 // xpic_step cleans E on every k-th step.  "background": "neutralize" (the default, and the only kind) names what the clean
 // does with a net charge: its mean is taken out as a uniform neutralising background and reported.  One row per diagnosed
@@ -403,7 +405,7 @@ public:
 private:
   interfaces::Simulation& simulation;
   bool at_start_ = false;
-  int every_ = 0, maxit_ = 10000;
+  int every_ = 0, maxit_ = 10000, solver_ = -1;
   double rtol_ = 1e-10, atol_ = 0.0, cleans_seen_ = 0.0;
 };
 
