@@ -32,7 +32,15 @@
  *
  * xpic_poisson_apply: one application of the transform solve to rhs - mean(rhs), without refinement, whatever the
  * context's kind: phi [nz][ny][nx] from rhs [nz][ny][nx].  The hook that pins the kernels, as xpic_precond_apply pins the
- * preconditioner.  The same refusals; a right-hand side that is not finite is an error.  Overwrites the Gauss vectors. */
+ * preconditioner.  The same refusals; a right-hand side that is not finite is an error.  Overwrites the Gauss vectors.
+ *
+ * xpic_poisson_solve: the refinement itself on rhs - mean(rhs), whatever the context's kind -- the function the clean
+ * calls with XPIC_POISSON_DIRECT, phi from 0, the stopping rule |r|_2 <= tol -> phi, the count of applications and the last
+ * explicitly formed |r|_2.  The hook that pins the second and later applications (the += epilogue, the residual between
+ * them, the "did not halve" exit): not converging is no error here, since the caller asked for a count -- tol = 0,
+ * maxit = k gives exactly k applications while each one halves the residual it was given, and maxit = 1 returns
+ * xpic_poisson_apply's bits.  xpic_poisson_apply's refusals; tol must be finite and >= 0, maxit >= 1.  Overwrites the
+ * Gauss vectors; leaves the kind and xpic_gauss_info's counters as they were. */
 #ifndef XPIC_POISSON_H
 #define XPIC_POISSON_H
 #define XPIC_POISSON_MAX_EXTENT 1024
@@ -43,6 +51,8 @@ extern "C" {
 int xpic_set_poisson_solver(xpic_ctx* ctx, int kind);
 int xpic_get_poisson_solver(xpic_ctx* ctx, int* kind);
 int xpic_poisson_apply(xpic_ctx* ctx, const double* rhs_zyx, double* phi_zyx);
+int xpic_poisson_solve(xpic_ctx* ctx, const double* rhs_zyx, double tol, int maxit, double* phi_zyx, int* applications,
+                       double* rnorm);
 #ifdef __cplusplus
 }
 #endif

@@ -16,6 +16,7 @@ LITERAL = {
     "xpic_set_poisson_solver": ["xpic_ctx*", "int"],
     "xpic_get_poisson_solver": ["xpic_ctx*", "int*"],
     "xpic_poisson_apply": ["xpic_ctx*", "const double*", "double*"],
+    "xpic_poisson_solve": ["xpic_ctx*", "const double*", "double", "int", "double*", "int*", "double*"],
 }
 
 
@@ -67,7 +68,7 @@ def test_library_exports_and_types_the_symbols():
         assert hasattr(lib, name), name
         f = getattr(L, name)
         assert f.restype is C.c_int and list(f.argtypes) == [X.CTYPES[a] for a in LITERAL[name]], name
-    for f in ("set_poisson_solver", "poisson_apply"):
+    for f in ("set_poisson_solver", "poisson_apply", "poisson_solve"):
         assert callable(getattr(X.Context, f)), f
     assert isinstance(X.Context.poisson_solver, property)
 
@@ -87,6 +88,8 @@ def test_null_handle_sweep():
         ctx.poisson_solver
     with refused:
         ctx.poisson_apply(np.ones((2, 2, 3)))
+    with refused:
+        ctx.poisson_solve(np.ones((2, 2, 3)), tol=0.0, maxit=2)
     with pytest.raises(X.XpicError, match="none of"):  # (the package's own refusal of a name it does not know)
         ctx.set_poisson_solver("fft")
     assert ctx.L.seen >= set(LITERAL)

@@ -535,6 +535,16 @@ class PoissonCommands:
         self._ck(self.L.xpic_poisson_apply(self.h, _dp(rhs), _dp(phi)))
         return phi
 
+    def poisson_solve(self, rhs, tol=0.0, maxit=1):
+        """the refinement the "direct" clean runs, on rhs - mean(rhs) [nz][ny][nx] from phi = 0 until |r|_2 <= tol ->
+        (phi, applications, the last explicit |r|_2), whatever poisson_solver is.  Not converging is no error: tol = 0,
+        maxit = k gives k applications while each halves the residual it was given; maxit = 1 is poisson_apply's bits"""
+        rhs = np.ascontiguousarray(rhs, dtype=np.float64).reshape(self.nzl, self.n[1], self.n[0])
+        phi = np.zeros_like(rhs)
+        its, rn = C.c_int(), C.c_double()
+        self._ck(self.L.xpic_poisson_solve(self.h, _dp(rhs), float(tol), int(maxit), _dp(phi), C.byref(its), C.byref(rn)))
+        return phi, its.value, rn.value
+
 
 class Context(LoadCommands, TracerCommands, FieldLineCommands, GaussCommands, EsCommands, PoissonCommands):
     """One z-slab context = one `interfaces::Simulation` backend instance."""

@@ -365,6 +365,7 @@ POISSON_PROTOTYPES = {
     "xpic_set_poisson_solver": ("int", ["xpic_ctx*", "int"]),
     "xpic_get_poisson_solver": ("int", ["xpic_ctx*", "int*"]),
     "xpic_poisson_apply": ("int", ["xpic_ctx*", "const double*", "double*"]),
+    "xpic_poisson_solve": ("int", ["xpic_ctx*", "const double*", "double", "int", "double*", "int*", "double*"]),
 }
 POISSON_SOLVERS = {"cg": 0, "direct": 1}  # enum xpic_poisson_solver
 POISSON_MAX_EXTENT = 1024  # XPIC_POISSON_MAX_EXTENT

@@ -506,30 +506,62 @@ int xpic_get_poisson_solver(xpic_ctx* ctx, int* kind)
   return 0;
 }
 
-int xpic_poisson_apply(xpic_ctx* ctx, const double* rhs_zyx, double* phi_zyx)
+// plane `to` = rhs_zyx - its mean, `stage` the plane the host's values land in (to for none).  The mean in two passes
+// (charge_mean's refinement), taken out before the transform sees the data.
+static int poisson_stage(xpic_ctx* ctx, const double* rhs_zyx, double* stage, double* to)
 {
-  XPIC_CHECK(ctx != nullptr, "null context");
-  XPIC_CHECK(rhs_zyx && phi_zyx, "null argument");
-  XPIC_CALL(poisson_check(ctx));
-  XPIC_CALL(gauss_alloc(ctx));
   const GridDev& g = ctx->g;
-  double *res = plane_of(ctx, kRes), *r = plane_of(ctx, kR);
-  XPIC_HIP(hipMemcpyAsync(res, rhs_zyx, sizeof(double) * g.nown, hipMemcpyHostToDevice, ctx->stream));
-  // the mean in two passes (charge_mean's refinement), taken out before the transform sees the data
+  XPIC_HIP(hipMemcpyAsync(stage, rhs_zyx, sizeof(double) * g.nown, hipMemcpyHostToDevice, ctx->stream));
   const unsigned blocks = red_blocks(g, 4);
   double mean = 0.0;
   for (int pass = 0; pass < 2; ++pass) {
-    hipLaunchKernelGGL(k_gauss_sum, dim3(blocks), dim3(kBlock), 0, ctx->stream, g, res, mean, ctx->red_partial);
+    hipLaunchKernelGGL(k_gauss_sum, dim3(blocks), dim3(kBlock), 0, ctx->stream, g, stage, mean, ctx->red_partial);
     XPIC_HIP(hipGetLastError());
     double sum;
     XPIC_CALL(reduce_to_host(ctx, 1, (int)blocks, 1, true, &sum));
     XPIC_CHECK(std::isfinite(sum), "poisson: the right-hand side is not finite");
     mean += sum / (double)g.nown;
   }
-  hipLaunchKernelGGL(k_gauss_shift, dim3(blocks), dim3(kBlock), 0, ctx->stream, g, res, mean, r);
+  hipLaunchKernelGGL(k_gauss_shift, dim3(blocks), dim3(kBlock), 0, ctx->stream, g, stage, mean, to);
   XPIC_HIP(hipGetLastError());
+  return 0;
+}
+
+int xpic_poisson_apply(xpic_ctx* ctx, const double* rhs_zyx, double* phi_zyx)
+{
+  XPIC_CHECK(ctx != nullptr, "null context");
+  XPIC_CHECK(rhs_zyx && phi_zyx, "null argument");
+  XPIC_CALL(poisson_check(ctx));
+  XPIC_CALL(gauss_alloc(ctx));
+  double* r = plane_of(ctx, kR);
+  XPIC_CALL(poisson_stage(ctx, rhs_zyx, plane_of(ctx, kRes), r));
   XPIC_CALL(poisson_transform_solve(ctx, r, plane_of(ctx, kP), plane_of(ctx, kAp), plane_of(ctx, kPhi), false));
   return scalar_to_host(ctx, plane_of(ctx, kPhi), phi_zyx);
+}
+
+int xpic_poisson_solve(xpic_ctx* ctx, const double* rhs_zyx, double tol, int maxit, double* phi_zyx, int* applications,
+  double* rnorm)
+{
+  XPIC_CHECK(ctx != nullptr, "null context");
+  XPIC_CHECK(rhs_zyx && phi_zyx && applications && rnorm, "null argument");
+  XPIC_CHECK(tol >= 0.0 && std::isfinite(tol), "poisson: tol must be finite and >= 0");
+  XPIC_CHECK(maxit >= 1, "poisson: maxit must be >= 1");
+  XPIC_CALL(poisson_check(ctx));
+  XPIC_CALL(gauss_alloc(ctx));
+  const GridDev& g = ctx->g;
+  double *res = plane_of(ctx, kRes), *phi = plane_of(ctx, kPhi);
+  XPIC_CALL(poisson_stage(ctx, rhs_zyx, plane_of(ctx, kRho), res));
+  // |res|_2^2, which the clean has from its residual kernel: the explicit residual of phi = 0
+  XPIC_CALL(acc_plane<0>(ctx, nullptr, phi));
+  XPIC_CALL(halo_fill(ctx, vector_of(ctx, kPhi), 1));
+  const unsigned sblocks = red_blocks(g, 1);
+  double rr;
+  hipLaunchKernelGGL(k_lap_residual, dim3(sblocks), dim3(kBlock), 0, ctx->stream, g, phi, res, plane_of(ctx, kR), ctx->red_partial);
+  XPIC_HIP(hipGetLastError());
+  XPIC_CALL(reduce_to_host(ctx, 1, (int)sblocks, 1, true, &rr));
+  bool converged; // (not an error here: the caller asked for a count)
+  XPIC_CALL(poisson_direct(ctx, rr, tol, maxit, applications, &converged, rnorm));
+  return scalar_to_host(ctx, phi, phi_zyx);
 }
 
 }  // extern "C"
