@@ -966,4 +966,6 @@ int xpic_probe_copy_bandwidth(xpic_ctx* ctx, int64_t bytes, int reps, double* by
 #include "xpic_es.h"
 /* ---- the direct Poisson solve for the cleans and the XPIC_ES step: a separable Hartley transform */
 #include "xpic_poisson.h"
+/* ---- field spectra on the device: power, axis and shell sums, single modes, a probe that rides with the step */
+#include "xpic_spectrum.h"
 #endif

@@ -167,7 +167,7 @@ _lib = None
 
 def load_library():
     """Loads libxpic_hip.so and types every entry point from PROTOTYPES, LOAD_PROTOTYPES, TRACER_PROTOTYPES,
-    TRACER_MOMENT_PROTOTYPES, FIELD_LINE_PROTOTYPES, GAUSS_PROTOTYPES, ES_PROTOTYPES and POISSON_PROTOTYPES; raises if it has not been built (no fallback path exists).  The xpic_debug_*_stamps symbols of experiment builds are not in the header and stay untyped."""
+    TRACER_MOMENT_PROTOTYPES, FIELD_LINE_PROTOTYPES, GAUSS_PROTOTYPES, ES_PROTOTYPES, POISSON_PROTOTYPES and SPECTRUM_PROTOTYPES; raises if it has not been built (no fallback path exists).  The xpic_debug_*_stamps symbols of experiment builds are not in the header and stay untyped."""
     global _lib
     if _lib is not None:
         return _lib
@@ -176,7 +176,8 @@ def load_library():
                         "xpic_amd has no CPU fallback")
     L = C.CDLL(LIB_PATH)
     for name, (ret, args) in dict(PROTOTYPES, **LOAD_PROTOTYPES, **TRACER_PROTOTYPES, **TRACER_MOMENT_PROTOTYPES,
-                                   **FIELD_LINE_PROTOTYPES, **GAUSS_PROTOTYPES, **ES_PROTOTYPES, **POISSON_PROTOTYPES).items():
+                                   **FIELD_LINE_PROTOTYPES, **GAUSS_PROTOTYPES, **ES_PROTOTYPES, **POISSON_PROTOTYPES,
+                                   **SPECTRUM_PROTOTYPES).items():
         f = getattr(L, name)
         f.restype, f.argtypes = CTYPES[ret], [CTYPES[a] for a in args]
     if L.xpic_version() & VERSION_EXPERIMENT_BIT and os.environ.get("XPIC_ALLOW_EXPERIMENT") != "1":
@@ -546,7 +547,106 @@ class PoissonCommands:
         return phi, its.value, rn.value
 
 
-class Context(LoadCommands, TracerCommands, FieldLineCommands, GaussCommands, EsCommands, PoissonCommands):
+class Spectrum(collections.namedtuple("Spectrum", "axis k_axis shell shell_count k_edges outside outside_count total")):
+    """The reduced spectrum of a scalar: axis[a][i] = the sum of P over the other two indices at index i of axis a (x, y, z),
+    k_axis[a][i] its folded physical wavenumber 2 pi m / (n_a d_a), m in (-n_a/2, n_a/2]; shell[j] the power and
+    shell_count[j] the modes with k_edges[j] <= |k| < k_edges[j+1] (empty arrays without shells); outside, outside_count:
+    the modes in no shell; total = sum_k P = sum_j x(j)^2"""
+
+
+class SpectrumProbe:
+    """A probe of modes that rides with Context.step() (include/xpic_spectrum.h): get() -> (steps [r], F^ [r][nmodes]
+    complex, dropped), reset=True empties it afterwards; close() frees it"""
+
+    def __init__(self, ctx, pid, nmodes):
+        self.ctx, self.id, self.nmodes = ctx, pid, nmodes
+
+    def get(self, reset=False):
+        c = self.ctx
+        rec, drop = C.c_int64(), C.c_int64()
+        c._ck(c.L.xpic_spectrum_probe_get(c.h, self.id, 0, None, None, C.byref(rec), C.byref(drop), 0))
+        steps = np.zeros(rec.value, dtype=np.int64)
+        out = np.zeros((rec.value, self.nmodes, 2))
+        c._ck(c.L.xpic_spectrum_probe_get(c.h, self.id, rec.value, _i64p(steps), _dp(out), C.byref(rec), C.byref(drop), int(reset)))
+        return steps, out[..., 0] + 1j * out[..., 1], drop.value
+
+    def close(self):
+        if self.id is not None:
+            self.ctx._ck(self.ctx.L.xpic_spectrum_probe_destroy(self.ctx.h, self.id))
+            self.id = None
+
+
+class SpectrumCommands:
+    """Field spectra on the device (include/xpic_spectrum.h; the reference has none), as methods of Context.  source: a
+    field id (comp 0, 1 or 2 is then needed), "rho" (the charge density gauss_residual deposits, the mean left in) or a
+    numpy scalar [nz][ny][nx].  F^(k) = sum_j x(j) exp(-2 pi i k.j / n) / sqrt(N) on the node index of the component's own
+    array (no Yee stagger); P = |F^|^2."""
+
+    def _spectrum_source(self, source, comp):
+        """(source id, comp, the host scalar or None)"""
+        if isinstance(source, str):
+            if source not in SPECTRUM_SOURCES or source == "host":
+                raise XpicError("spectrum: %r is no source (a field id, \"rho\" or an array)" % (source,))
+            return SPECTRUM_SOURCES[source], 0, None
+        if isinstance(source, (int, np.integer)):
+            if comp is None:
+                raise XpicError("spectrum: a field source needs comp (0, 1 or 2)")
+            return int(source), int(comp), None
+        scalar = np.ascontiguousarray(source, dtype=np.float64).reshape(self.nzl, self.n[1], self.n[0])
+        return SPECTRUM_SOURCES["host"], 0, scalar
+
+    def spectrum_power(self, source, comp=None):
+        """P [nz][ny][nx], index (kz, ky, kx), unfolded: index n - m is wavenumber -m"""
+        sid, comp, scalar = self._spectrum_source(source, comp)
+        out = np.zeros((self.nzl, self.n[1], self.n[0]))
+        self._ck(self.L.xpic_spectrum_power(self.h, sid, comp, _dp(scalar), _dp(out)))
+        return out
+
+    def spectrum(self, source, comp=None, dk=None, nshell=0, edges=None):
+        """The axis spectra, the total and shells of |k| -> Spectrum.  edges: ascending shell edges in |k| (nshell + 1 of
+        them), or dk and nshell for edges = dk * arange(nshell + 1); neither: no shells"""
+        sid, comp, scalar = self._spectrum_source(source, comp)
+        if edges is None and dk is not None:
+            edges = float(dk) * np.arange(int(nshell) + 1)
+        edges = np.zeros(0) if edges is None else np.ascontiguousarray(edges, dtype=np.float64)
+        ns = max(edges.size - 1, 0) if edges.size else int(nshell)
+        if edges.size and not (edges >= 0.0).all():  # (a NaN too: the edges are |k|)
+            raise XpicError("spectrum: the shell edges are |k| and must be finite and >= 0")
+        e2 = np.ascontiguousarray(edges * edges) if edges.size else None
+        axis = [np.zeros(self.n[0]), np.zeros(self.n[1]), np.zeros(self.nzl)]
+        shell, count, outside, total = np.zeros(max(ns, 0)), np.zeros(max(ns, 0), dtype=np.int64), np.zeros(2), C.c_double()
+        self._ck(self.L.xpic_spectrum(self.h, sid, comp, _dp(scalar), _dp(axis[0]), _dp(axis[1]), _dp(axis[2]), ns, _dp(e2),
+                                      _dp(shell) if ns > 0 else None, _i64p(count) if ns > 0 else None, _dp(outside),
+                                      C.byref(total)))
+        k_axis = []
+        for a, n in enumerate((self.n[0], self.n[1], self.nzl)):
+            m = np.arange(n)
+            k_axis.append(2.0 * np.pi * np.where(m <= n // 2, m, m - n) / (n * self.d[a]))
+        return Spectrum(axis, k_axis, shell, count, edges, outside[0], int(outside[1]), total.value)
+
+    def spectrum_modes(self, source, modes, comp=None):
+        """F^ (complex [nmodes]) of the signed mode numbers modes [nmodes][3] = (m_x, m_y, m_z)"""
+        sid, comp, scalar = self._spectrum_source(source, comp)
+        modes = np.ascontiguousarray(modes, dtype=np.int32).reshape(-1, 3)
+        out = np.zeros((modes.shape[0], 2))
+        self._ck(self.L.xpic_spectrum_modes(self.h, sid, comp, _dp(scalar), modes.shape[0], _i32p(modes), _dp(out)))
+        return out[:, 0] + 1j * out[:, 1]
+
+    def spectrum_probe(self, source, modes, comp=None, every=1, capacity=4096):
+        """A passive probe of the modes [nmodes][3] of a field component or of "rho": after every every-th step() -- after
+        the riding clean and the attached tracer sets -- one row (step, F^ per mode) goes to a device buffer of `capacity`
+        rows; a full buffer counts what it drops -> SpectrumProbe"""
+        if not isinstance(source, (str, int, np.integer)):
+            raise XpicError("spectrum_probe: an array is no probe source (a field id or \"rho\")")
+        sid, comp, _ = self._spectrum_source(source, comp)
+        modes = np.ascontiguousarray(modes, dtype=np.int32).reshape(-1, 3)
+        pid = C.c_int()
+        self._ck(self.L.xpic_spectrum_probe_create(self.h, sid, comp, modes.shape[0], _i32p(modes), int(every), int(capacity),
+                                                   C.byref(pid)))
+        return SpectrumProbe(self, pid.value, modes.shape[0])
+
+
+class Context(LoadCommands, TracerCommands, FieldLineCommands, GaussCommands, EsCommands, PoissonCommands, SpectrumCommands):
     """One z-slab context = one `interfaces::Simulation` backend instance."""
 
     def __init__(self, scheme, n, d, dt, device=0, rank=0, nranks=1, self_ring=False):

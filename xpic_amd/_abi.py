@@ -369,3 +369,19 @@ POISSON_PROTOTYPES = {
 }
 POISSON_SOLVERS = {"cg": 0, "direct": 1}  # enum xpic_poisson_solver
 POISSON_MAX_EXTENT = 1024  # XPIC_POISSON_MAX_EXTENT
+
+# the entry points of include/xpic_spectrum.h (field spectra: power, axis and shell sums, single modes, the probe that rides
+# with the step), typed by load_library() as PROTOTYPES' are; tests/test_abi_spectrum.py holds them to that header
+_SOURCE = ["xpic_ctx*", "int", "int", "const double*"]
+SPECTRUM_PROTOTYPES = {
+    "xpic_spectrum_power": ("int", _SOURCE + ["double*"]),
+    "xpic_spectrum": ("int", _SOURCE + ["double*", "double*", "double*", "int", "const double*", "double*", "int64_t*", "double*",
+                                        "double*"]),
+    "xpic_spectrum_modes": ("int", _SOURCE + ["int", "const int32_t*", "double*"]),
+    "xpic_spectrum_probe_create": ("int", ["xpic_ctx*", "int", "int", "int", "const int32_t*", "int", "int64_t", "int*"]),
+    "xpic_spectrum_probe_get": ("int", ["xpic_ctx*", "int", "int64_t", "int64_t*", "double*", "int64_t*", "int64_t*", "int"]),
+    "xpic_spectrum_probe_destroy": ("int", ["xpic_ctx*", "int"]),
+}
+SPECTRUM_SOURCES = {"host": 100, "rho": 101}  # enum xpic_spectrum_source (a field id is a source too)
+SPECTRUM_MAX_SHELLS = 2048  # XPIC_SPECTRUM_MAX_SHELLS
+SPECTRUM_MAX_PROBES = 16    # XPIC_SPECTRUM_MAX_PROBES

@@ -440,6 +440,7 @@ int xpic_destroy(xpic_ctx* ctx)
   tracers_free(ctx);
   gauss_free(ctx);
   poisson_free(ctx);
+  spectrum_free(ctx);
   (void)hipFree(ctx->es_rho);
   (void)hipFree(ctx->abar32); (void)hipFree(ctx->abar_work); (void)hipFree(ctx->abar_r);
   (void)hipFree(ctx->lrow_buf[0]); (void)hipFree(ctx->lrow_buf[1]);
@@ -878,6 +879,7 @@ int xpic_step(xpic_ctx* ctx, int* ksp_iterations)
   ctx->steps_done += 1;
   if (rc == 0 && ctx->gauss_every > 0 && ctx->steps_done % ctx->gauss_every == 0) rc = gauss_ride(ctx); // div E = rho restored
   if (rc == 0 && ctx->tracers) rc = tracers_ride(ctx); // the attached tracer sets, on the E and B the step leaves behind
+  if (rc == 0 && ctx->spectrum) rc = spectrum_ride(ctx); // the mode probes, last: they read and change nothing a step reads
   return rc;
 }
 

@@ -196,6 +196,7 @@ struct ProfileEntry {
 };
 
 struct TracerSets; // tracers.hip: the tracer sets of a context
+struct SpectrumState; // spectrum.hip: the partial sums and the probes of a context
 // tracer_moments.hip: doubles of a workgroup's private copy of a moment's region: 72 KiB of the CU's 160 KiB of LDS, so that
 // two workgroups and their static arrays fit on a CU
 constexpr int kTracerMomentLds = 9216;
@@ -275,6 +276,7 @@ struct xpic_ctx {
   int poisson_kind = XPIC_POISSON_CG;
   double* poisson_H[3] = {nullptr, nullptr, nullptr};
   double* poisson_lam[3] = {nullptr, nullptr, nullptr};
+  xpic::SpectrumState* spectrum = nullptr; // spectrum.hip: made by the first spectrum call; null: xpic_step has no probe to run
   // es.hip: the electrostatic step's charge accumulator (a stored vector whose component 0 is rho: the halo exchange adds whole
   // vectors), made with an XPIC_ES context; null on every other scheme
   double* es_rho = nullptr;
@@ -436,7 +438,17 @@ int gauss_clean_given(xpic_ctx* c, const double* rho_vec, double rtol, double at
 // the refusals of a context it cannot serve (ghost planes, an extent above the cap); frees the tables (xpic_destroy)
 int poisson_check(const xpic_ctx* c);
 int poisson_transform_solve(xpic_ctx* c, const double* rhs, double* w0, double* w1, double* out, bool add);
+int poisson_forward(xpic_ctx* c, const double* in, double* w0, double* w1); // w0 = the separable transform of in (x, y, z)
+int poisson_tables(xpic_ctx* c); // the tables, made now (a probe sizes its memory when it is created)
 void poisson_free(xpic_ctx* c);
+
+// spectrum.hip (include/xpic_spectrum.h; an extension: the reference has no spectral diagnostic): the probes that ride with
+// xpic_step (only when c->spectrum), after the clean and the tracer sets; frees the partial sums and the probes (xpic_destroy).
+// gauss.hip lends it the Gauss vectors' planes (stage, w0, w1: r, p, Ap) and the charge density of the residual's own deposit
+int spectrum_ride(xpic_ctx* c);
+void spectrum_free(xpic_ctx* c);
+int gauss_lend_planes(xpic_ctx* c, double** stage, double** w0, double** w1);
+int gauss_charge_plane(xpic_ctx* c, const double** rho); // all sorts + the background, the mean left in
 
 // es.hip: the electrostatic scheme's particle phase of one sort -- gather at r, kick, full move, deposit of the new position
 // into component 0 of rho_vec (added to what is there; ghost planes included, the caller adds them to their owners)

@@ -212,9 +212,9 @@ int charge_mean(xpic_ctx* c, double* mean, bool refine)
   return 0;
 }
 
-// plane kRho = the sorts' charge densities in creation order (+ the background); *mean = its mean over the whole box.
+// plane kRho = the sorts' charge densities in creation order (+ the background), the mean left in.
 // given: the sorts' sum is handed in (component 0 of a stored vector) and nothing is deposited here.
-int collect_charge(xpic_ctx* c, double* mean, const double* given = nullptr)
+int deposit_charge(xpic_ctx* c, const double* given = nullptr)
 {
   double* rho = plane_of(c, kRho);
   double* tmp = c->field[XPIC_W2]; // the deposit's scratch vector, as xpic_charge_density's
@@ -231,6 +231,13 @@ int collect_charge(xpic_ctx* c, double* mean, const double* given = nullptr)
     }
   if (c->gauss_bg) XPIC_CALL(first ? acc_plane<1>(c, c->gauss_bg, rho) : acc_plane<2>(c, c->gauss_bg, rho));
   else if (first) XPIC_CALL(acc_plane<0>(c, nullptr, rho));
+  return 0;
+}
+
+// deposit_charge, and *mean = the mean of plane kRho over the whole box
+int collect_charge(xpic_ctx* c, double* mean, const double* given = nullptr)
+{
+  XPIC_CALL(deposit_charge(c, given));
   return charge_mean(c, mean, given != nullptr);
 }
 
@@ -397,6 +404,23 @@ int gauss_ride(xpic_ctx* c)
 }
 
 int gauss_reserve(xpic_ctx* c) { return gauss_alloc(c); }
+
+// spectrum.hip's work planes: r to stage a host scalar in, p and Ap for the passes, as xpic_poisson_apply takes them.  No
+// clean and no step carries state in them from one call to the next.
+int gauss_lend_planes(xpic_ctx* c, double** stage, double** w0, double** w1)
+{
+  XPIC_CALL(gauss_alloc(c));
+  *stage = plane_of(c, kR); *w0 = plane_of(c, kP); *w1 = plane_of(c, kAp);
+  return 0;
+}
+
+int gauss_charge_plane(xpic_ctx* c, const double** rho)
+{
+  XPIC_CALL(gauss_alloc(c));
+  XPIC_CALL(deposit_charge(c));
+  *rho = plane_of(c, kRho);
+  return 0;
+}
 
 int gauss_clean_given(xpic_ctx* c, const double* rho_vec, double rtol, double atol, int maxit, int* iterations)
 {

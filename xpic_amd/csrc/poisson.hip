@@ -191,6 +191,16 @@ int poisson_transform_solve(xpic_ctx* c, const double* rhs, double* w0, double* 
   return add ? pass<kAdd>(c, 0, w0, out) : pass<kStore>(c, 0, w0, out);
 }
 
+// the three forward passes alone, x, y, z as the solve makes them: w0 = Hz Hy Hx in (include/xpic_spectrum.h).  in, w0, w1:
+// the owned nodes of three distinct scalar planes; in is only read, w1 is overwritten.
+int poisson_forward(xpic_ctx* c, const double* in, double* w0, double* w1)
+{
+  XPIC_CALL(poisson_tables(c));
+  XPIC_CALL(pass<kStore>(c, 0, in, w0));
+  XPIC_CALL(pass<kStore>(c, 1, w0, w1));
+  return pass<kStore>(c, 2, w1, w0);
+}
+
 void poisson_free(xpic_ctx* c)
 {
   for (int a = 0; a < 3; ++a) {

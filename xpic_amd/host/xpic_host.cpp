@@ -1059,6 +1059,44 @@ PetscErrorCode FieldLines::diagnose(PetscInt t)
   return 0;
 }
 
+FieldSpectrum::FieldSpectrum(const std::string& out_dir, const std::string& table, interfaces::Simulation& simulation, int source,
+  int comp, std::vector<int32_t> modes, std::vector<double> edges2, PetscInt period)
+  : simulation(simulation), out_dir_(out_dir), table_(table), source_(source), comp_(comp), modes_(std::move(modes)),
+    edges2_(std::move(edges2)), period_(period)
+{
+}
+
+// the reduced spectrum of the source as it stands: axis_x, axis_y, axis_z, shell as raw float64; the modes to the table
+PetscErrorCode FieldSpectrum::diagnose(PetscInt t)
+{
+  if (period_ > 0 && t % period_ != 0) return 0;
+  const int nshell = edges2_.empty() ? 0 : (int)edges2_.size() - 1;
+  std::vector<double> out((size_t)geom_nx + geom_ny + geom_nz + nshell);
+  double* ax = out.data();
+  HIPCALL(xpic_spectrum(simulation.ctx, source_, comp_, nullptr, ax, ax + geom_nx, ax + geom_nx + geom_ny, nshell,
+    nshell ? edges2_.data() : nullptr, nshell ? ax + geom_nx + geom_ny + geom_nz : nullptr, nullptr, nullptr, nullptr));
+  make_dirs(out_dir_);
+  std::ofstream f(out_dir_ + "/" + FieldView::format_time(t), std::ios::binary);
+  if (!f) throw std::runtime_error("Cannot open " + out_dir_ + "/" + FieldView::format_time(t));
+  f.write(reinterpret_cast<const char*>(out.data()), (std::streamsize)(out.size() * sizeof(double)));
+  if (modes_.empty()) return 0;
+  const int nmodes = (int)(modes_.size() / 3);
+  std::vector<double> re_im(2 * (size_t)nmodes);
+  HIPCALL(xpic_spectrum_modes(simulation.ctx, source_, comp_, nullptr, nmodes, modes_.data(), re_im.data()));
+  make_dirs(CONFIG().out_dir + "/temporal");
+  std::ofstream table(table_, started_ ? std::ios::app : std::ios::trunc);
+  if (!table) throw std::runtime_error("Cannot open " + table_);
+  started_ = true;
+  char buf[40];
+  table << t;
+  for (double v : re_im) {
+    std::snprintf(buf, sizeof(buf), " % .17e", v);
+    table << buf;
+  }
+  table << "\n";
+  return 0;
+}
+
 namespace {
 
 std::unique_ptr<interfaces::Diagnostic> build_field_lines(interfaces::Simulation& simulation, const Configuration::json_t& info)
@@ -1091,6 +1129,39 @@ std::unique_ptr<interfaces::Diagnostic> build_field_lines(interfaces::Simulation
   const std::string dir = CONFIG().out_dir + "/field_lines" + (info.contains("name") ? "_" + info.at("name").as_string() : "");
   LOG("  field lines diagnostic is added for " << field << ": " << seeds.size() / 3 << " points, period " << period << " [dt]");
   return std::make_unique<FieldLines>(dir, simulation, id, std::move(seeds), params, open, region, period);
+}
+
+std::unique_ptr<interfaces::Diagnostic> build_field_spectrum(interfaces::Simulation& simulation, const Configuration::json_t& info)
+{
+  using interfaces::Builder;
+  const std::string field = info.at("field").as_string();
+  const int source = field == "rho" ? (int)XPIC_SPECTRUM_RHO : simulation.get_named_vector(field);
+  const int comp = field == "rho" ? 0 : info.at("comp").as_int();
+  if (comp < 0 || comp > 2) throw std::runtime_error("FieldSpectrum comp should be 0, 1 or 2");
+  std::vector<int32_t> modes;
+  if (info.contains("modes"))
+    for (auto&& m : info.at("modes").arr) {
+      if (m.arr.size() != 3) throw std::runtime_error("FieldSpectrum modes are [m_x, m_y, m_z]");
+      for (int i = 0; i < 3; ++i) modes.push_back((int32_t)m.arr[i].as_int());
+    }
+  std::vector<double> edges2;
+  if (info.contains("dk") || info.contains("nshell")) {
+    const double dk = info.at("dk").as_double();
+    const int nshell = info.at("nshell").as_int();
+    if (!(dk > 0.0) || nshell < 1 || nshell > XPIC_SPECTRUM_MAX_SHELLS)
+      throw std::runtime_error("FieldSpectrum takes dk > 0 and nshell in 1 .. " + std::to_string(XPIC_SPECTRUM_MAX_SHELLS));
+    for (int j = 0; j <= nshell; ++j) {
+      const double e = dk * (double)j;
+      edges2.push_back(e * e);
+    }
+  }
+  const PetscInt period = info.contains("diagnose_period") ? ROUND_STEP(Builder::parse_value(info.at("diagnose_period")), dt)
+                                                           : diagnose_period;
+  const std::string suffix = info.contains("name") ? "_" + info.at("name").as_string() : "";
+  LOG("  field spectrum diagnostic is added for " << field << ": " << modes.size() / 3 << " modes, "
+    << (edges2.empty() ? 0 : edges2.size() - 1) << " shells, period " << period << " [dt]");
+  return std::make_unique<FieldSpectrum>(CONFIG().out_dir + "/field_spectrum" + suffix,
+    CONFIG().out_dir + "/temporal/field_modes" + suffix + ".txt", simulation, source, comp, std::move(modes), std::move(edges2), period);
 }
 
 void parse_region(const Configuration::json_t& info, FieldView::Region& region, std::string& suffix, const std::string& name);
@@ -1307,8 +1378,9 @@ PetscErrorCode build_diagnostics(interfaces::Simulation& simulation,
     }
     else if (name == "TracedParticles") result.emplace_back(build_traced_particles(simulation, info));
     else if (name == "FieldLines") result.emplace_back(build_field_lines(simulation, info));
+    else if (name == "FieldSpectrum") result.emplace_back(build_field_spectrum(simulation, info));
     else throw std::runtime_error("Unknown diagnostic name " + name +
-      " (HIP backends: FieldView, DistributionMoment, VelocityDistribution, TracedParticles, FieldLines)");
+      " (HIP backends: FieldView, DistributionMoment, VelocityDistribution, TracedParticles, FieldLines, FieldSpectrum)");
   }
   return 0;
 }

@@ -531,6 +531,29 @@ private:
   PetscInt period_;
 };
 
+// EXTENSION (not reference behaviour): "FieldSpectrum", the spectrum of a field component or of the charge density on the
+// device (include/xpic_spectrum.h).  Keys: "field" ("E" | "B" | "B0" | "rho"), "comp" (0, 1, 2; not read for "rho"), optional
+// "modes" (a list of signed [m_x, m_y, m_z]), optional "dk" and "nshell" (shells of |k| with the edges dk * j, j = 0 .. nshell),
+// "diagnose_period" (default: the geometry's), "name" (a suffix of the directory and of the table).  Every diagnose_period
+// <out_dir>/field_spectrum[_name]/<time> is written as raw float64: axis_x[nx], axis_y[ny], axis_z[nz], then shell[nshell];
+// with "modes", a row "t Re Im Re Im .." (%.17e) is appended to temporal/field_modes[_name].txt.  The class exists only where
+// the key is present.
+class FieldSpectrum final : public interfaces::Diagnostic {
+public:
+  FieldSpectrum(const std::string& out_dir, const std::string& table, interfaces::Simulation& simulation, int source, int comp,
+    std::vector<int32_t> modes, std::vector<double> edges2, PetscInt period);
+  PetscErrorCode diagnose(PetscInt t) override;
+
+private:
+  interfaces::Simulation& simulation;
+  std::string out_dir_, table_;
+  int source_, comp_;
+  std::vector<int32_t> modes_;
+  std::vector<double> edges2_;
+  PetscInt period_;
+  bool started_ = false;
+};
+
 // ---- restart files (src/diagnostics/simulation_backup.cpp:30-160): <out_dir>/<t>/{E,B,B0} as PETSc binary Vecs
 // (big endian: int32 VEC_FILE_CLASSID = 1211214, int32 n, n doubles in natural [z][y][x][c] order), particles as
 // <sort_name> = raw big-endian doubles {r, p} per particle and <sort_name>.numparts = one big-endian int32
